@@ -13,7 +13,15 @@ steps, then K timed steps bracketed by barrier + device sync; the max over ranks
 c1_paths: the reference's per-order SubmitOrder + SQLite path, the build's SubmitOrder -> slice ->
 GPU -> batched-ingest path and the CPU oracle, on the C1 1M-order stream.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5]
+A plain run does what the headline figure needs and no more: set-up, W warmup steps, the K timed
+steps, the result line. --full adds everything else the benchmark measures or checks, after the timed
+region and never in `value`: the oracle replay of the last launch group (fills_check), the pipelined
+host path (e2e), the native CPU baseline sweep, c1's c1_paths and the sharded-deployment leg (cluster);
+the line carries null for what a plain run left out. --dump-outputs DIR writes the last timed step's
+outputs (the results and the tape a caller of that step receives) as DIR/results.npy and DIR/fills.npy;
+the stream is seeded, so two builds run with the same arguments can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 """
 from __future__ import annotations
@@ -34,6 +42,7 @@ import matching_engine_amd as me  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level parameters)
 BYTES_PER_ORDER = 48   # 32 B record read + 16 B resting insert / cancel
 BYTES_PER_FILL = 48    # 32 B tape record + 16 B maker-slot RMW
+RESTING_CAP = 42 << 20  # largest max_resting sized from the stream's length: the default run's 672 x 65,536 orders
 
 
 # Per-workload shape. Weak scaling: symbols and batch grow with N, except config 4
@@ -70,6 +79,12 @@ def parse():
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS),
                     help="c2 (default) = BASELINE configs[1], the metric's workload; c3/c4/c5 = the other "
                          "BASELINE configs as secondary lines (DESIGN.md §7)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run, after the timed region, what the headline figure does not need: the oracle "
+                         "fills check, the pipelined host path, the CPU baseline sweep, c1_paths and the cluster leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (per-record results and fill tape of the last timed "
+                         "batch) to DIR/results.npy and DIR/fills.npy as float64, one column per field")
     ap.add_argument("--symbols-per-gpu", type=int, default=None)
     ap.add_argument("--levels", type=int, default=None,
                     help="window L override (experiments: L > 128 runs the sort path; with ME_HOT_MIN=1 every "
@@ -84,9 +99,10 @@ def parse():
                     help="thread counts of the native CPU baseline (every core of the affinity mask is added, "
                          "SURVEY.md §8(d)); value = the best")
     ap.add_argument("--cpu-warmup", type=int, default=4, help="untimed stream batches before the CPU sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-fills-check", action="store_true", help="skip the post-run oracle check of the last group")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (and c1_paths)")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the pipelined host path")
+    ap.add_argument("--no-fills-check", action="store_true",
+                    help="with --full: skip the post-run oracle check of the last group")
     ap.add_argument("--fills-check-max", type=int, default=24_000_000,
                     help="largest oracle replay (orders) to check (config 4's 20M seeded orders included)")
     ap.add_argument("--e2e-steps", type=int, default=384,
@@ -99,9 +115,9 @@ def parse():
     ap.add_argument("--cluster-steps", type=int, default=None,
                     help="global slices run after the timed loop through the C++ sharded deployment "
                          "(include/me_cluster.h: split on rank 0, RCCL scatter, match, RCCL gather of tapes and "
-                         "results, merge by taker seq); reported beside value, never in it. Default: 16 at N > 1 "
-                         "or with --workload c3, else 0. c3's slices have config 3's global shape (1,048,576 "
-                         "orders over 100,000 symbols) at every N")
+                         "results, merge by taker seq); reported beside value, never in it. Default: with --full, "
+                         "16 at N > 1 or with --workload c3; else 0. c3's slices have config 3's global shape "
+                         "(1,048,576 orders over 100,000 symbols) at every N")
     ap.add_argument("--traffic-from", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="JSON {bytes_per_order: ...} from tools/gpu/pmc_traffic_wl.sh for roofline.traffic (c2; the "
                          "k_match_reg measurement when the engine runs c2 without grouped aggregate launches)")
@@ -240,6 +256,21 @@ def check_fills(eng, seeds, batches, ids, args):
         ob.close()
     return {"checked": True, "batches": g, "orders": orders, "fills": fills, "mismatched_batches": bad,
             "how": "the last launch group's results and tapes vs oracle/oracle_book.cpp replaying the stream"}
+
+
+def dump_outputs(eng, n, out_dir, world, rank):
+    """--dump-outputs: what the last timed step handed its caller — the per-record results and the fill
+    tape of the last timed batch (n records, the last batch of the last launch group) — as float64 arrays,
+    one column per field in the dtype's order (every field is an integer below 2^53, so float64 holds it
+    exactly). At N > 1 every rank writes its shard's arrays with a _rank<r> suffix."""
+    res, fills = eng.fetch_group_outputs(eng.last_group_size() - 1, n)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a, fields in (("results", res, ("filled_qty", "remaining_qty", "fill_count", "tape_offset", "status",
+                                              "reason")),
+                            ("fills", fills, ("taker_seq", "maker_seq", "price_q4", "qty", "symbol"))):
+        cols = np.stack([a[f].astype(np.float64) for f in fields], axis=1)
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), cols)
 
 
 def cpu_baseline(args):
@@ -514,8 +545,8 @@ def main():
 
     nb = args.warmup + args.steps
     n_cluster = args.cluster_steps if args.cluster_steps is not None else (
-        16 if world > 1 or (args.workload == "c3" and not args.shape_override) else 0)
-    n_e2e = 0 if args.no_e2e else args.e2e_steps
+        16 if args.full and (world > 1 or (args.workload == "c3" and not args.shape_override)) else 0)
+    n_e2e = args.e2e_steps if args.full and not args.no_e2e else 0
     sc, gbase, ids, batches, positions, global_orders, seeds, whole = build_rank_batches(
         args, world, rank, nb + n_e2e, 0 if args.workload == "c3" else n_cluster)
     csc, cbase = sc, gbase
@@ -528,10 +559,20 @@ def main():
     e2e_batches = batches[nb:]
     batches = batches[:nb]
     total_local = sum(len(b) for b in batches + e2e_batches)
+    if not args.full and not args.no_e2e:
+        # a plain run generates no host-path batches but sizes the engine as if it had (their share at the
+        # timed batches' mean length), so the timed steps run on the same engine with and without --full
+        total_local += args.e2e_steps * total_local // max(nb, 1)
     n_seed = sum(len(b) for b in seeds)
+    # max_resting follows the stream's length (no submit ever has to wait for a resting count) up to
+    # RESTING_CAP: the engine's HBM pools grow with it (with 32-batch launch groups, 96 scratch sets and 32
+    # tapes of max_resting fills each: a 4,000-step run sized by its length ends in hipMalloc's out of
+    # memory), so a longer run keeps the cap and admission leans on the device's published count instead
+    # (admission_rank0.exact_counts says how often a submit had to wait for an exact one)
+    stream_resting = min(max(total_local // 3, sum(len(b) for b in batches)), RESTING_CAP)
     eng = me.Engine(len(ids), sc.levels, base,
                     max_batch=max(len(b) for b in batches + e2e_batches + seeds) + 1,
-                    max_resting=max(total_local // 3, sum(len(b) for b in batches)) + n_seed + 65536, seq_ring=args.seq_ring,
+                    max_resting=stream_resting + n_seed + 65536, seq_ring=args.seq_ring,
                     device=local, symbol_ids=ids, batches_per_launch=args.batches_per_launch)
     if seeds:
         progress(f"seeding {n_seed} resting orders (untimed)")
@@ -588,11 +629,14 @@ def main():
         if traffic_per_order:
             traffic = traffic_per_order * tm["orders"] / timed
 
+    if args.dump_outputs:  # (reads the last launch group's outputs; nothing runs on the engine)
+        dump_outputs(eng, len(batches[-1]), args.dump_outputs, world, rank)
+
     # fills check (after the timed region, before anything else runs on the engine): the oracle replays
     # this rank's stream from the start (seeded books, warmup, timed batches) and every batch of the last
     # timed launch group — its results and tape — must equal it bit for bit; the metric's "fills bit-exact"
     # is this check plus the -m gpu parity suite
-    fills_check = check_fills(eng, seeds, batches, ids, args) if not args.no_fills_check else None
+    fills_check =check_fills(eng, seeds, batches, ids, args) if args.full and not args.no_fills_check else None
     bad_all = allreduce(float(fills_check["mismatched_batches"] if fills_check and fills_check["checked"] else 0),
                         world, SUM, local)
 
@@ -623,8 +667,9 @@ def main():
 
     line = None
     if rank == 0:
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args)
-        c1 = c1_paths(args) if (args.workload == "c1" and world == 1 and not args.no_cpu_baseline) else None
+        cpu_legs = args.full and not args.no_cpu_baseline and world == 1
+        cpu = cpu_baseline(args) if cpu_legs else None
+        c1 = c1_paths(args) if cpu_legs and args.workload == "c1" else None
         line = {
             "metric": "orders matched/sec (whole node); fills bit-exact vs CPU oracle",
             "value": orders_all / job_time,
@@ -632,6 +677,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": job_time / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",

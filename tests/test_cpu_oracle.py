@@ -52,8 +52,8 @@ def test_price_golden_vectors_product(me):
 
 def test_price_golden_vectors_regenerate_from_reference(orc):
     """Re-run the reference's own normalize_to_q4 (oracle/_ref) and compare with the fixture."""
-    if not os.path.exists("/root/reference/include/domain/price.hpp"):
-        pytest.skip("reference tree absent (GPU box): fixture is the pin")
+    if not os.path.exists(orc.REF_PRICE):
+        pytest.skip("oracle/_ref/ref_price not built (build() makes it where the reference tree is): fixture is the pin")
     cases = json.load(open(os.path.join(GOLD, "price_q4.json")))["cases"]
     outs = orc.ref_normalize_many([(c["price"], c["scale"]) for c in cases])
     for c, o in zip(cases, outs):

@@ -18,6 +18,6 @@ for spec in "$@"; do
   envs=(); rest=()
   for t in $spec; do if [[ $t == *=* ]]; then envs+=("$t"); else rest+=("$t"); fi; done
   wl=${rest[0]:-c2}; k=${rest[1]:-20}; w=${rest[2]:-5}
-  env "${envs[@]}" timeout -k 10 400 python3 bench.py --workload $wl --steps $k --warmup $w --no-cpu-baseline --no-e2e $BENCH_ARGS > $O/b$i.json 2> $O/b$i.err || { echo "BENCH_FAIL $spec"; tail -20 $O/b$i.err; exit 1; }
+  env "${envs[@]}" timeout -k 10 400 python3 bench.py --workload $wl --steps $k --warmup $w --full --no-cpu-baseline --no-e2e $BENCH_ARGS > $O/b$i.json 2> $O/b$i.err || { echo "BENCH_FAIL $spec"; tail -20 $O/b$i.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/b$i.json')); print('$spec:', round(d['value']/1e6,2), 'M/s', 'kernel_ms', round(d['kernel_match_ms_avg'],3), d['build'])"
 done

@@ -7,7 +7,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-B="python3 $R/bench.py --workload c4 --steps 6 --warmup 2 --no-cpu-baseline --no-e2e --traffic-from ''"
+B="python3 $R/bench.py --workload c4 --steps 6 --warmup 2 --full --no-cpu-baseline --no-e2e --traffic-from ''"
 run() { timeout -s KILL 300 rocprofv3 --pmc $2 --kernel-include-regex k_match_hot --output-format csv -d $O/$1 -o pmc -- $B > $O/$1.log 2>&1 || { echo "PMC_FAIL $1"; tail -5 $O/$1.log; exit 1; }; }
 run sq1 "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM" &&
 run sq2 "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_WAVES SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_WAIT_INST_LDS" || exit 1

@@ -3,7 +3,7 @@
 set -o pipefail
 TAG=${1:-pmcc1}
 O=gpurun_out/$TAG; mkdir -p $O; export TMPDIR=/tmp
-B="python3 bench.py --workload c1 --steps 6 --warmup 2 --no-cpu-baseline --no-e2e"
+B="python3 bench.py --workload c1 --steps 6 --warmup 2 --full --no-cpu-baseline --no-e2e"
 run() { timeout -s KILL 200 rocprofv3 --pmc $2 --kernel-include-regex "$3" --output-format csv -d $O/$1 -o pmc -- $B > $O/$1.log 2>&1 || { echo "PMC_FAIL $1"; tail -5 $O/$1.log; exit 1; }; }
 run c1w1 "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM" k_agg_walk &&
 run c1w2 "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_WAVES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS" k_agg_walk || exit 1

@@ -40,7 +40,7 @@ for step in "$@"; do
     if [ $rc -ne 0 ]; then echo TESTS_FAIL; grep -E "^E |FAILED|Error" $O/pytest_gpu.log | head -30; exit 1; fi
     ;;
   bench)
-    timeout -k 10 400 python3 bench.py --workload $wl --steps $k --warmup $w $BENCH_ARGS > $O/bench_${wl}_$k.json 2> $O/bench_${wl}_$k.err || { echo "BENCH_FAIL $wl"; tail -20 $O/bench_${wl}_$k.err; exit 1; }
+    timeout -k 10 400 python3 bench.py --workload $wl --steps $k --warmup $w --full $BENCH_ARGS > $O/bench_${wl}_$k.json 2> $O/bench_${wl}_$k.err || { echo "BENCH_FAIL $wl"; tail -20 $O/bench_${wl}_$k.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/bench_${wl}_$k.json')); print('$wl K=$k', round(d['value']/1e6,1), 'M/s', d['build'], 'frac', round(d['roofline']['frac'],4))"
     ;;
   trace)
@@ -73,7 +73,7 @@ for step in "$@"; do
     python3 $R/tools/prof_summary.py sq $O/sq_${wl}_1 $O/sq_${wl}_2 > $O/sq_$wl.txt && cat $O/sq_$wl.txt
     ;;
   cpu)
-    timeout -k 10 600 python3 bench.py --workload $wl --steps $k --warmup $w --no-e2e $BENCH_ARGS > $O/cpu_$wl.json 2> $O/cpu_$wl.err || { echo "CPU_FAIL $wl"; tail -20 $O/cpu_$wl.err; exit 1; }
+    timeout -k 10 600 python3 bench.py --workload $wl --steps $k --warmup $w --full --no-e2e $BENCH_ARGS > $O/cpu_$wl.json 2> $O/cpu_$wl.err || { echo "CPU_FAIL $wl"; tail -20 $O/cpu_$wl.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/cpu_$wl.json')); c=d['cpu_baseline']; print('$wl GPU', round(d['value']/1e6,1), 'M/s; CPU', round(c['value']/1e6,2), 'M/s on', c['cores'], 'threads; 1 core', round(c.get('single_core_value', c['value'])/1e6,2))"
     ;;
   *) echo "unknown step $step"; exit 2 ;;
