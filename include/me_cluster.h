@@ -62,7 +62,9 @@ typedef struct me_cluster_config {
 typedef struct me_shard_ops {
   void* ctx;
   uint64_t max_resting;  /* resting orders it holds at most */
-  /* may be NULL (always admits): would a part with n_rest LIMIT records be admitted? */
+  /* may be NULL (always admits): would a part with n_rest records that may rest be admitted? (NEW LIMITs with
+   * time in force GTC or POST_ONLY: the root counts them while splitting; the kind byte, time-in-force bits
+   * included, travels untouched through split and merge) */
   int (*admit)(void* ctx, uint64_t n_rest, int* ok);
   /* me_collect's contract: outputs valid until the next call */
   int (*match)(void* ctx, const me_order_soa* part, size_t n, const me_fill** fills, size_t* n_fills,

@@ -58,12 +58,31 @@ enum {
   ME_RJ_BAD_SYMBOL = 4,    /* symbol id >= num_symbols */
   ME_RJ_UNKNOWN_ORDER = 5, /* CANCEL target is not a live resting order of this symbol */
   ME_RJ_BAD_SEQ = 6,       /* seq == 0 (no OID is 0: the counter starts at 1, storage.cpp:254-267) */
-  ME_RJ_CAPACITY = 7       /* service only: a LIMIT the shard could not admit while its books hold
+  ME_RJ_CAPACITY = 7,      /* service only: a LIMIT the shard could not admit while its books hold
                               max_resting orders (me_service.h; never produced by the engine) */
+  ME_RJ_WOULD_CROSS = 8,   /* a POST_ONLY LIMIT whose price reaches the opposite side's best price */
+  ME_RJ_BAD_TIF = 9        /* POST_ONLY on a MARKET */
 };
+/* Time in force / execution instruction of a NEW record (bits 4-5 of the kind byte, DESIGN.md §2;
+ * build extension, the reference has none). CANCEL records ignore it.
+ *   GTC        a LIMIT rests its remainder, a MARKET drops it (the behaviour without the bits).
+ *   IOC        crosses exactly as a LIMIT at its price would; the remainder is discarded and never
+ *              rests: FILLED, or CANCELED with remaining_qty = the discarded part (the MARKET
+ *              convention). A no-op on a MARKET.
+ *   FOK        fillable when the opposite side's resting quantity at prices within the limit (any price
+ *              for a MARKET) is >= qty, judged on the book as it stands at that record: then it
+ *              executes like the IOC / MARKET and ends FILLED. Else it is killed: no fill, the book
+ *              unchanged, CANCELED, filled_qty 0, remaining_qty = qty, fill_count 0, reason NONE.
+ *   POST_ONLY  LIMIT only. REJECTED with ME_RJ_WOULD_CROSS (filled_qty 0, remaining_qty = qty, the book
+ *              unchanged) when the opposite best price is within its limit; else it rests whole (NEW)
+ *              and is an ordinary resting order from then on. On a MARKET: REJECTED, ME_RJ_BAD_TIF.
+ * Reject order: BAD_QTY, BAD_SIDE, BAD_SEQ (BAD_SYMBOL ahead of them all), then BAD_TIF, then WOULD_CROSS. */
+enum { ME_TIF_GTC = 0, ME_TIF_IOC = 1, ME_TIF_FOK = 2, ME_TIF_POST_ONLY = 3 };
 
-/* kind byte of a batch record: bits 0-1 side, bit 2 type (1 = MARKET), bit 3 op (1 = CANCEL). */
+/* kind byte of a batch record: bits 0-1 side, bit 2 type (1 = MARKET), bit 3 op (1 = CANCEL),
+ * bits 4-5 time in force (ME_TIF_*; 0 = GTC), bits 6-7 reserved and ignored. */
 #define ME_KIND(side, type, op) ((uint8_t)(((side) & 3) | (((type) & 1) << 2) | (((op) & 1) << 3)))
+#define ME_KIND_TIF(side, type, op, tif) ((uint8_t)(ME_KIND(side, type, op) | (((tif) & 3) << 4)))
 
 /* Slots per FIFO chunk (one wave-wide load of a level's queue). */
 #define ME_CHUNK_SLOTS 16
@@ -101,11 +120,11 @@ typedef struct me_config {
                                   window re-centres as the market moves */
   uint32_t max_batch;          /* largest n accepted by me_submit_batch* */
   uint64_t max_resting;        /* resting orders the scratch/tape bound is sized for. Admission control:
-                                  a batch is accepted only while (resting orders) + (LIMIT records
-                                  accepted and not yet matched) + (its LIMIT records; every record of
-                                  a device batch) <= max_resting, else me_submit_* return
-                                  ME_E_CAPACITY for that batch, NOT sticky: nothing of it was enqueued
-                                  and the engine stays usable (me_admission_read) */
+                                  a batch is accepted only while (resting orders) + (records that may
+                                  rest — GTC and POST_ONLY LIMITs — accepted and not yet matched) + (its
+                                  records that may rest; every record of a device batch) <= max_resting,
+                                  else me_submit_* return ME_E_CAPACITY for that batch, NOT sticky: nothing
+                                  of it was enqueued and the engine stays usable (me_admission_read) */
   uint64_t max_chunks;         /* FIFO chunk pool (ME_CHUNK_SLOTS slots each, 256 B); 0 = max_resting + 32*S + 64,
                                   enough for any book shape and any movement of liquidity between symbols:
                                   free chunks go back to a shared pool (me_chunk_stats) */
@@ -135,7 +154,7 @@ typedef struct me_order_soa {
   const int64_t* price_q4;  /* NEW: normalized Q4 price (ignored for MARKET); CANCEL: target seq */
   const int32_t* qty;       /* NEW: quantity (wire int32, proto:44); CANCEL: ignored */
   const uint32_t* symbol;   /* local symbol id */
-  const uint8_t* kind;      /* ME_KIND(side, type, op) */
+  const uint8_t* kind;      /* ME_KIND(side, type, op) / ME_KIND_TIF(side, type, op, tif) */
 } me_order_soa;
 
 /* One trade (32 B): the maker rests, the taker crosses; price is the maker's level. */
@@ -151,7 +170,7 @@ typedef struct me_fill {
  * quantity removed from the book, or REJECTED/UNKNOWN_ORDER. */
 typedef struct me_order_result {
   int32_t filled_qty;
-  int32_t remaining_qty;  /* LIMIT: resting remainder; MARKET: discarded remainder */
+  int32_t remaining_qty;  /* GTC / POST_ONLY LIMIT: resting remainder; MARKET, IOC, FOK: discarded remainder */
   uint32_t fill_count;
   uint32_t tape_offset;   /* index of this record's first fill in the batch tape */
   uint8_t status;         /* ME_ST_* */
@@ -224,10 +243,12 @@ int me_get_config(const me_engine* e, me_config* out);
  * Outputs stay on the device until me_fetch_outputs (me_fetch_outputs / me_fetch_group_outputs /
  * me_copy_*_device read the most recent batch and fail with ME_E_INVALID when it was a host batch). */
 int me_submit_batch_device(me_engine* e, const me_order_soa* dev_batch, size_t n);
-/* The same with the batch's LIMIT-record count known to the caller (me_submit_batch_device counts
- * every record of a device batch as one that may rest): admission control takes n_limits, which must
- * be at least the batch's NEW records of type LIMIT (fewer can overflow the scratch bound: a loud,
- * sticky ME_E_CAPACITY). The cluster's shards use it (the root counted them while splitting). */
+/* The same with the count of the batch's records that may rest known to the caller
+ * (me_submit_batch_device counts every record of a device batch as one that may rest): admission control
+ * takes n_limits, which must be at least the batch's NEW records of type LIMIT with time in force GTC or
+ * POST_ONLY (IOC and FOK never rest and need not be counted; fewer than that can overflow the scratch
+ * bound: a loud, sticky ME_E_CAPACITY). The cluster's shards use it (the root counted them while
+ * splitting). */
 int me_submit_device_limits(me_engine* e, const me_order_soa* dev_batch, size_t n, uint64_t n_limits);
 /* Wait for all enqueued work; returns ME_E_CAPACITY if a pool overflowed in any batch. */
 int me_sync(me_engine* e);
@@ -287,6 +308,10 @@ int me_timing_read(me_engine* e, double* match_ms, double* pipeline_ms, uint64_t
 /* Event counters since me_create: handoffs = symbols the register-window kernel handed to its
  * continuation launch (a far price level, a re-centre, a cancel of a far or very old order). */
 int me_stats_read(me_engine* e, uint64_t* handoffs);
+/* The same for deep windows (L > 128): hot_handoffs = hot symbols whose walk (k_agg_walk / k_match_hot) gave
+ * the rest of a batch to the generic record loop (k_match_hot_cont): a cancel, a price outside the window, a
+ * taker while far levels exist, a FOK or POST_ONLY record, no room in the walk's pools. */
+int me_hot_stats_read(me_engine* e, uint64_t* hot_handoffs);
 
 /* Far levels (price levels outside a symbol's window; unbounded since round 5): moves =
  * sides that outgrew their region and moved to a larger one in the far arena, collections = the
@@ -312,9 +337,9 @@ int me_paths_read(const me_engine* e, uint32_t* flags);
  * accepted record is matched); exact_counts = times a submit had to take an exact count (flush + sync)
  * because the published count was too stale or too close to max_resting. */
 int me_admission_read(me_engine* e, uint64_t* resting, uint64_t* bound, uint64_t* exact_counts);
-/* Would a batch with n_rest LIMIT records be admitted now? (*ok = 1/0; nothing is enqueued.) A submit
- * from the same thread right after a 1 is admitted. Shards that must accept a slice all-or-none
- * (cluster.ShardedMatcher) ask every engine first. */
+/* Would a batch with n_rest records that may rest (GTC / POST_ONLY LIMITs) be admitted now? (*ok = 1/0;
+ * nothing is enqueued.) A submit from the same thread right after a 1 is admitted. Shards that must accept
+ * a slice all-or-none (cluster.ShardedMatcher) ask every engine first. */
 int me_admission_check(me_engine* e, uint64_t n_rest, int* ok);
 
 /* Last error text of e (or of the last failed me_create when e == NULL). */

@@ -43,9 +43,9 @@
  * Capacity: a slice the backend refuses (its books near max_resting) is split and matched in parts;
  * a single LIMIT that still does not fit is answered in-band with an OrderUpdate REJECTED (reason
  * ME_RJ_CAPACITY) instead of stalling every later slice behind it. Deliberate deviation from the
- * reference, which has no capacity: admission counts every LIMIT as one that may rest (whether it fills
- * is only known once matched), so near max_resting a marketable LIMIT that would have filled completely is
- * refused too. max_resting is a deployment parameter sized to HBM; a deployment sizes it
+ * reference, which has no capacity: admission counts every GTC / POST_ONLY LIMIT as one that may rest
+ * (whether it fills is only known once matched), so near max_resting a marketable LIMIT that would have
+ * filled completely is refused too. max_resting is a deployment parameter sized to HBM; a deployment sizes it
  * above its resting high-water mark.
  */
 #ifndef ME_SERVICE_H
@@ -119,6 +119,16 @@ me_service* me_service_create_matcher(const me_matcher* m, const char* const* sy
 
 /* Always returns 0 (the RPC itself succeeded or failed in-band, like the reference). */
 int me_service_submit_order(me_service* s, const me_order_request* req, me_order_response* resp);
+
+/* SubmitOrder with a time in force (ME_TIF_*, me_engine.h; build extension: the reference's OrderRequest
+ * carries none, so me_order_request stays as it is). me_service_submit_order is this call with
+ * ME_TIF_GTC. After the reference's own validations (same strings, same order) a tif outside 0..3, or
+ * POST_ONLY on a MARKET, is answered in-band: success = 0, "invalid time in force", no OID. An IOC or
+ * FOK never rests (no live entry, nothing to cancel): its remainder or kill arrives as an OrderUpdate
+ * CANCELED with the discarded quantity; a POST_ONLY that would cross as REJECTED. The orders row carries
+ * the final state, as a MARKET's does; a restart rebuilds resting orders as plain LIMITs (only GTC and
+ * POST_ONLY orders ever rest). */
+int me_service_submit_order_tif(me_service* s, const me_order_request* req, int32_t tif, me_order_response* resp);
 
 /* n SubmitOrder calls in order (what a server's handler threads do one request at a time), for
  * drivers and benchmarks holding many requests at once; resps[i] answers reqs[i]. */
@@ -196,8 +206,9 @@ int me_service_cancel_order(me_service* s, const me_cancel_request* req, me_orde
 
 /* OrderUpdate (proto:71-91). Events per flushed record, in slice order: for each fill the maker's
  * update then the taker's (fill price/qty, remaining after the fill, PARTIALLY_FILLED / FILLED);
- * then a closing taker update when no fill closed it (NEW resting, CANCELED market remainder,
- * REJECTED); a cancel record emits CANCELED (remaining = removed qty) or REJECTED for its target. */
+ * then a closing taker update when no fill closed it (NEW resting, CANCELED market / IOC remainder or
+ * FOK kill, REJECTED — a POST_ONLY that would cross included); a cancel record emits CANCELED
+ * (remaining = removed qty) or REJECTED for its target. */
 typedef struct me_order_update {
   char order_id[32];
   char client_id[64];

@@ -20,13 +20,15 @@ TYPE_LIMIT, TYPE_MARKET = 0, 1
 OP_NEW, OP_CANCEL = 0, 1
 ST_NEW, ST_PARTIALLY_FILLED, ST_FILLED, ST_CANCELED, ST_REJECTED = 0, 1, 2, 3, 4
 RJ_NONE, RJ_BAD_QTY, RJ_BAD_SIDE, RJ_OUT_OF_WINDOW, RJ_BAD_SYMBOL, RJ_UNKNOWN_ORDER, RJ_BAD_SEQ, RJ_CAPACITY = range(8)
+RJ_WOULD_CROSS, RJ_BAD_TIF = 8, 9
+TIF_GTC, TIF_IOC, TIF_FOK, TIF_POST_ONLY = 0, 1, 2, 3
 ME_OK, ME_E_INVALID, ME_E_HIP, ME_E_CAPACITY, ME_E_STATE, ME_E_SQLITE = 0, -1, -2, -3, -4, -5
 CHUNK_SLOTS = 16
 
 
-def kind(side: int, otype: int = TYPE_LIMIT, op: int = OP_NEW) -> int:
-    """ME_KIND(side, type, op)."""
-    return (side & 3) | ((otype & 1) << 2) | ((op & 1) << 3)
+def kind(side: int, otype: int = TYPE_LIMIT, op: int = OP_NEW, tif: int = TIF_GTC) -> int:
+    """ME_KIND_TIF(side, type, op, tif) (ME_KIND with tif = 0)."""
+    return (side & 3) | ((otype & 1) << 2) | ((op & 1) << 3) | ((tif & 3) << 4)
 
 
 # ---- structs ---------------------------------------------------------------------------------
@@ -149,6 +151,7 @@ PROTOTYPES = {
     ),
     "me_last_error": (C.c_int, [_P, C.c_char_p, _SZ]),
     "me_stats_read": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "me_hot_stats_read": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "me_far_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_chunk_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_paths_read": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
@@ -336,6 +339,7 @@ PROTOTYPES.update({
     "me_service_create": (_P, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p]),
     "me_service_destroy": (None, [_P]),
     "me_service_submit_order": (C.c_int, [_P, C.POINTER(MeOrderRequest), C.POINTER(MeOrderResponse)]),
+    "me_service_submit_order_tif": (C.c_int, [_P, C.POINTER(MeOrderRequest), C.c_int32, C.POINTER(MeOrderResponse)]),
     "me_service_pending": (_SZ, [_P]),
     "me_service_next_oid": (C.c_uint64, [_P]),
     "me_service_flush": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), _P, _P, _SZ, C.POINTER(_SZ)]),

@@ -388,12 +388,15 @@ __device__ __forceinline__ bool a_reserve(const AggDev& ag, gptr<AggSlot> slot, 
 
 // Reject reason (k_match's, in its order; cancels are the generic loop's) and whether the walk covers
 // the record: not a cancel, and a LIMIT inside the window or a MARKET while the side it crosses has no
-// far levels.
+// far levels. Time in force: an IOC is covered like the LIMIT it is priced as (lw_cw makes it a taker
+// that never rests); FOK and POST_ONLY records are not covered (their verdicts are the generic loop's),
+// rejected ones included.
 __device__ __forceinline__ bool a_classify(bool v, unsigned long long oseq, long long opx, int oq, uint32_t okd,
                                            long long base, int L, uint32_t nfar0, uint32_t nfar1, uint32_t& rj,
                                            int& olm) {
   const uint32_t side = okd & 3u;
-  const bool market = (okd >> 2) & 1u, cancel = (okd >> 3) & 1u;
+  // (one test: a cancel, or a record whose verdict is the generic loop's — FOK, POST_ONLY)
+  const bool market = (okd >> 2) & 1u, uncovered = (okd & (8u | KD_VERDICT)) != 0u;
   rj = oq <= 0                                          ? (uint32_t)ME_RJ_BAD_QTY
        : (side != ME_SIDE_BUY && side != ME_SIDE_SELL) ? (uint32_t)ME_RJ_BAD_SIDE
        : oseq == 0ull                                   ? (uint32_t)ME_RJ_BAD_SEQ
@@ -402,7 +405,7 @@ __device__ __forceinline__ bool a_classify(bool v, unsigned long long oseq, long
   const bool inw = off < (unsigned long long)L;
   const bool farx = (side == ME_SIDE_BUY ? nfar1 : nfar0) != 0u;
   olm = (int)off;
-  return v && !cancel && (rj != 0u || (market ? !farx : inw));
+  return v && !uncovered && (rj != 0u || (market ? !farx : inw));
 }
 
 // A list running low with levels beyond it is rebuilt at a block start (its totals flushed first).
@@ -978,11 +981,13 @@ __device__ __forceinline__ void lw_end(RWalk& w, const BookDev& bk, uint32_t s) 
 }
 
 // Control word of a record in vector form: the level a LIMIT rests at / the last level a taker may
-// trade at (MARKET: the far end of the window), side, type, reject reason.
+// trade at (MARKET: the far end of the window; IOC: its own level), side, LW_MKT = the remainder never
+// rests (MARKET, IOC), reject reason. (The flag's form is measured: `(okd & 0x14) ? ...` and the two-shift
+// form ran config 2's grouped walk 3 % slower than this one, same box, profiles/tif/plain_ab.md.)
 __device__ __forceinline__ uint32_t lw_cw(uint32_t okd, int olm, uint32_t rj, int L) {
   const bool buy = (okd & 3u) == ME_SIDE_BUY, mkt = (okd >> 2) & 1u;
   const int lim = mkt ? (buy ? L - 1 : 0) : (olm & (int)LW_LIM);
-  return (uint32_t)lim | (buy ? LW_BUY : 0u) | (mkt ? LW_MKT : 0u) | (rj << LW_RJ_SHIFT);
+  return (uint32_t)lim | (buy ? LW_BUY : 0u) | ((mkt | ((okd >> 4) & 1u)) ? LW_MKT : 0u) | (rj << LW_RJ_SHIFT);
 }
 
 // (record r of the block logs its events with jt = (jb + r) << JS: scalar arithmetic, no v_readlane)
@@ -1044,7 +1049,7 @@ __device__ __forceinline__ uint32_t lw_block(LE& e, W& w, int oq, uint32_t ocw, 
 // A record's result from its fields and the remainder the chain left (vector form); fill count and
 // scratch start come later (k_agg_fin / k_agg_gres, from the log).
 __device__ __forceinline__ me_order_result a_result(int oq, uint32_t okd, uint32_t rj, int rem) {
-  const bool mkt = (okd >> 2) & 1u;
+  const bool mkt = (okd & KD_FAST_NOREST) != 0u;  // MARKET, IOC: a remainder was discarded
   const int filled = rj ? 0 : oq - rem;
   me_order_result o;
   o.filled_qty = filled;
@@ -2861,7 +2866,7 @@ __device__ __forceinline__ void gw_prepare_cx(GwBuf& B, const GwBuf& Bp, GwCx& X
       rjs[j] = (g << AGG_GSHIFT) | oi;
       // a LIMIT of this group the walk may rest: its ring entry names its record until k_agg_gres places it
       // (and its rest info reads "none" until the walker writes it)
-      if (!cancel && !((okd >> 2) & 1u) && cov && rj == 0u) {
+      if (!cancel && !(okd & KD_FAST_NOREST) && cov && rj == 0u) {
         bk.loc[oseq & bk.ring_mask] = CX_TAG | j;
         ri.r[j].lq = 0u;
       }

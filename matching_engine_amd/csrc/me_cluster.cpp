@@ -589,7 +589,7 @@ void split_count(const uint32_t* owner, uint32_t W, uint32_t S, const me_order_s
       const uint32_t s = b->symbol[k];
       const uint32_t r = s < S ? owner[s] : 0;
       ci[r]++;
-      li[r] += (b->kind[k] & 0x0Cu) == 0u;  // NEW LIMIT: may rest
+      li[r] += (b->kind[k] & 0x0Cu) == 0u && (((b->kind[k] >> 4) ^ (b->kind[k] >> 5)) & 1u) == 0u;  // NEW LIMIT, GTC or POST_ONLY: may rest
     }
     std::copy(ci.begin(), ci.end(), sc.cnt.begin() + i * W);
     std::copy(li.begin(), li.end(), sc.lim.begin() + i * W);

@@ -1207,7 +1207,8 @@ static int check_err_word(me_engine* e) {
   return check_err_bits(e, w);
 }
 
-// Records of kind LIMIT-new (neither the MARKET nor the CANCEL bit), eight kind bytes per step.
+// Records that may rest: LIMIT-new (neither the MARKET nor the CANCEL bit) whose time in force is GTC or
+// POST_ONLY (bits 4-5 equal; IOC = 01 and FOK = 10 never rest), eight kind bytes per step.
 static uint64_t count_limits(const uint8_t* kind, size_t n) {
   uint64_t other = 0;
   size_t i = 0;
@@ -1215,9 +1216,10 @@ static uint64_t count_limits(const uint8_t* kind, size_t n) {
     uint64_t w;
     memcpy(&w, kind + i, 8);
     const uint64_t x = (w >> 2) & 0x0303030303030303ull;  // the MARKET and CANCEL bits of each byte
-    other += (uint64_t)__builtin_popcountll((x | (x >> 1)) & 0x0101010101010101ull);
+    const uint64_t t = (w >> 4) ^ (w >> 5);               // bit 0 of each byte: IOC or FOK
+    other += (uint64_t)__builtin_popcountll((x | (x >> 1) | t) & 0x0101010101010101ull);
   }
-  for (; i < n; ++i) other += (kind[i] & 0x0Cu) != 0u;
+  for (; i < n; ++i) other += kd_norest(kind[i]) || (kind[i] & 0x08u) != 0u;
   return (uint64_t)n - other;
 }
 
@@ -1863,6 +1865,16 @@ extern "C" int me_stats_read(me_engine* e, uint64_t* handoffs) {
   unsigned long long v[ME_STATS];
   HIP_TRY(hipMemcpy(v, e->bk.stats, sizeof v, hipMemcpyDeviceToHost), "D2H stats");
   if (handoffs) *handoffs = v[ST_HANDOFFS];
+  return ME_OK;
+}
+
+extern "C" int me_hot_stats_read(me_engine* e, uint64_t* hot_handoffs) {
+  if (!e) return ME_E_INVALID;
+  int rc = me_sync(e);
+  if (rc) return rc;
+  unsigned long long v[ME_STATS];
+  HIP_TRY(hipMemcpy(v, e->bk.stats, sizeof v, hipMemcpyDeviceToHost), "D2H stats");
+  if (hot_handoffs) *hot_handoffs = v[ST_HOT_HANDOFFS];
   return ME_OK;
 }
 

@@ -1067,6 +1067,64 @@ __device__ __forceinline__ RecOut rec_out(int filled, int remaining, uint32_t nf
   return o;
 }
 
+// FOK pre-pass (reads only): is the resting quantity a taker of `want` may trade against — window levels
+// from the opposite best to lim through the occupancy bitmap, then (far) the far levels in price order
+// while within the limit — at least `want`? Stops as soon as the running 64-bit sum reaches it.
+__device__ bool fok_fillable(WaveCtx& c, bool buy, bool market, bool far, int lim, long long px, long long want) {
+  const int lane = lane_id();
+  const int L = (int)c.bk.L;
+  const int dir = buy ? 1 : -1;
+  long long sum = 0;
+  int cur = buy ? c.ba : c.bb;
+  wave_mem_order();
+  while (sum < want) {
+    if (dir > 0 ? (cur > lim || cur >= L) : (cur < lim || cur < 0)) break;
+    const int lv = cur + dir * lane;
+    bool valid = (dir > 0) ? (lv <= lim && lv < L) : (lv >= lim && lv >= 0);
+    if (valid) valid = (c.lad.occ[lv >> 6] >> (lv & 63)) & 1ull;
+    const Level W = c.lad.lane_get(lv, valid);
+    sum += rli64(wave_incl_scan(valid ? W.total : 0ll), 63);
+    const int nxt = cur + dir * 64;
+    if (dir > 0) {
+      if (nxt > lim) break;
+      cur = c.lad.next_occ(nxt);
+    } else {
+      if (nxt < lim) break;
+      cur = c.lad.prev_occ(nxt);
+    }
+  }
+  if (sum >= want || !far) return sum >= want;
+  const uint32_t k = buy ? 1u : 0u;
+  const uint32_t n = c.fcount(k);
+  if (n == 0u) return false;
+  const gptr<FarLevel> a = far_arr(c, k);
+  wave_mem_order();
+  for (uint32_t top = n; top != 0u && sum < want;) {  // best level last: blocks of 64 from the top
+    const uint32_t i = top - 1u - (uint32_t)lane;
+    const bool v = (uint32_t)lane < top;
+    FarLevel e{};
+    if (v) e = a[i];
+    const bool in = v && (market || (buy ? e.price <= px : e.price >= px));
+    sum += rli64(wave_incl_scan(in ? e.total : 0ll), 63);
+    if (__ballot(v && !in)) break;  // price order: every further level is beyond the limit too
+    top = top > 64u ? top - 64u : 0u;
+  }
+  return sum >= want;
+}
+
+// POST_ONLY: would a LIMIT at px take? The opposite best price is the window best, or the best far
+// level when that side's window is empty (invariant I: window levels are better than far levels).
+__device__ bool post_would_cross(WaveCtx& c, bool buy, bool far, int lim, long long px) {
+  const int L = (int)c.bk.L;
+  if (buy ? c.ba < L : c.bb >= 0) return buy ? c.ba <= lim : c.bb >= lim;
+  const uint32_t k = buy ? 1u : 0u;
+  const uint32_t n = c.fcount(k);
+  if (!far || n == 0u) return false;
+  wave_mem_order();
+  const long long best = far_get(far_arr(c, k), n - 1u).price;
+  return buy ? best <= px : best >= px;
+}
+
 // One record in the generic way (deep windows): reject reasons, sweep, far levels, rest or cancel.
 __device__ __forceinline__ RecOut generic_record(WaveCtx& c, unsigned long long seq, long long px, int q,
                                                  uint32_t kind) {
@@ -1074,6 +1132,7 @@ __device__ __forceinline__ RecOut generic_record(WaveCtx& c, unsigned long long 
   const uint32_t side = kind & 3u;
   const bool market = (kind >> 2) & 1u;
   const bool cancel = (kind >> 3) & 1u;
+  const uint32_t tif = kd_tif(kind);
   const unsigned long long fstart = c.wptr;
   if (cancel) {
     const int got = cancel_order(c, (unsigned long long)px);
@@ -1095,6 +1154,15 @@ __device__ __forceinline__ RecOut generic_record(WaveCtx& c, unsigned long long 
                 : buy    ? (above ? (int)Lw - 1 : -1)
                          : (above ? (int)Lw : 0);
   const bool far = market || (buy ? above : (!inw && !above));
+  if (ME_UNLIKELY(tif >= (uint32_t)ME_TIF_FOK)) {  // verdicts that leave the book as it is
+    if (tif == (uint32_t)ME_TIF_POST_ONLY) {
+      if (market) return rec_out(0, q, 0, ME_ST_REJECTED, ME_RJ_BAD_TIF, fstart);
+      if (post_would_cross(c, buy, far, lim, px)) return rec_out(0, q, 0, ME_ST_REJECTED, ME_RJ_WOULD_CROSS, fstart);
+    } else if (!fok_fillable(c, buy, market, far, lim, px, (long long)q)) {
+      return rec_out(0, q, 0, ME_ST_CANCELED, ME_RJ_NONE, fstart);
+    }
+  }
+  const bool norest = kd_norest(kind);  // MARKET, IOC, FOK: the remainder is discarded
   long long got = sweep(c, buy ? 1 : -1, lim, (long long)q, seq);
   if (got < q && far && c.fcount(buy ? 1u : 0u) != 0u)
     got += far_take(c, buy, market, px, (uint32_t)(q - got), seq);
@@ -1103,7 +1171,7 @@ __device__ __forceinline__ RecOut generic_record(WaveCtx& c, unsigned long long 
   const int filled = (int)got;
   const int rem = q - filled;
   uint8_t stt;
-  if (market) {
+  if (norest) {
     stt = rem == 0 ? ME_ST_FILLED : ME_ST_CANCELED;
   } else {
     const bool failed = rem > 0 && !(inw ? rest_order(c, (int)off, seq, rem, buy)
@@ -2135,13 +2203,14 @@ __device__ __forceinline__ void match_records_hot(HotState& h, WaveCtx& c, const
     const bool market = (okd >> 2) & 1u, cancel = (okd >> 3) & 1u;
     const bool good = v && !cancel && oq > 0 && (side == ME_SIDE_BUY || side == ME_SIDE_SELL) && oseq != 0ull;
     // which records the lists take (vector form; again after a generic record moved the window):
-    // cancels, LIMITs outside the window and takers while the side they cross has far levels are generic
+    // cancels, LIMITs outside the window, takers while the side they cross has far levels, FOK and
+    // POST_ONLY records are generic (an IOC is a LIMIT here: its own level is its last, and it never rests)
     unsigned long long fastm;
     auto classify = [&]() {
       const unsigned long long off = (unsigned long long)opx - (unsigned long long)h.base;
       const bool inw = off < (unsigned long long)L;
       const bool farx = (side == ME_SIDE_BUY ? h.nfar1 : h.nfar0) != 0u;
-      const bool fast = good && (market || inw) && !farx;
+      const bool fast = good && (market || inw) && !farx && !(okd & KD_VERDICT);
       h.rlvl = fast && !market ? (int)off : -1;
       fastm = __ballot(fast);
     };
@@ -2191,6 +2260,7 @@ __device__ __forceinline__ void match_records_hot(HotState& h, WaveCtx& c, const
       HMARK("record-fast");
       const bool buy = (kd & 3u) == ME_SIDE_BUY;
       const bool mkt = (kd >> 2) & 1u;
+      const bool nr = (kd & KD_FAST_NOREST) != 0u;  // MARKET or IOC: the remainder is dropped
       const int lm = mkt ? 0 : rli32(h.rlvl, (int)k);  // the LIMIT's window level
       const unsigned long long fstart = h.wptr;
       uint32_t rem = (uint32_t)q;
@@ -2201,11 +2271,11 @@ __device__ __forceinline__ void match_records_hot(HotState& h, WaveCtx& c, const
       if (buy) {
         hot_take<1>(h, h.A, mkt ? L - 1 : lm, rem, seq);
         HS(PH_SWEEP);
-        if (!mkt && rem) rested = hot_rest<0>(h, c, h.B, L - 1 - lm, lm, seq, (int)rem, (int)k);
+        if (!nr && rem) rested = hot_rest<0>(h, c, h.B, L - 1 - lm, lm, seq, (int)rem, (int)k);
       } else {
         hot_take<0>(h, h.B, mkt ? L - 1 : L - 1 - lm, rem, seq);
         HS(PH_SWEEP);
-        if (!mkt && rem) rested = hot_rest<1>(h, c, h.A, lm, lm, seq, (int)rem, (int)k);
+        if (!nr && rem) rested = hot_rest<1>(h, c, h.A, lm, lm, seq, (int)rem, (int)k);
       }
       if (ME_UNLIKELY(!rested)) {
         ok = false;  // the chunk pool is exhausted (sticky error word from alloc_chunk)
@@ -2214,7 +2284,7 @@ __device__ __forceinline__ void match_records_hot(HotState& h, WaveCtx& c, const
       const int filled = q - (int)rem;
       const uint32_t nfill = (uint32_t)(h.wptr - fstart);
       uint8_t stt;
-      if (mkt)
+      if (nr)
         stt = rem == 0 ? ME_ST_FILLED : ME_ST_CANCELED;
       else
         stt = rem == 0 ? ME_ST_FILLED : (filled > 0 ? ME_ST_PARTIALLY_FILLED : ME_ST_NEW);
@@ -2318,6 +2388,8 @@ __global__ __launch_bounds__(64) void k_match_hot(BookDev bk, BatchDev bt) {
 // record loop (k_match's), on the same stream right after k_match_hot; hand-off i is bk.hand[S + i].
 __global__ __launch_bounds__(64) void k_match_hot_cont(BookDev bk, BatchDev bt) {
   const uint32_t nh = min(*(volatile uint32_t*)(bk.hcount + 1), bk.S);
+  if (nh && blockIdx.x == 0 && threadIdx.x == 0 && bk.stats)  // (me_hot_stats_read)
+    atomicAdd(bk.stats + ST_HOT_HANDOFFS, (unsigned long long)nh);
   for (uint32_t i = blockIdx.x; i < nh; i += gridDim.x) {
     const Handoff ho = bk.hand[bk.S + i];
     const uint32_t s = rl32(ho.s, 0), pos = rl32(ho.pos, 0), hi = rl32(ho.nsg, 0);

@@ -53,6 +53,17 @@ constexpr uint32_t LDS_MAX_LEVELS = 1024; // ladders up to this depth are staged
                          // for two workgroups per CU)
 #endif
 constexpr int ME_GMAX = ME_GROUP_MAX;
+
+// Time in force of a kind byte (ME_TIF_*), and whether the record can never rest: a MARKET, an IOC or a FOK.
+__host__ __device__ constexpr uint32_t kd_tif(uint32_t kd) { return (kd >> 4) & 3u; }
+__host__ __device__ constexpr bool kd_norest(uint32_t kd) { return ((kd >> 2) & 1u) != 0u || kd_tif(kd) - 1u < 2u; }
+// The fast walks' forms (one AND each): a record they do not cover (FOK = 10, POST_ONLY = 11), and "never
+// rests" among the records they do cover (a MARKET, or tif bit 0: an IOC, FOK and POST_ONLY being excluded).
+constexpr uint32_t KD_VERDICT = 0x20u, KD_FAST_NOREST = 0x14u;
+// KD_FAST_NOREST is also set for a POST_ONLY (11): it is right only for records KD_VERDICT let through
+static_assert(KD_VERDICT == (2u << 4) && (KD_FAST_NOREST & (3u << 4)) == (1u << 4) &&
+                  ((uint32_t)ME_TIF_FOK & 2u) && ((uint32_t)ME_TIF_POST_ONLY & 2u) && !((uint32_t)ME_TIF_IOC & 2u),
+              "KD_VERDICT singles out FOK and POST_ONLY; of the rest, tif bit 0 is an IOC");
 constexpr uint32_t ME_DEFAULT_GROUP = 32;
 
 // Sticky error bits (BookDev::err).
@@ -162,7 +173,7 @@ struct alignas(8) BkRec {
   uint64_t seq;
   int64_t px;
   int32_t qty;
-  uint32_t ok;  // batch index | (kind & 15) << BK_KIND_SHIFT
+  uint32_t ok;  // batch index | (kind & 63) << BK_KIND_SHIFT
 };
 
 // A symbol the register-window kernel handed to its continuation launch (me_match_reg.hip): its
@@ -290,7 +301,7 @@ struct HotLaunch {
 // hand-off publication.
 // ST_FAR_GROW / ST_FAR_GC: far sides moved to a larger arena region / collection passes (me_far_stats).
 // ST_CHUNK_GC: chunk-pool reclamations (k_seq_sweep, me_chunk_stats).
-enum : uint32_t { ST_HANDOFFS = 0, ST_RESTING = 1, ST_LAUNCH = 2, ST_FAR_GROW = 3, ST_FAR_GC = 4, ST_CHUNK_GC = 5, ME_STATS = 8 };
+enum : uint32_t { ST_HANDOFFS = 0, ST_RESTING = 1, ST_LAUNCH = 2, ST_FAR_GROW = 3, ST_FAR_GC = 4, ST_CHUNK_GC = 5, ST_HOT_HANDOFFS = 6, ME_STATS = 8 };
 
 struct BookDev {
   Level* levels;
@@ -470,7 +481,8 @@ struct SnapReq {
 };
 
 constexpr int BK_CAP = 128;          // records per bucket (two 64-record blocks)
-constexpr int BK_KIND_SHIFT = 28;    // BkRec::ok: kind bits above the batch index
+constexpr int BK_KIND_SHIFT = 26;    // BkRec::ok: six kind bits (side, type, op, time in force) above the batch index
+constexpr uint32_t BK_KIND_BITS = 63u;
 constexpr uint32_t BK_IDX_MASK = (1u << BK_KIND_SHIFT) - 1u;
 constexpr uint32_t BK_MAX_BATCH = 1u << 25;  // sort key (index << 7 | bucket slot) fits 32 bits
 constexpr int BK_CNT_STRIDE = 32;    // bcnt[b * stride]: one 128-B line per counter (atomics on one

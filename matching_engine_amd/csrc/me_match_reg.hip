@@ -990,7 +990,7 @@ __device__ __forceinline__ void aux_bucket(const GA& G, uint32_t j, uint32_t r0,
         brec[d].seq = sq;
         brec[d].px = p;
         brec[d].qty = q;
-        brec[d].ok = i | ((k & 15u) << BK_KIND_SHIFT);
+        brec[d].ok = i | ((k & BK_KIND_BITS) << BK_KIND_SHIFT);
       }
     }
   }
@@ -1230,7 +1230,7 @@ __device__ __forceinline__ void side_bucket_wg(const GA& G, uint32_t j, uint32_t
       brec[d].seq = sq[k];
       brec[d].px = p[k];
       brec[d].qty = q[k];
-      brec[d].ok = i | ((k8[k] & 15u) << BK_KIND_SHIFT);
+      brec[d].ok = i | ((k8[k] & BK_KIND_BITS) << BK_KIND_SHIFT);
     }
   }
 }
@@ -1343,9 +1343,12 @@ __global__ __launch_bounds__(SIDE_THREADS) void k_side(SideArgs args, uint32_t n
 // FAR (the limit reaches past the window on the side the taker crosses: MARKET, a BUY above the
 // window, a SELL below it) | OUT (a LIMIT priced outside the window: its rest takes the far path).
 // HAND (common launch only): the record needs a far level — OUT, or a MARKET while the side it crosses
-// has far levels (far counts only change in the continuation launch, so they are fixed per launch).
+// has far levels (far counts only change in the continuation launch, so they are fixed per launch), or a
+// FOK / POST_ONLY record (their verdicts are the continuation's: no such code in the common launch).
+// NR: the remainder never rests (MARKET, IOC, FOK). An IOC is a LIMIT in every other bit: its own level is
+// the last it trades at. FOK / PO: the continuation's verdict before the walk.
 constexpr uint32_t CW_BUY = 1u << 8, CW_MKT = 1u << 9, CW_CXL = 1u << 10, CW_FAR = 1u << 11, CW_OUT = 1u << 12,
-                   CW_HAND = 1u << 13;
+                   CW_HAND = 1u << 13, CW_NR = 1u << 14, CW_FOK = 1u << 15, CW_PO = 1u << 16;
 
 // far: bit 0 = the symbol has far bids (side 0), bit 1 = far asks (side 1)
 __device__ __forceinline__ uint32_t make_cw(long long opx, uint32_t kd, long long base, uint32_t L, uint32_t far_nz) {
@@ -1363,9 +1366,61 @@ __device__ __forceinline__ uint32_t make_cw(long long opx, uint32_t kd, long lon
   // a CANCEL's price field is its target seq: none of the window / far tests apply to it
   const bool far = !cancel && (market || (buy ? above : (!inw && !above)));
   const bool out = !market && !cancel && !inw;
-  const bool hand = out || (market && ((far_nz >> (buy ? 1 : 0)) & 1u));
+  const uint32_t tif = cancel ? 0u : kd_tif(kd);
+  const bool hand = out || (market && ((far_nz >> (buy ? 1 : 0)) & 1u)) || tif >= (uint32_t)ME_TIF_FOK;
   return (uint32_t)(lim + 1) | (buy ? CW_BUY : 0u) | (market ? CW_MKT : 0u) | (cancel ? CW_CXL : 0u) |
-         (far ? CW_FAR : 0u) | (out ? CW_OUT : 0u) | (hand ? CW_HAND : 0u);
+         (far ? CW_FAR : 0u) | (out ? CW_OUT : 0u) | (hand ? CW_HAND : 0u) |
+         (!cancel && kd_norest(kd) ? CW_NR : 0u) | (tif == (uint32_t)ME_TIF_FOK ? CW_FOK : 0u) |
+         (tif == (uint32_t)ME_TIF_POST_ONLY ? CW_PO : 0u);
+}
+
+// The continuation's FOK pre-pass (reads only): the resting quantity a taker may trade against — the
+// window levels from the opposite best to lm, then (CW_FAR) far levels in price order while within the
+// limit — reaches q? 64-bit sum.
+template <class C>
+__device__ bool reg_fok_fillable(C& c, uint32_t ctl, int lm, long long px, uint32_t q) {
+  const int lane = lane_id();
+  const bool buy = (ctl & CW_BUY) != 0u;
+  const int lo = buy ? c.occ.next(c.ba) : lm, hi = buy ? lm : c.occ.prev(c.bb);
+  long long t = 0;
+  for (int row = 0; row < 2; ++row) {
+    const int l = row * 64 + lane;
+    const bool occ = ((row ? c.occ.w1 : c.occ.w0) >> lane) & 1ull;
+    if (occ && l >= lo && l <= hi) t += c.M->tot[l];
+  }
+  long long sum = rli64(wave_incl_scan(t), 63);
+  if (sum >= (long long)q || !(ctl & CW_FAR)) return sum >= (long long)q;
+  const uint32_t k = buy ? 1u : 0u;
+  const uint32_t n = c.fcount(k);
+  if (n == 0u) return false;
+  const gptr<FarLevel> a = far_arr(c, k);
+  wave_mem_order();
+  for (uint32_t top = n; top != 0u && sum < (long long)q;) {  // best level last: blocks of 64 from the top
+    const uint32_t i = top - 1u - (uint32_t)lane;
+    const bool v = (uint32_t)lane < top;
+    FarLevel e{};
+    if (v) e = a[i];
+    const bool in = v && ((ctl & CW_MKT) || (buy ? e.price <= px : e.price >= px));
+    sum += rli64(wave_incl_scan(in ? e.total : 0ll), 63);
+    if (__ballot(v && !in)) break;  // price order: every further level is beyond the limit too
+    top = top > 64u ? top - 64u : 0u;
+  }
+  return sum >= (long long)q;
+}
+
+// The continuation's POST_ONLY verdict: the opposite best price (the window best, or the best far level
+// when that side's window is empty) is within the limit.
+template <class C>
+__device__ bool reg_post_would_cross(C& c, uint32_t ctl, int lm, long long px) {
+  const bool buy = (ctl & CW_BUY) != 0u;
+  const int best = buy ? c.occ.next(c.ba) : c.occ.prev(c.bb);  // (bids and asks share the bitmap: asks from ba up)
+  if (buy ? best < RL : best >= 0) return buy ? best <= lm : best >= lm;
+  const uint32_t k = buy ? 1u : 0u;
+  const uint32_t n = c.fcount(k);
+  if (!(ctl & CW_FAR) || n == 0u) return false;
+  wave_mem_order();
+  const long long p = far_get(far_arr(c, k), n - 1u).price;
+  return buy ? p <= px : p >= px;
 }
 
 // One wavefront per symbol. kSlow = false: the common launch — every symbol of the group, no far-level
@@ -1651,6 +1706,8 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
             rj = ME_RJ_BAD_SIDE;
           else if (oseq == 0ull)
             rj = ME_RJ_BAD_SEQ;  // no OID is 0 (the counter starts at 1, storage.cpp:254-267)
+          else if ((kd & 0x34u) == 0x34u)
+            rj = ME_RJ_BAD_TIF;  // POST_ONLY on a MARKET
         }
         const uint32_t fnz = kSlow ? 0u : ((ldsu(c.M->nfar[0]) != 0u) | ((ldsu(c.M->nfar[1]) != 0u) << 1));
         cw = make_cw(v ? opx_ : 0ll, kd, c.base, L, fnz);
@@ -1712,6 +1769,21 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
           const int lm = (int)(ctl & 0xFFu) - 1;
           const uint32_t w_in = c.wptr;
           uint32_t rem = q;
+          if constexpr (kSlow) {  // FOK / POST_ONLY verdicts, before anything changes
+            if (ME_UNLIKELY(ctl & (CW_FOK | CW_PO))) {
+              const long long px = (long long)rl64((unsigned long long)opx_, k);
+              const bool stopped = (ctl & CW_PO) ? reg_post_would_cross(c, ctl, lm, px)
+                                                 : !reg_fok_fillable(c, ctl, lm, px, q);
+              if (stopped) {  // killed (CANCELED, the whole quantity discarded) or rejected: no fill, no rest
+                const bool me_ = lane == k;
+                out_n = me_ ? 0u : out_n;
+                out_w = me_ ? w_in : out_w;
+                if (ctl & CW_PO) rj = me_ ? (uint32_t)ME_RJ_WOULD_CROSS : rj;
+                out_q = me_ ? 0u : out_q;
+                continue;
+              }
+            }
+          }
           // one walk loop for both sides (one copy of the walk): the opposite best moves away from
           // the taker's limit as levels empty
           int lvl = buy ? c.ba : c.bb;
@@ -1731,7 +1803,7 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
             if (rem != 0u && (ctl & CW_FAR) && c.fcount(buy ? 1u : 0u) != 0u)
               rem -= far_take(c, buy, (ctl & CW_MKT) != 0u, (long long)rl64((unsigned long long)opx_, k), rem, seq);
             // a LIMIT priced outside the window rests through the far path (may re-centre the window)
-            if ((ctl & CW_OUT) && rem != 0u)
+            if ((ctl & (CW_OUT | CW_NR)) == CW_OUT && rem != 0u)
               rr = reg_far_rest(c, (long long)rl64((unsigned long long)opx_, k), seq, rem, buy) < 0 ? -1 : 1;
           }
           outq = q - rem;
@@ -1747,7 +1819,7 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
             }
             const bool v = j < hi && vis + j >= skip;
             cw = make_cw(v ? opx_ : 0ll, v ? kd_ : 0u, c.base, L, 0u);  // the window may have moved
-          } else if (!(ctl & (CW_MKT | CW_OUT)) && rem != 0u && ME_UNLIKELY(!reg_rest(c, lm, seq, rem, buy))) {
+          } else if (!(ctl & (CW_NR | CW_OUT)) && rem != 0u && ME_UNLIKELY(!reg_rest(c, lm, seq, rem, buy))) {
             stop = (uint32_t)k;  // chunk pool exhausted: the batch fails (sticky error word)
             handoff = false;
             break;
@@ -1762,7 +1834,7 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
       const bool sortp = ldsu(G.bt[0].bcnt) == nullptr;
       uint32_t* tile_sum = ldsg(G.bt[ldsu(c.M->g_cur)].tile_sum);
       if (rj != 0xFFu && (uint32_t)lane < stop) {
-        const bool market = (kd_ >> 2) & 1u, cancel = (kd_ >> 3) & 1u;
+        const bool market = kd_norest(kd_), cancel = (kd_ >> 3) & 1u;  // (MARKET, IOC, FOK: CANCELED when not filled)
         me_order_result r;
         r.tape_offset = out_w;  // scratch start until the tape job writes the tape offset
         r.pad[0] = r.pad[1] = 0;

@@ -630,6 +630,11 @@ static void append(me_service* s, uint64_t seq, int64_t px, int32_t qty, uint32_
 }
 
 extern "C" int me_service_submit_order(me_service* s, const me_order_request* r, me_order_response* resp) {
+  return me_service_submit_order_tif(s, r, ME_TIF_GTC, resp);
+}
+
+extern "C" int me_service_submit_order_tif(me_service* s, const me_order_request* r, int32_t tif,
+                                           me_order_response* resp) {
   memset(resp, 0, sizeof(*resp));
   const char* symbol = r->symbol ? r->symbol : "";
   // --- validation (:66-83): first failing check wins, no OID
@@ -643,6 +648,11 @@ extern "C" int me_service_submit_order(me_service* s, const me_order_request* r,
   }
   if (r->order_type == ME_TYPE_LIMIT && r->price <= 0) {
     put(resp->error_message, sizeof resp->error_message, "price must be > 0 for LIMIT");
+    return 0;
+  }
+  // --- time in force (build extension): after the reference's own checks, no OID either
+  if (tif < ME_TIF_GTC || tif > ME_TIF_POST_ONLY || (tif == ME_TIF_POST_ONLY && r->order_type != ME_TYPE_LIMIT)) {
+    put(resp->error_message, sizeof resp->error_message, "invalid time in force");
     return 0;
   }
   const std::string sym(symbol);
@@ -674,13 +684,13 @@ extern "C" int me_service_submit_order(me_service* s, const me_order_request* r,
   }
   resp->success = 1;
   const bool limit = r->order_type == ME_TYPE_LIMIT;
-  if (limit) {  // its owner, for CancelOrder and the OrderUpdate stream
+  const uint8_t kd = ME_KIND_TIF(r->side, limit ? ME_TYPE_LIMIT : ME_TYPE_MARKET, ME_OP_NEW, tif);
+  if (limit && tif != ME_TIF_IOC && tif != ME_TIF_FOK) {  // may rest: its owner, for CancelOrder and the OrderUpdate stream
     std::lock_guard<std::mutex> lv(s->live_mu);
     s->live[id] = Live{client, sym, r->quantity, sid};
   }
-  ref_add(s, sid, 1);  // a LIMIT's live entry, or a MARKET record on its way
-  append(s, id, q4, r->quantity, sid, ME_KIND(r->side, limit ? ME_TYPE_LIMIT : ME_TYPE_MARKET, ME_OP_NEW),
-         Pending{std::move(client), sym, r->side, false, 0});
+  ref_add(s, sid, 1);  // a resting LIMIT's live entry, or a MARKET / IOC / FOK record on its way
+  append(s, id, q4, r->quantity, sid, kd, Pending{std::move(client), sym, r->side, false, 0});
   return 0;
 }
 
@@ -824,12 +834,13 @@ static void emit_updates(me_service* s, const Slice& sl, const me_order_result* 
         push_update(s, oid, m.client, m.symbol, rem > 0 ? ME_ST_PARTIALLY_FILLED : ME_ST_FILLED, fl.price_q4,
                     fl.qty, rem);
       }
-      const bool market = ((sl.kind[i] >> 2) & 1u) != 0;
+      // never rests: a MARKET, an IOC or a FOK
+      const bool market = ((sl.kind[i] >> 2) & 1u) != 0 || (((sl.kind[i] >> 4) ^ (sl.kind[i] >> 5)) & 1u) != 0;
       if (r.status == ME_ST_REJECTED || r.status == ME_ST_CANCELED ||
           (r.fill_count == 0 && r.status == ME_ST_NEW && !sl.recovery))
         push_update(s, oid, m.client, m.symbol, r.status, 0, 0, r.remaining_qty);
       if (market) {
-        ref_add(s, sl.sid[i], -1);  // the MARKET record (it never rests)
+        ref_add(s, sl.sid[i], -1);  // the MARKET / IOC / FOK record (it never rests)
         continue;
       }
       // a LIMIT's count is its live entry, created at submit: it stays while the order rests
@@ -1152,7 +1163,7 @@ static int on_refused(me_service* s, Slice&& sl, FlushOut* out, size_t& taken) {
     return s->fail(ME_E_CAPACITY, "the backend's max_resting is below the resting orders the DB holds: " +
                                       backend_err(s));
   }
-  if (n == 1 && (sl.kind[0] & 0x0Cu) == 0u) {  // one LIMIT and no room to rest it
+  if (n == 1 && (sl.kind[0] & 0x0Cu) == 0u && (((sl.kind[0] >> 4) ^ (sl.kind[0] >> 5)) & 1u) == 0u) {  // one LIMIT that may rest (GTC / POST_ONLY) and no room to rest it
     me_order_result r{};
     r.remaining_qty = sl.qty[0];
     r.status = ME_ST_REJECTED;

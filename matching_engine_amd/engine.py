@@ -312,10 +312,12 @@ class Engine:
         return v.value
 
     def stats(self) -> dict:
-        """Device event counters since creation (me_stats_read)."""
-        h = C.c_uint64(0)
+        """Device event counters since creation (me_stats_read, me_hot_stats_read)."""
+        h, hh = C.c_uint64(0), C.c_uint64(0)
         _check(self.lib, self.h, self.lib.me_stats_read(self.h, C.byref(h)))
-        return {"handoffs": h.value}
+        if hasattr(self.lib, "me_hot_stats_read"):  # (absent from an older build loaded through ME_ENGINE_LIB)
+            _check(self.lib, self.h, self.lib.me_hot_stats_read(self.h, C.byref(hh)))
+        return {"handoffs": h.value, "hot_handoffs": hh.value}
 
     def far_stats(self) -> dict:
         """The far arena (me_far_stats): sides moved to a larger region, collections, entries in use."""
@@ -338,7 +340,7 @@ class Engine:
 
     def admits(self, b: Batch) -> bool:
         """Would submit_batch(b) be admitted now (me_admission_check)? Nothing is enqueued."""
-        n_rest = int(np.count_nonzero((b.kind & 0x0C) == 0))
+        n_rest = int(np.count_nonzero(((b.kind & 0x0C) == 0) & ((((b.kind >> 4) ^ (b.kind >> 5)) & 1) == 0)))
         ok = C.c_int(0)
         _check(self.lib, self.h, self.lib.me_admission_check(self.h, n_rest, C.byref(ok)))
         return bool(ok.value)

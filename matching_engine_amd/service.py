@@ -72,11 +72,12 @@ class MatchingEngineService:
         self.lib.me_service_last_error(self.h, buf, 1024)
         return buf.value.decode(errors="replace")
 
-    def submit_order(self, client_id, symbol, order_type, side, price, scale, quantity) -> dict:
-        """OrderRequest -> OrderResponse fields + grpc status (0 OK, 2 UNKNOWN)."""
+    def submit_order(self, client_id, symbol, order_type, side, price, scale, quantity, tif=0) -> dict:
+        """OrderRequest -> OrderResponse fields + grpc status (0 OK, 2 UNKNOWN). tif: TIF_* (me_service_submit_order_tif;
+        0 = the reference's SubmitOrder)."""
         req = MeOrderRequest(client_id.encode(), symbol.encode(), order_type, side, price, scale, quantity)
         resp = MeOrderResponse()
-        self.lib.me_service_submit_order(self.h, C.byref(req), C.byref(resp))
+        self.lib.me_service_submit_order_tif(self.h, C.byref(req), tif, C.byref(resp))
         return {"order_id": resp.order_id.decode(), "success": bool(resp.success),
                 "error_message": resp.error_message.decode(), "grpc_status": resp.grpc_status}
 

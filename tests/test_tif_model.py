@@ -1,0 +1,262 @@
+"""The time-in-force model (tests/tif_model.py) pinned with the unchanged native oracle (no GPU).
+
+1. With tif = 0 the model equals OracleBook: results, tapes, books.
+2. Rewrite: a TIF stream and the model's verdicts become plain records (IOC / fillable FOK -> LIMIT +
+   a CANCEL of itself repeating its seq; killed FOK / rejected POST_ONLY -> dropped; accepted POST_ONLY ->
+   LIMIT); the native oracle on the rewritten stream must give the same fills and the same final books, each
+   IOC's filled_qty must equal its LIMIT's and its remaining_qty what the self-cancel removed (0 when that
+   cancel is answered UNKNOWN_ORDER). So everything but the FOK and POST_ONLY verdicts is pinned by the C++
+   oracle.
+3. Hand-written verdict cases.
+4. ABI: header, library and PROTOTYPES carry me_service_submit_order_tif; kind(1, 0, 0, TIF_IOC) == 0x11.
+5. The committed fixture tests/golden/match_tif.npz replays through the model.
+"""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import tif_model as tm
+from tests.tif_model import (RJ_BAD_TIF, RJ_WOULD_CROSS, TIF_FOK, TIF_GTC, TIF_IOC, TIF_POST_ONLY, Arrays, TifBook,
+                             kind)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUY, SELL = 1, 2
+ST_NEW, ST_PARTIAL, ST_FILLED, ST_CANCELED, ST_REJECTED = 0, 1, 2, 3, 4
+RJ_NONE, RJ_BAD_QTY, RJ_BAD_SIDE, RJ_UNKNOWN, RJ_BAD_SEQ = 0, 1, 2, 5, 6
+FIELDS_RES = ("filled_qty", "remaining_qty", "fill_count", "tape_offset", "status", "reason")
+FIELDS_FILL = ("taker_seq", "maker_seq", "price_q4", "qty", "symbol")
+FIELDS_BOOK = ("seq", "price_q4", "qty", "side")
+
+
+@pytest.fixture(scope="module")
+def orc(built):
+    from oracle import oracle
+
+    return oracle
+
+
+def same(a, b, fields, ctx):
+    assert len(a) == len(b), f"{ctx}: {len(a)} vs {len(b)} entries"
+    for f in fields:
+        if not np.array_equal(np.asarray(a[f]), np.asarray(b[f])):
+            i = int(np.nonzero(np.asarray(a[f]) != np.asarray(b[f]))[0][0])
+            raise AssertionError(f"{ctx}: field {f} differs first at {i}: {a[i]} vs {b[i]}")
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_model_equals_oracle_without_tif(orc, seed):
+    S = 12
+    _, batches = tm.tif_stream(seed, S, 128, 4, 2000, far_pct=3)
+    ob, tb = orc.OracleBook(S), TifBook(S)
+    for k, b in enumerate(batches):
+        p = Arrays(b.seq, b.price_q4, b.qty, b.symbol, b.kind & 0x0F)
+        ro, fo = ob.submit(p)
+        rt, ft = tb.submit(p)
+        same(rt, ro, FIELDS_RES, f"batch {k} results")
+        same(ft, fo, FIELDS_FILL, f"batch {k} tape")
+    for s in range(S):
+        same(tb.dump(s), ob.dump(s), FIELDS_BOOK, f"book {s}")
+    assert tb.resting() == ob.resting()
+
+
+@pytest.mark.parametrize("seed,far", [(3, 0), (4, 4)])
+def test_rewrite_into_plain_records(orc, seed, far):
+    S = 10
+    _, batches = tm.tif_stream(seed, S, 128, 5, 2000, far_pct=far)
+    ob, tb = orc.OracleBook(S), TifBook(S)
+    fills_t, fills_o = [], []
+    n_ioc = n_partial = 0
+    for k, b in enumerate(batches):
+        rt, ft = tb.submit(b)
+        fills_t.append(ft)
+        sq, px, qt, sy, kd, back = [], [], [], [], [], []  # back: (tif record, is the self-cancel)
+        for i, v in enumerate(tb.verdicts):
+            if v == tm.V_DROP:
+                continue
+            sq.append(b.seq[i]); px.append(b.price_q4[i]); qt.append(b.qty[i]); sy.append(b.symbol[i])
+            kd.append(int(b.kind[i]) & 0x0F)
+            back.append((i, False))
+            if v == tm.V_IOC:
+                sq.append(b.seq[i]); px.append(int(b.seq[i])); qt.append(0); sy.append(b.symbol[i])
+                kd.append(kind(BUY, 0, 1))
+                back.append((i, True))
+        ro, fo = ob.submit(Arrays(sq, px, qt, sy, kd))
+        fills_o.append(fo)
+        for j, (i, selfcx) in enumerate(back):
+            v = tb.verdicts[i]
+            if v == tm.V_IOC and not selfcx:
+                n_ioc += 1
+                assert rt[i]["filled_qty"] == ro[j]["filled_qty"], f"batch {k} record {i}: IOC filled"
+                assert rt[i]["fill_count"] == ro[j]["fill_count"]
+                cx = ro[j + 1]
+                removed = 0 if (cx["status"] == ST_REJECTED and cx["reason"] == RJ_UNKNOWN) else int(cx["remaining_qty"])
+                assert rt[i]["remaining_qty"] == removed, f"batch {k} record {i}: IOC remainder"
+                assert rt[i]["status"] == (ST_FILLED if removed == 0 else ST_CANCELED)
+                n_partial += removed > 0 and rt[i]["filled_qty"] > 0
+            elif not selfcx and v in (tm.V_PLAIN, tm.V_POST, tm.V_MARKET):
+                for f in ("filled_qty", "remaining_qty", "fill_count", "status", "reason"):
+                    assert rt[i][f] == ro[j][f], f"batch {k} record {i} ({v}): {f}"
+    same(np.concatenate(fills_t), np.concatenate(fills_o), FIELDS_FILL, "fills")
+    for s in range(S):
+        same(tb.dump(s), ob.dump(s), FIELDS_BOOK, f"book {s}")
+    assert n_ioc > 500 and n_partial > 20
+
+
+# ---- hand-written verdicts -----------------------------------------------------------------------
+
+def _run(records, S=1):
+    """records: (seq, price, qty, kind) on symbol 0 -> results of one batch and the model."""
+    tb = TifBook(S)
+    a = Arrays([r[0] for r in records], [r[1] for r in records], [r[2] for r in records], [0] * len(records),
+               [r[3] for r in records])
+    res, fills = tb.submit(a)
+    return res, fills, tb
+
+
+def _st(r):
+    return (int(r["status"]), int(r["reason"]), int(r["filled_qty"]), int(r["remaining_qty"]), int(r["fill_count"]))
+
+
+def test_fok_exact_and_one_short():
+    asks = [(1, 100, 30, kind(SELL)), (2, 100, 20, kind(SELL))]
+    res, fills, tb = _run(asks + [(3, 100, 50, kind(BUY, 0, 0, TIF_FOK))])
+    assert _st(res[2]) == (ST_FILLED, RJ_NONE, 50, 0, 2) and tb.resting() == 0
+    res, fills, tb = _run(asks + [(3, 100, 51, kind(BUY, 0, 0, TIF_FOK))])
+    assert _st(res[2]) == (ST_CANCELED, RJ_NONE, 0, 51, 0) and len(fills) == 0 and tb.resting() == 2
+    assert res[2]["tape_offset"] == 0
+
+
+def test_fok_several_levels_and_levels_beyond_the_limit():
+    asks = [(1, 100, 10, kind(SELL)), (2, 101, 10, kind(SELL)), (3, 103, 10, kind(SELL))]
+    res, fills, tb = _run(asks + [(4, 101, 20, kind(BUY, 0, 0, TIF_FOK))])
+    assert _st(res[3]) == (ST_FILLED, RJ_NONE, 20, 0, 2)
+    assert [int(p) for p in fills["price_q4"]] == [100, 101]
+    res, fills, tb = _run(asks + [(4, 101, 21, kind(BUY, 0, 0, TIF_FOK))])  # the rest is at 103, beyond the limit
+    assert _st(res[3]) == (ST_CANCELED, RJ_NONE, 0, 21, 0) and tb.resting() == 3
+    bids = [(1, 100, 10, kind(BUY)), (2, 99, 10, kind(BUY))]
+    res, fills, tb = _run(bids + [(3, 99, 20, kind(SELL, 0, 0, TIF_FOK))])
+    assert _st(res[2]) == (ST_FILLED, RJ_NONE, 20, 0, 2)
+
+
+def test_fok_depends_on_an_earlier_record_of_the_batch():
+    recs = [(1, 100, 10, kind(SELL)), (2, 100, 5, kind(BUY, 0, 0, TIF_IOC)), (3, 100, 10, kind(BUY, 0, 0, TIF_FOK)),
+            (4, 100, 5, kind(BUY, 0, 0, TIF_FOK))]
+    res, fills, tb = _run(recs)
+    assert _st(res[1]) == (ST_FILLED, RJ_NONE, 5, 0, 1)
+    assert _st(res[2]) == (ST_CANCELED, RJ_NONE, 0, 10, 0)  # 5 left after the IOC
+    assert _st(res[3]) == (ST_FILLED, RJ_NONE, 5, 0, 1)
+    assert res[2]["tape_offset"] == 1 and res[3]["tape_offset"] == 1
+
+
+def test_market_fok_and_market_ioc():
+    asks = [(1, 100, 10, kind(SELL)), (2, 500, 10, kind(SELL))]
+    res, _, tb = _run(asks + [(3, 0, 20, kind(BUY, 1, 0, TIF_FOK))])
+    assert _st(res[2]) == (ST_FILLED, RJ_NONE, 20, 0, 2)
+    res, _, tb = _run(asks + [(3, 0, 21, kind(BUY, 1, 0, TIF_FOK))])
+    assert _st(res[2]) == (ST_CANCELED, RJ_NONE, 0, 21, 0) and tb.resting() == 2
+    res, _, tb = _run(asks + [(3, 0, 25, kind(BUY, 1, 0, TIF_IOC))])  # a no-op on a MARKET
+    assert _st(res[2]) == (ST_CANCELED, RJ_NONE, 20, 5, 2)
+
+
+def test_ioc_remainder_never_rests():
+    res, _, tb = _run([(1, 100, 10, kind(SELL)), (2, 100, 15, kind(BUY, 0, 0, TIF_IOC)),
+                       (3, 100, 15, kind(BUY, 0, 0, TIF_IOC))])
+    assert _st(res[1]) == (ST_CANCELED, RJ_NONE, 10, 5, 1)
+    assert _st(res[2]) == (ST_CANCELED, RJ_NONE, 0, 15, 0)
+    assert tb.resting() == 0
+
+
+def test_post_only_at_inside_through_and_empty():
+    ask = [(1, 100, 10, kind(SELL))]
+    res, _, tb = _run(ask + [(2, 100, 5, kind(BUY, 0, 0, TIF_POST_ONLY))])  # at the best
+    assert _st(res[1]) == (ST_REJECTED, RJ_WOULD_CROSS, 0, 5, 0) and tb.resting() == 1
+    res, _, tb = _run(ask + [(2, 105, 5, kind(BUY, 0, 0, TIF_POST_ONLY))])  # through it
+    assert _st(res[1]) == (ST_REJECTED, RJ_WOULD_CROSS, 0, 5, 0)
+    res, _, tb = _run(ask + [(2, 99, 5, kind(BUY, 0, 0, TIF_POST_ONLY))])  # inside the spread
+    assert _st(res[1]) == (ST_NEW, RJ_NONE, 0, 5, 0) and tb.resting() == 2
+    res, _, tb = _run([(2, 99, 5, kind(SELL, 0, 0, TIF_POST_ONLY))])  # against an empty side
+    assert _st(res[0]) == (ST_NEW, RJ_NONE, 0, 5, 0)
+    # afterwards an ordinary resting order: it trades and can be cancelled
+    res, _, tb = _run([(1, 99, 5, kind(SELL, 0, 0, TIF_POST_ONLY)), (2, 99, 2, kind(BUY)),
+                       (2, 1, 0, kind(BUY, 0, 1))])
+    assert _st(res[1]) == (ST_FILLED, RJ_NONE, 2, 0, 1) and _st(res[2]) == (ST_CANCELED, RJ_NONE, 0, 3, 0)
+    res, _, tb = _run([(1, 100, 10, kind(BUY)), (2, 100, 5, kind(SELL, 0, 0, TIF_POST_ONLY)),
+                       (3, 101, 5, kind(SELL, 0, 0, TIF_POST_ONLY))])
+    assert _st(res[1]) == (ST_REJECTED, RJ_WOULD_CROSS, 0, 5, 0) and _st(res[2]) == (ST_NEW, RJ_NONE, 0, 5, 0)
+
+
+def test_market_post_only_and_the_reject_order():
+    P = TIF_POST_ONLY
+    res, _, tb1 = _run([(1, 100, 10, kind(SELL)),
+                       (2, 0, 5, kind(BUY, 1, 0, P)),      # BAD_TIF
+                       (3, 0, 0, kind(BUY, 1, 0, P)),      # qty first
+                       (4, 0, 5, kind(0, 1, 0, P)),        # side before tif
+                       (5, 100, 0, kind(BUY, 0, 0, P)),    # qty before WOULD_CROSS
+                       (6, 100, 5, kind(3, 0, 0, P)),      # side before WOULD_CROSS
+                       (7, 100, 5, kind(BUY, 0, 1, P))])   # a cancel ignores the bits
+    assert _st(res[1]) == (ST_REJECTED, RJ_BAD_TIF, 0, 5, 0)
+    assert _st(res[2]) == (ST_REJECTED, RJ_BAD_QTY, 0, 0, 0)
+    assert _st(res[3]) == (ST_REJECTED, RJ_BAD_SIDE, 0, 5, 0)
+    assert _st(res[4]) == (ST_REJECTED, RJ_BAD_QTY, 0, 0, 0)
+    assert _st(res[5]) == (ST_REJECTED, RJ_BAD_SIDE, 0, 5, 0)
+    assert _st(res[6]) == (ST_REJECTED, RJ_UNKNOWN, 0, 0, 0)
+    res, _, _ = _run([(0, 0, 5, kind(BUY, 1, 0, P))])  # seq 0 before tif
+    assert _st(res[0]) == (ST_REJECTED, RJ_BAD_SEQ, 0, 5, 0)
+    assert tb1.resting() == 1
+
+
+# ---- ABI -----------------------------------------------------------------------------------------
+
+def test_abi_declares_and_exports_the_tif_entry(built):
+    from matching_engine_amd import _abi
+
+    hdr = open(os.path.join(ROOT, "include", "me_service.h")).read()
+    assert re.search(r"\bint\s+me_service_submit_order_tif\s*\(", hdr)
+    eh = open(os.path.join(ROOT, "include", "me_engine.h")).read()
+    for name in ("ME_TIF_GTC", "ME_TIF_IOC", "ME_TIF_FOK", "ME_TIF_POST_ONLY", "ME_KIND_TIF", "ME_RJ_WOULD_CROSS",
+                 "ME_RJ_BAD_TIF"):
+        assert name in eh, name
+    assert "me_service_submit_order_tif" in _abi.PROTOTYPES
+    syms = subprocess.run(["nm", "-D", "--defined-only", _abi.LIB_PATH], check=True, capture_output=True,
+                          text=True).stdout
+    assert re.search(r"\bT me_service_submit_order_tif\b", syms)
+    assert _abi.kind(1, 0, 0, _abi.TIF_IOC) == 0x11
+    assert _abi.kind(2, 1, 0) == 6 and _abi.kind(1, 0, 1) == 9  # ME_KIND keeps its value
+    assert (_abi.TIF_GTC, _abi.TIF_IOC, _abi.TIF_FOK, _abi.TIF_POST_ONLY) == (0, 1, 2, 3)
+    assert (_abi.RJ_WOULD_CROSS, _abi.RJ_BAD_TIF) == (8, 9)
+
+
+# ---- the committed fixture ----------------------------------------------------------------------
+
+def load_tif_fixture():
+    z = np.load(os.path.join(ROOT, "tests", "golden", "match_tif.npz"))
+    from oracle.pybook import BOOK_DTYPE, FILL_DTYPE, RESULT_DTYPE
+
+    batches, res, fills = [], [], []
+    for k in range(int(z["nbatches"][0])):
+        batches.append(Arrays(*[z[f"b{k}_{f}"] for f in ("seq", "price_q4", "qty", "symbol", "kind")]))
+        res.append(np.ascontiguousarray(z[f"b{k}_res"]).view(RESULT_DTYPE).reshape(-1))
+        fills.append(np.ascontiguousarray(z[f"b{k}_fills"]).view(FILL_DTYPE).reshape(-1))
+    book = np.ascontiguousarray(z["book"]).view(BOOK_DTYPE).reshape(-1)
+    meta = dict(num_symbols=int(z["num_symbols"][0]), levels=int(z["levels"][0]), base=z["base"],
+                book_counts=z["book_counts"])
+    return meta, batches, res, fills, book
+
+
+def test_fixture_replays_through_the_model():
+    meta, batches, res, fills, book = load_tif_fixture()
+    tb = TifBook(meta["num_symbols"])
+    tifs = set()
+    for k, b in enumerate(batches):
+        r, f = tb.submit(b)
+        same(r, res[k], FIELDS_RES, f"batch {k} results")
+        same(f, fills[k], FIELDS_FILL, f"batch {k} tape")
+        tifs |= set(((b.kind >> 4) & 3).tolist())
+    dumps = np.concatenate([tb.dump(s) for s in range(meta["num_symbols"])])
+    same(dumps, book, FIELDS_BOOK, "final book")
+    assert tifs == {0, 1, 2, 3}
+    reasons = set(np.concatenate([r["reason"] for r in res]).tolist())
+    assert {RJ_WOULD_CROSS, RJ_BAD_TIF} <= reasons
