@@ -20,6 +20,9 @@
  *            sends the entries and levels to rank 0.
  *   SNAPSHOT the periodic book snapshot: every rank's top-N levels of all its symbols
  *            (me_book_levels_all, one launch) gathered to rank 0.
+ *   QUOTES   the top-of-book change feed (me_quotes_*, me_engine.h): every rank drains its shard's events
+ *            and sends them to rank 0, which concatenates them in rank order (QUOTES_ENABLE turns every
+ *            shard's feed on or off).
  *   STOP     the serve loops return.
  * The service keeps two slices in flight through the matcher's submit / collect (SUBMIT of slice k+1
  * runs before COLLECT of slice k), so the shards match k+1 while rank 0 merges and persists k.
@@ -75,6 +78,9 @@ typedef struct me_shard_ops {
               size_t* n_bid_levels, size_t* n_ask_levels);
   /* me_book_levels_all's contract over its local symbols */
   int (*levels_all)(void* ctx, uint32_t depth, me_level* levels, uint32_t* counts);
+  /* optional (NULL: no feed): me_quotes_read's contract over its local symbols (local ids; `batches` = the
+   * parts it has matched) */
+  int (*quotes)(void* ctx, me_quote* out, size_t cap, size_t* n, size_t* left);
 } me_shard_ops;
 
 typedef struct me_cluster me_cluster;
@@ -113,6 +119,17 @@ int me_cluster_book(me_cluster* c, uint32_t symbol, uint32_t depth, me_book_entr
 /* Rank 0: top `depth` levels of every global symbol from every shard:
  * levels[(symbol * 2 + side) * depth + k] (zeros past a side's levels), counts[symbol * 2 + side]. */
 int me_cluster_snapshot(me_cluster* c, uint32_t depth, me_level* levels, uint32_t* counts);
+/* Rank 0: every shard's quote feed on with a log of cap_events events (me_quotes_enable on each engine; a
+ * shard behind me_shard_ops must have `quotes`), or off with 0. Events gathered and not yet read are dropped. */
+int me_cluster_quotes_enable(me_cluster* c, uint64_t cap_events);
+/* Rank 0: me_quotes_read's contract over the whole cluster. When everything gathered before has been handed
+ * out, every rank drains its shard (what it has logged so far: after me_cluster_collect of a slice, that
+ * slice's events) and rank 0 appends the events in rank order; then up to cap of them are handed out, *left
+ * = gathered events still unread. Symbols are global ids. Events of one shard keep their order; `batches` is
+ * the shard's OWN count of matched parts (a shard is not handed a slice that holds none of its symbols), not
+ * a cluster-wide number. Through me_cluster_matcher's `quotes` the same events are stamped with the slice's
+ * number instead (slices the cluster has matched, from 1), as the service requires. */
+int me_cluster_quotes(me_cluster* c, me_quote* out, size_t cap, size_t* n, size_t* left);
 /* Rank 0: the me_matcher over this cluster for me_service_create_matcher (submit / collect set: the
  * service keeps two slices in flight). max_resting = the sum over the shards. */
 int me_cluster_matcher(me_cluster* c, me_matcher* out);

@@ -295,6 +295,58 @@ int me_book_dump(me_engine* e, uint32_t symbol, me_book_entry* out, size_t cap, 
 /* Resting orders over all symbols (device counter). */
 int me_resting_count(me_engine* e, uint64_t* n);
 
+/* ---- top-of-book change feed (StreamMarketData, proto/matching_engine.proto:32,62-69) ---------------
+ * A symbol's QUOTE is (has_bid, bid_price_q4, bid_qty, has_ask, ask_price_q4, ask_qty): per side the
+ * price of the best occupied level and that level's total resting quantity (int64, as level totals
+ * are). A side with no resting order has its flag clear and price and quantity 0; price 0 and negative
+ * prices are legitimate, so the flag, not the price, says whether a side is absent. The best level is
+ * the window's best level of that side when the window holds one, else the side's best far level
+ * (a window level always beats a far level of the same side).
+ *
+ * The feed is CONFLATED PER LAUNCH GROUP: after every match launch (a group of up to batches_per_launch
+ * batches when levels <= 128, a single batch on deeper windows) a device job compares every symbol's
+ * quote with the one last published for it and logs one me_quote for each symbol that differs.
+ * Events of one job ascend by local symbol id, jobs appear in launch order; quotes a symbol passed
+ * through inside a group are not observable. The published state starts as "both sides absent", and
+ * enabling the feed runs the job once at that point of the stream: enabling on resting books yields one
+ * event per symbol with a non-empty side. `batches` is the number of batches (host and device) the
+ * engine had matched when the quote was taken; a batch's ordinal is its 1-based position among all
+ * batches submitted to the engine (ticket t of an engine fed only by me_submit_host: t + 1).
+ *
+ * The log is a bounded ring in pinned memory and never loses a change: a job whose changed symbols do
+ * not fit into the free part of the log (judged by the events the host had read when the job was
+ * enqueued) logs nothing, leaves the published quotes untouched and counts as deferred; its changes
+ * stay pending and come out, conflated, with a later job. After me_sync and reads until *left == 0,
+ * replaying every event ever read gives exactly the current top of every book. */
+typedef struct me_quote { /* 48 B */
+  int64_t bid_price_q4, ask_price_q4;
+  int64_t bid_qty, ask_qty;
+  uint64_t batches;
+  uint32_t symbol; /* the id space of me_fill.symbol (symbol_ids when given) */
+  uint32_t flags;  /* bit 0 has_bid, bit 1 has_ask */
+} me_quote;
+#define ME_QUOTE_HAS_BID 1u
+#define ME_QUOTE_HAS_ASK 2u
+/* cap_events = 0 turns the feed off (an engine that never enables it launches exactly what it launched
+ * without it); else the log's capacity in events, raised to at least num_symbols so that one job always
+ * fits an empty log; more than max(64 * num_symbols, 2^24) events (pinned host memory, 48 B each) is
+ * refused with ME_E_INVALID. Enabling waits for the work in flight and for its own first job (no partial group is
+ * launched), so the read after it holds the whole initial state. Enabling an enabled feed starts it
+ * afresh (published state "both sides absent", unread events dropped). */
+int me_quotes_enable(me_engine* e, uint64_t cap_events);
+/* Hands out logged events in order, at most `cap` of them (out may be NULL when cap is 0); *n = events
+ * copied, *left = events logged and still unread. It launches no partial group and does not wait for
+ * jobs in flight: it returns what the device has logged so far. After me_collect(t) returned, every event
+ * with batches <= t's ordinal is there; after me_sync, every event. One exception: a read that leaves the
+ * log empty while a deferral is outstanding waits for the work in flight and, if that still holds, runs
+ * one catch-up job; its events follow in the same call as far as `cap` allows and count in *left beyond
+ * that, so "read until *left == 0" also drains deferred changes. *n and *left are written on every return, also a
+ * failing one: the caller always knows how many events it holds. ME_E_INVALID while the feed is off. */
+int me_quotes_read(me_engine* e, me_quote* out, size_t cap, size_t* n, size_t* left);
+/* Jobs run, events logged and jobs deferred since the feed was enabled, as of the work the device has
+ * finished (exact after me_sync). Any pointer may be NULL. ME_E_INVALID while the feed is off. */
+int me_quotes_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred);
+
 /* Kernel timing. period >= 1: every period-th match-kernel launch records its own start and end
  * (hipExtLaunchKernelGGL events: no marker packets, though each timed launch still costs the
  * stream a few microseconds, hence the sampling); period <= 0: off. Resets the counters below. */

@@ -111,6 +111,11 @@ typedef struct me_matcher {
    * next collect). Tickets are collected in submission order, at most two outstanding. */
   int (*submit)(void* ctx, const me_order_soa* slice, size_t n, uint64_t* ticket);
   int (*collect)(void* ctx, uint64_t ticket, const me_fill** fills, size_t* n_fills, const me_order_result** results);
+  /* Optional (NULL: no feed): me_quotes_read's contract over the matcher's books — top-of-book change events
+   * in order, at most cap of them, *left = events still unread. `symbol` is the id space of `match`; `batches`
+   * must count the slices the matcher has matched (slice k of this service is stamped k, from 1): the service
+   * names an event's symbol by it (me_service_market_stream). */
+  int (*quotes)(void* ctx, me_quote* out, size_t cap, size_t* n, size_t* left);
 } me_matcher;
 
 /* The service over a matcher instead of an engine (same contract otherwise). NULL on a bad matcher. */
@@ -247,6 +252,29 @@ typedef struct me_market_data {
 } me_market_data;
 
 int me_service_market_data(me_service* s, const char* symbol, me_market_data* out);
+
+/* StreamMarketData (proto/matching_engine.proto:32, MarketDataUpdate :62-69) as a change stream instead of
+ * the poll above: one update per symbol whose top of book changed in a matched slice, from the backend's
+ * quote feed (me_quotes_*, me_engine.h) — nothing is snapshotted and the pipeline is not drained.
+ * md follows me_service_market_data's conventions (scale 4, sizes saturated to int32, has_* flags). */
+typedef struct me_market_update {
+  char symbol[32];
+  me_market_data md;
+} me_market_update;
+/* on != 0: enable the backend's feed — me_quotes_enable on the service's engine (the engine must have been
+ * fresh when the service was created: the service matches event stamps with the slices it submitted), or
+ * the matcher's `quotes` hook — and queue the books' current tops (one update per symbol with a non-empty
+ * side; after restart recovery: the recovered books). ME_E_INVALID with neither. It waits for a running
+ * flush. on == 0: the stream stops and queued updates are dropped. */
+int me_service_market_subscribe(me_service* s, int on);
+/* Drain up to cap queued updates (symbol NULL or "": every symbol; else only that symbol's, leaving the
+ * others queued, as me_service_updates does for clients). After each matched slice the flush path reads
+ * the backend's events and queues them. The queue conflates: a symbol has at most one pending update, a
+ * newer one overwrites its payload and keeps its place, so the queue is bounded by the number of symbols
+ * and nothing is ever dropped. An event is named by the symbol that owned its book at the slice the event
+ * belongs to (its `batches` stamp), so a book handed from an idle symbol to a new one never reports one
+ * symbol's quote under the other's name. *n = updates written; ME_E_INVALID when not subscribed. */
+int me_service_market_stream(me_service* s, const char* symbol, me_market_update* out, size_t cap, size_t* n);
 
 int me_service_last_error(const me_service* s, char* buf, size_t cap);
 

@@ -109,6 +109,13 @@ BOOK_ENTRY_DTYPE = np.dtype(
 )
 assert FILL_DTYPE.itemsize == 32 and RESULT_DTYPE.itemsize == 20
 assert LEVEL_DTYPE.itemsize == 24 and BOOK_ENTRY_DTYPE.itemsize == 24
+# me_quote: one top-of-book change (flags bit 0 has_bid, bit 1 has_ask)
+QUOTE_DTYPE = np.dtype(
+    [("bid_price_q4", "<i8"), ("ask_price_q4", "<i8"), ("bid_qty", "<i8"), ("ask_qty", "<i8"), ("batches", "<u8"),
+     ("symbol", "<u4"), ("flags", "<u4")]
+)
+QUOTE_HAS_BID, QUOTE_HAS_ASK = 1, 2
+assert QUOTE_DTYPE.itemsize == 48
 
 # every symbol include/me_engine.h declares -> (restype, argtypes)
 _P = C.c_void_p
@@ -157,6 +164,9 @@ PROTOTYPES = {
     "me_paths_read": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "me_admission_read": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_admission_check": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int)]),
+    "me_quotes_enable": (C.c_int, [_P, C.c_uint64]),
+    "me_quotes_read": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "me_quotes_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_gen_create": (_P, [C.POINTER(MeGenParams)]),
     "me_gen_destroy": (None, [_P]),
     "me_gen_base_prices": (C.c_int, [_P, _P]),
@@ -259,6 +269,13 @@ class MeMarketData(C.Structure):
         ("pad", C.c_int32),
     ]
 
+class MeMarketUpdate(C.Structure):
+    _fields_ = [("symbol", C.c_char * 32), ("md", MeMarketData)]
+
+
+assert C.sizeof(MeMarketUpdate) == 72, "me_market_update layout"
+
+
 class MeBookOrder(C.Structure):
     _fields_ = [
         ("order_id", C.c_char * 32),
@@ -281,6 +298,7 @@ BOOK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C
 SUBMIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(MeOrderSoa), C.c_size_t, C.POINTER(C.c_uint64))
 COLLECT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                          C.POINTER(C.c_void_p))
+QUOTES_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t))
 
 
 class MeMatcher(C.Structure):
@@ -293,6 +311,7 @@ class MeMatcher(C.Structure):
         ("book", BOOK_FN),
         ("submit", SUBMIT_FN),
         ("collect", COLLECT_FN),
+        ("quotes", QUOTES_FN),
     ]
 
 
@@ -326,6 +345,7 @@ class MeShardOps(C.Structure):
         ("match", MATCH_FN),
         ("book", BOOK_FN),
         ("levels_all", LEVELS_FN),
+        ("quotes", QUOTES_FN),
     ]
 
 
@@ -335,6 +355,10 @@ PROTOTYPES.update({
                                         C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ)]),
     "me_service_cancel_order": (C.c_int, [_P, C.POINTER(MeCancelRequest), C.POINTER(MeOrderResponse)]),
     "me_service_market_data": (C.c_int, [_P, C.c_char_p, C.POINTER(MeMarketData)]),
+    "me_service_market_subscribe": (C.c_int, [_P, C.c_int]),
+    "me_service_market_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeMarketUpdate), _SZ, C.POINTER(_SZ)]),
+    "me_cluster_quotes_enable": (C.c_int, [_P, C.c_uint64]),
+    "me_cluster_quotes": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "me_service_updates": (C.c_int, [_P, C.c_char_p, C.POINTER(MeOrderUpdate), _SZ, C.POINTER(_SZ)]),
     "me_service_create": (_P, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p]),
     "me_service_destroy": (None, [_P]),

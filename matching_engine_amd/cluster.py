@@ -56,6 +56,27 @@ def _book_out(got, bids, bcap, nb, asks, acap, na, bl, al, nbl, nal):
             C.memmove(p, arr.ctypes.data, len(arr) * arr.itemsize)
 
 
+def _quotes_cb(obj):
+    """me_quotes_read's contract over obj.quotes(cap) -> (events QUOTE_DTYPE, events left unread)."""
+
+    def quotes_cb(ctx, out, cap, n, left):
+        try:
+            ev, rest = obj.quotes(int(cap))
+            ev = np.ascontiguousarray(ev, dtype=_abi.QUOTE_DTYPE)
+            assert len(ev) <= cap
+            if len(ev):
+                C.memmove(out, ev.ctypes.data, ev.nbytes)
+            if n:
+                n[0] = len(ev)
+            if left:
+                left[0] = int(rest)
+            return 0
+        except Exception:
+            return _abi.ME_E_STATE
+
+    return quotes_cb
+
+
 def python_matcher(obj) -> MeMatcher:
     """me_matcher over a Python object with match(batch) -> (results, tape), book_orders(symbol, depth)
     -> (bid entries, ask entries, bid levels, ask levels), num_symbols, max_batch, max_resting. Test
@@ -89,6 +110,9 @@ def python_matcher(obj) -> MeMatcher:
     m.match = _abi.MATCH_FN(match_cb)
     m.book = _abi.BOOK_FN(book_cb)
     m._keep = (m.match, m.book, keep)  # the callbacks live as long as the struct
+    if hasattr(obj, "quotes"):  # the top-of-book change feed: quotes(cap) -> (events QUOTE_DTYPE, left)
+        m.quotes = _abi.QUOTES_FN(_quotes_cb(obj))
+        m._keep += (m.quotes,)
     return m
 
 
@@ -138,6 +162,8 @@ class ShardOps:
 
         self.struct = MeShardOps(None, int(max_resting), _abi.ADMIT_FN(admit_cb), _abi.MATCH_FN(match_cb),
                                  _abi.BOOK_FN(book_cb), _abi.LEVELS_FN(levels_cb))
+        if hasattr(book, "quotes"):  # quotes(cap) -> (events QUOTE_DTYPE with local ids, events left unread)
+            self.struct.quotes = _abi.QUOTES_FN(_quotes_cb(book))
 
 
 def shard_symbols(num_symbols: int, world: int, rank: int) -> np.ndarray:
@@ -242,6 +268,27 @@ class Cluster:
         cnt = np.zeros((self.num_symbols, 2), dtype=np.uint32)
         self._check(self.lib.me_cluster_snapshot(self.h, depth, ptr(lv), ptr(cnt)))
         return lv, cnt
+
+    def quotes_enable(self, cap_events: int):
+        """me_cluster_quotes_enable: every shard's quote feed on (a log of cap_events events) or off (0)."""
+        self._check(self.lib.me_cluster_quotes_enable(self.h, int(cap_events)))
+
+    def quotes(self, cap: int = 0):
+        """me_cluster_quotes: (events QUOTE_DTYPE with global symbol ids, left). Drains every shard when all
+        gathered events were handed out; `batches` is each shard's own count."""
+        cap = int(cap) or max(self.num_symbols, 1)
+        out = np.zeros(cap, dtype=_abi.QUOTE_DTYPE)
+        n, left = C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.me_cluster_quotes(self.h, ptr(out), cap, C.byref(n), C.byref(left)))
+        return out[: n.value], left.value
+
+    def quotes_drain(self) -> np.ndarray:
+        parts = []
+        while True:
+            ev, left = self.quotes()
+            parts.append(ev)
+            if not left:
+                return np.concatenate(parts)
 
     def c_matcher(self) -> MeMatcher:
         """me_cluster_matcher: the service on rank 0 is created over it (two slices in flight)."""

@@ -45,7 +45,7 @@ std::mutex g_err_mu;
 std::string g_create_err;
 
 constexpr size_t kRec = 8 + 8 + 4 + 4 + 1;  // packed slice record: seq, price_q4, qty, symbol, kind
-enum : int64_t { CMD_SUBMIT = 1, CMD_COLLECT = 2, CMD_BOOK = 3, CMD_SNAPSHOT = 4, CMD_STOP = 5 };
+enum : int64_t { CMD_SUBMIT = 1, CMD_COLLECT = 2, CMD_BOOK = 3, CMD_SNAPSHOT = 4, CMD_STOP = 5, CMD_QUOTES = 6, CMD_QUOTES_ENABLE = 7 };
 constexpr int kMaxInflight = 2;
 // rank 0's time per protocol phase (me_cluster_phases)
 enum { PH_SPLIT, PH_CTRL, PH_SCATTER, PH_VOTE, PH_MATCH, PH_COLLECT, PH_GATHER, PH_MERGE, PH_SPLIT_COUNT, PH_SPLIT_SLOT, PH_N };
@@ -751,6 +751,13 @@ struct me_cluster {
   uint64_t max_resting_total = 0;
   bool failed = false;
   bool stopped = false;
+  // the quote feed (QUOTES): rank 0 keeps what it gathered until me_cluster_quotes handed it out; every rank
+  // notes which slices (counted over the whole cluster, from 1) its shard matched a part of, so a shard's own
+  // batch count can be turned into the slice's number for the service's matcher
+  std::vector<me_quote> qbuf;
+  size_t qpos = 0;
+  std::deque<uint64_t> qslice;  // qslice[b - 1 - qbase]: the slice that was this shard's b-th batch
+  uint64_t qbase = 0, nslices = 0;
   uint64_t slices = 0;
   std::string err;
 
@@ -1014,6 +1021,8 @@ static int run_submit(me_cluster* c, const int64_t* hdr) {
     return c->fail(ME_E_STATE, "a shard failed to match its part" + (c->eng ? ": " + eng_err(c->eng) : std::string()));
   }
   p.used = true;
+  ++c->nslices;
+  if (p.n) c->qslice.push_back(c->nslices);
   return ME_OK;
 }
 
@@ -1301,8 +1310,84 @@ static int run_snapshot(me_cluster* c, const int64_t* hdr, me_level* levels, uin
   return ME_OK;
 }
 
+// QUOTES_ENABLE: every shard's feed on (hdr[3] = the log's capacity in events) or off (0).
+static int run_quotes_enable(me_cluster* c, const int64_t* hdr) {
+  const uint64_t cap = (uint64_t)hdr[3];
+  int rc = ME_OK;
+  if (!c->failed) {
+    if (c->use_ops)
+      rc = cap && !c->ops.quotes ? ME_E_INVALID : ME_OK;  // (a shard that is not an engine feeds whenever it is asked)
+    else
+      rc = me_quotes_enable(c->eng, cap);
+  }
+  if (!agree(c, rc)) return c->tfail("status");
+  if (rc != ME_OK) return c->fail(rc, "a shard has no quote feed or failed to enable it");
+  if (c->cfg.rank == 0) {
+    c->qbuf.clear();
+    c->qpos = 0;
+  }
+  return ME_OK;
+}
+
+// QUOTES: every rank drains its shard's feed (global symbol ids) and sends the events to rank 0, which
+// appends them in rank order. hdr[3] != 0: `batches` is turned from the shard's own count into the number
+// of the slice (the service's matcher); else it stays the shard's own count.
+static int run_quotes(me_cluster* c, const int64_t* hdr) {
+  const bool restamp = hdr[3] != 0;
+  std::vector<me_quote> ev;
+  int rc = ME_OK;
+  if (!c->failed) {
+    std::vector<me_quote> buf(4096);
+    for (size_t n = 0, left = 1; rc == ME_OK && left;) {
+      left = 0;
+      if (c->use_ops)
+        rc = c->ops.quotes ? c->ops.quotes(c->ops.ctx, buf.data(), buf.size(), &n, &left) : ME_E_INVALID;
+      else
+        rc = me_quotes_read(c->eng, buf.data(), buf.size(), &n, &left);
+      if (rc == ME_OK) ev.insert(ev.end(), buf.begin(), buf.begin() + std::min(n, buf.size()));
+    }
+    const std::vector<uint32_t>& ids = c->members[c->cfg.rank];
+    uint64_t last = 0;
+    for (auto& q : ev) {
+      if (c->use_ops) {  // local ids -> global (an engine shard writes symbol_ids itself)
+        if (q.symbol >= ids.size()) {
+          rc = ME_E_STATE;
+          break;
+        }
+        q.symbol = ids[q.symbol];
+      }
+      last = std::max<uint64_t>(last, q.batches);
+      if (restamp && q.batches) {
+        const uint64_t k = q.batches - 1;
+        q.batches = k >= c->qbase && k - c->qbase < c->qslice.size() ? c->qslice[k - c->qbase] : c->nslices;
+      }
+    }
+    while (last > 1 && c->qbase + 1 < last && !c->qslice.empty()) {  // stamps never decrease: older entries are done
+      c->qslice.pop_front();
+      ++c->qbase;
+    }
+  }
+  if (!agree(c, rc)) return c->tfail("status");
+  if (rc != ME_OK) return c->fail(rc, "a shard failed to read its quote feed");
+  std::vector<char> mine((const char*)ev.data(), (const char*)ev.data() + ev.size() * sizeof(me_quote)), all;
+  std::vector<size_t> bytes;
+  if (!gather_host(c, mine, all, bytes)) return c->tfail("quotes gather");
+  if (c->cfg.rank != 0) return ME_OK;
+  size_t off = 0;
+  for (uint32_t r = 0; r < c->cfg.world; ++r) {
+    const me_quote* q = (const me_quote*)(all.data() + off);
+    c->qbuf.insert(c->qbuf.end(), q, q + bytes[r] / sizeof(me_quote));
+    off += bytes[r];
+  }
+  return ME_OK;
+}
+
 static int dispatch(me_cluster* c, const int64_t* hdr, const BookReq* q, me_level* levels, uint32_t* counts) {
   switch (hdr[0]) {
+    case CMD_QUOTES:
+      return run_quotes(c, hdr);
+    case CMD_QUOTES_ENABLE:
+      return run_quotes_enable(c, hdr);
     case CMD_SUBMIT:
       return run_submit(c, hdr);
     case CMD_COLLECT:
@@ -1449,6 +1534,39 @@ extern "C" int me_cluster_snapshot(me_cluster* c, uint32_t depth, me_level* leve
   return issue(c, hdr, nullptr, levels, counts);
 }
 
+extern "C" int me_cluster_quotes_enable(me_cluster* c, uint64_t cap_events) {
+  if (!c) return ME_E_INVALID;
+  std::vector<int64_t> hdr(c->hdr_words(), 0);
+  hdr[0] = CMD_QUOTES_ENABLE;
+  hdr[3] = (int64_t)cap_events;
+  return issue(c, hdr);
+}
+
+static int cluster_quotes(me_cluster* c, me_quote* out, size_t cap, size_t* n, size_t* left, bool restamp) {
+  if (n) *n = 0;
+  if (left) *left = 0;
+  if (!c || (cap && !out)) return ME_E_INVALID;
+  if (c->qpos == c->qbuf.size()) {  // everything gathered so far was handed out: drain the shards
+    c->qbuf.clear();
+    c->qpos = 0;
+    std::vector<int64_t> hdr(c->hdr_words(), 0);
+    hdr[0] = CMD_QUOTES;
+    hdr[3] = restamp ? 1 : 0;
+    const int rc = issue(c, hdr);
+    if (rc != ME_OK) return rc;
+  }
+  const size_t k = std::min(cap, c->qbuf.size() - c->qpos);
+  if (k) memcpy(out, c->qbuf.data() + c->qpos, k * sizeof(me_quote));
+  c->qpos += k;
+  if (n) *n = k;
+  if (left) *left = c->qbuf.size() - c->qpos;
+  return ME_OK;
+}
+
+extern "C" int me_cluster_quotes(me_cluster* c, me_quote* out, size_t cap, size_t* n, size_t* left) {
+  return cluster_quotes(c, out, cap, n, left, false);
+}
+
 extern "C" int me_cluster_stop(me_cluster* c) {
   if (!c) return ME_E_INVALID;
   std::vector<int64_t> hdr(c->hdr_words(), 0);
@@ -1471,6 +1589,10 @@ static int m_submit(void* ctx, const me_order_soa* b, size_t n, uint64_t* t) {
 static int m_collect(void* ctx, uint64_t t, const me_fill** f, size_t* nf, const me_order_result** r) {
   return me_cluster_collect((me_cluster*)ctx, t, f, nf, r);
 }
+// the service names events by slice number (me_service.h me_matcher.quotes): the shards translate their counts
+static int m_quotes(void* ctx, me_quote* out, size_t cap, size_t* n, size_t* left) {
+  return cluster_quotes((me_cluster*)ctx, out, cap, n, left, true);
+}
 
 extern "C" int me_cluster_matcher(me_cluster* c, me_matcher* out) {
   if (!c || !out) return ME_E_INVALID;
@@ -1484,6 +1606,7 @@ extern "C" int me_cluster_matcher(me_cluster* c, me_matcher* out) {
   out->book = m_book;
   out->submit = m_submit;
   out->collect = m_collect;
+  out->quotes = m_quotes;
   return ME_OK;
 }
 

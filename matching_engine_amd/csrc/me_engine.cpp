@@ -23,6 +23,7 @@
 static_assert(me::ME_C == ME_CHUNK_SLOTS, "chunk width mismatch");
 static_assert(sizeof(me_fill) == 32, "me_fill must be 32 B");
 static_assert(sizeof(me_order_result) == 20, "me_order_result must be 20 B");
+static_assert(sizeof(me_quote) == 48, "me_quote must be 48 B");
 
 namespace me {
 hipError_t launch_sort_pass(hipStream_t st, const uint32_t* keys_in, const uint32_t* idx_in, uint32_t n,
@@ -47,6 +48,7 @@ hipError_t launch_tape_spill(hipStream_t st, const me_order_result* res, const u
                              const me_fill* scratch, unsigned long long cap, me_fill* spill);
 hipError_t launch_init_levels(hipStream_t st, Level* levels, size_t count);
 hipError_t launch_book_snapshot(hipStream_t st, const BookDev& bk, const SnapReq& rq);
+hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q);
 hipError_t launch_init_chunks(hipStream_t st, Chunk* chunks, size_t count);
 }  // namespace me
 
@@ -266,6 +268,14 @@ struct me_engine {
     uint32_t* err = nullptr;
     size_t sym_cap = 0, lv_cap = 0, n_cap = 0, ord_cap = 0, nord_cap = 0, err_cap = 0;
   } snap;
+  // top-of-book change feed (me_quotes_*): off until enabled. The log and the control words' host copy
+  // are pinned and device-mapped (qd.log / qd.hctl are the device's addresses of h_qlog / h_qctl).
+  bool quotes_on = false;
+  QuoteDev qd{};
+  me_quote* h_qlog = nullptr;
+  unsigned long long* h_qctl = nullptr;
+  uint64_t q_consumed = 0;  // events handed out by me_quotes_read
+  uint64_t nmatched = 0;    // batches matched (enqueued match launches), host and device: the events' stamp
   uint32_t last_n = 0;
   uint32_t sq_idx = 0;  // seq-ring state the next k_seq_sweep reads (it writes the other one)
   struct LastGroup {    // the launch group holding the most recent batch: where its outputs live
@@ -331,7 +341,21 @@ static int set_create_err(const std::string& s) {
   return 0;
 }
 
+static void quotes_free(me_engine* e) {
+  void* dp[] = {e->qd.pub, e->qd.cand, e->qd.mask, e->qd.woff, e->qd.ctl};
+  for (void* p : dp)
+    if (p) (void)hipFree(p);
+  if (e->h_qlog) (void)hipHostFree(e->h_qlog);
+  if (e->h_qctl) (void)hipHostFree(e->h_qctl);
+  e->qd = QuoteDev{};
+  e->h_qlog = nullptr;
+  e->h_qctl = nullptr;
+  e->q_consumed = 0;
+  e->quotes_on = false;
+}
+
 static void free_all(me_engine* e) {
+  quotes_free(e);
   void* ptrs[] = {e->bk.levels,   e->bk.occ,      e->bk.sym,      e->bk.chunks,     e->bk.tend,
                   e->bk.loc,      e->bk.chunk_top, e->bk.err,       (void*)e->bk.gsym,
                   e->d_tape,      e->d_tape_count, e->d_fills_acc, e->bk.dbg,      e->bk.fcache,
@@ -929,6 +953,18 @@ static void bucket_job(const me_engine* e, const me_engine::Pend& p, AuxBucket& 
   J.zero_top = o.top;
 }
 
+// The feed's job behind a match launch (or at enable / catch-up time): every symbol's quote against the
+// published one, on the engine stream. `consumed` is the host's count now: the device sees no less free
+// space than there is, and never reads host memory.
+static int quotes_job(me_engine* e) {
+  QuoteDev q = e->qd;
+  q.consumed = e->q_consumed;
+  q.batches = e->nmatched;
+  hipError_t he = launch_quotes(e->stream, e->bk, q);
+  if (he != hipSuccess) return e->hip_fail(he, "quote feed launch");
+  return ME_OK;
+}
+
 // One launch of the pipelined register-ladder path: match group g_match (if any), bucket group nb
 // (if any) and clear the counters its batches will use, compact g_tape's tapes (if any) — then the
 // pipeline shifts by one group.
@@ -1015,6 +1051,13 @@ static int pipe_launch(me_engine* e, const me_engine::Group* nb) {
       if (gt.b[j].slot >= 0) slots[ns++] = gt.b[j].slot;
     int rc = enqueue_host_d2h(e, slots, ns);
     if (rc) return rc;
+  }
+  if (gm.n) {
+    e->nmatched += gm.n;
+    if (e->quotes_on) {  // behind the group's match (side streams joined back), outside its timed span
+      int rc = quotes_job(e);
+      if (rc) return rc;
+    }
   }
   e->g_tape = e->g_match;
   if (nb) {
@@ -1153,6 +1196,11 @@ static int enqueue_batch(me_engine* e, const uint64_t* seq, const int64_t* px, c
   if (he != hipSuccess) return e->hip_fail(he, "match launch");
   e->adm_matched += nadm;
   e->adm_at[++e->launch_no % me_engine::ADM_RING] = e->adm_matched;
+  e->nmatched++;
+  if (e->quotes_on) {  // before the tape job: the slot's completion event then covers the batch's quotes
+    rc = quotes_job(e);
+    if (rc) return rc;
+  }
   if (slot >= 0) {
     HostSlot& h = e->hs[slot];
     h.oset = oset;
@@ -1653,6 +1701,97 @@ extern "C" int me_set_stream(me_engine* e, void* s) {
   }
   HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
   e->stream = s ? (hipStream_t)s : e->own_stream;
+  return ME_OK;
+}
+
+// ---- top-of-book change feed (me_snapshot.hip k_quote_scan / k_quote_emit) -----------------------
+extern "C" int me_quotes_enable(me_engine* e, uint64_t cap_events) {
+  if (!e) return ME_E_INVALID;
+  if (e->failed) return ME_E_STATE;
+  HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
+  if (e->quotes_on) {  // jobs in flight write the log: wait for them before it goes
+    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    quotes_free(e);
+  }
+  if (!cap_events) return ME_OK;
+  const uint64_t S = e->bk.S;
+  const uint64_t cap = std::max<uint64_t>(cap_events, S);
+  // the log is pinned host memory, 48 B per event: 64 jobs in which every symbol changes, at least 2^24
+  // events (768 MB), is more than any reader that keeps up needs; a larger request is a mistake
+  if (cap > std::max<uint64_t>(64 * S, 1ull << 24))
+    return e->fail(ME_E_INVALID, "me_quotes_enable: cap_events above max(64 * num_symbols, 2^24)");
+  QuoteDev& q = e->qd;
+  q.nw = (uint32_t)((S + 63) / 64);
+  q.cap = cap;
+  hipError_t he;
+  if ((he = dalloc(&q.pub, S)) != hipSuccess || (he = dalloc(&q.cand, S)) != hipSuccess ||
+      (he = dalloc(&q.mask, q.nw)) != hipSuccess || (he = dalloc(&q.woff, q.nw)) != hipSuccess ||
+      (he = dalloc(&q.ctl, QC_N)) != hipSuccess ||
+      (he = hipHostMalloc((void**)&e->h_qlog, cap * sizeof(me_quote), hipHostMallocDefault)) != hipSuccess ||
+      (he = hipHostMalloc((void**)&e->h_qctl, QC_N * 8, hipHostMallocDefault)) != hipSuccess ||
+      (he = hipHostGetDevicePointer((void**)&q.log, e->h_qlog, 0)) != hipSuccess ||
+      (he = hipHostGetDevicePointer((void**)&q.hctl, e->h_qctl, 0)) != hipSuccess ||
+      // the published state: both sides absent
+      (he = hipMemsetAsync(q.pub, 0, S * sizeof(QuoteTop), e->stream)) != hipSuccess ||
+      (he = hipMemsetAsync(q.ctl, 0, QC_N * 8, e->stream)) != hipSuccess) {
+    quotes_free(e);
+    return e->hip_fail(he, "me_quotes_enable");
+  }
+  memset(e->h_qctl, 0, QC_N * 8);
+  e->quotes_on = true;
+  // the books as they stand at this point of the stream; a rare call, so it waits: the first read after it
+  // holds the whole initial state
+  int rc = quotes_job(e);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+  return ME_OK;
+}
+
+extern "C" int me_quotes_read(me_engine* e, me_quote* out, size_t cap, size_t* n, size_t* left) {
+  if (n) *n = 0;
+  if (left) *left = 0;
+  if (!e) return ME_E_INVALID;
+  if (!e->quotes_on) return e->fail(ME_E_INVALID, "the quote feed is off (me_quotes_enable)");
+  if (cap && !out) return e->fail(ME_E_INVALID, "null output");
+  volatile unsigned long long* h = e->h_qctl;
+  uint64_t done = 0, tail;
+  for (bool caught_up = false;;) {
+    tail = h[QC_TAIL];
+    std::atomic_thread_fence(std::memory_order_acquire);  // the events were stored before the tail
+    const uint64_t k = std::min<uint64_t>(tail - e->q_consumed, cap - done);
+    const uint64_t at = e->q_consumed % e->qd.cap;
+    const uint64_t first = std::min<uint64_t>(k, e->qd.cap - at);
+    if (first) memcpy(out + done, e->h_qlog + at, first * sizeof(me_quote));
+    if (k > first) memcpy(out + done + first, e->h_qlog, (k - first) * sizeof(me_quote));
+    e->q_consumed += k;
+    done += k;
+    if (n) *n = (size_t)done;  // (kept current: an error below still tells the caller what it holds)
+    if (left) *left = (size_t)(tail - e->q_consumed);
+    if (tail != e->q_consumed || !h[QC_PENDING] || caught_up || e->failed) break;
+    // read empty with a deferral outstanding (as far as the device has got): once everything in flight
+    // is done and that still holds, one catch-up job — the log is empty, so it fits — and its events
+    // follow in this same call (or count in *left)
+    caught_up = true;
+    HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
+    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    if (h[QC_TAIL] == e->q_consumed && h[QC_PENDING]) {
+      int rc = quotes_job(e);
+      if (rc) return rc;
+      HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    }
+  }
+  if (n) *n = (size_t)done;
+  if (left) *left = (size_t)(tail - e->q_consumed);
+  return ME_OK;
+}
+
+extern "C" int me_quotes_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred) {
+  if (!e) return ME_E_INVALID;
+  if (!e->quotes_on) return e->fail(ME_E_INVALID, "the quote feed is off (me_quotes_enable)");
+  volatile unsigned long long* h = e->h_qctl;
+  if (groups) *groups = h[QC_GROUPS];
+  if (events) *events = h[QC_TAIL];
+  if (deferred) *deferred = h[QC_DEFERRED];
   return ME_OK;
 }
 

@@ -480,6 +480,34 @@ struct SnapReq {
   uint32_t* err;             // set on a corrupt chain
 };
 
+// ---- top-of-book change feed (me_snapshot.hip k_quote_scan / k_quote_emit) -----------
+// A symbol's quote: the best occupied level of each side (flags bit 0 has_bid, bit 1 has_ask; an absent
+// side has price and quantity 0). qpub [S] holds the quote last published for every symbol.
+struct alignas(8) QuoteTop {
+  long long bid_px, ask_px;
+  long long bid_qty, ask_qty;
+  uint32_t flags;
+  uint32_t pad;
+};
+static_assert(sizeof(QuoteTop) == 40, "QuoteTop is 40 B");
+// Control words of the feed, kept in HBM (QuoteDev::ctl) and mirrored into pinned memory (QuoteDev::hctl)
+// by every emit pass: events ever logged (the ring's tail), jobs run, jobs deferred, a deferral outstanding.
+enum : uint32_t { QC_TAIL = 0, QC_GROUPS = 1, QC_DEFERRED = 2, QC_PENDING = 3, QC_N = 4 };
+struct QuoteDev {
+  QuoteTop* pub;             // [S] last published quote
+  QuoteTop* cand;            // [S] this job's quote of the symbols that differ from pub
+  unsigned long long* mask;  // [nw] one ballot word per 64 symbols: bit set <=> the symbol differs
+  uint32_t* woff;            // [nw] changed symbols before each word
+  unsigned long long* ctl;   // [QC_N]
+  unsigned long long* hctl;  // [QC_N] host-mapped copy
+  me_quote* log;             // [cap] host-mapped ring: event i sits at i % cap
+  unsigned long long cap;
+  unsigned long long consumed;  // events the host had read when the job was enqueued (<= the tail)
+  unsigned long long batches;   // the job's stamp: batches matched so far
+  uint32_t nw;                  // ceil(S / 64)
+  uint32_t pad;
+};
+
 constexpr int BK_CAP = 128;          // records per bucket (two 64-record blocks)
 constexpr int BK_KIND_SHIFT = 26;    // BkRec::ok: six kind bits (side, type, op, time in force) above the batch index
 constexpr uint32_t BK_KIND_BITS = 63u;

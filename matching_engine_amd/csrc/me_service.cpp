@@ -36,9 +36,11 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -241,6 +243,16 @@ struct me_service {
   std::vector<uint8_t> in_idle;   // ... each at most once: a book's count returns to 0 again and again
   uint64_t reclaimed = 0;
   uint64_t recovered = 0;
+  // --- md_mu: the market-data change stream (me_service_market_subscribe / _stream). Lock order:
+  // flush_mu, eng_mu, md_mu. One pending update per symbol, in first-change order; md_owner names a book's
+  // symbol per slice: {first slice ordinal, symbol}, oldest first (a book changes hands at submit time while
+  // events of earlier slices for its id may still be unread).
+  std::mutex md_mu;
+  std::atomic<bool> md_on{false};
+  std::list<me_market_update> md_q;
+  std::unordered_map<std::string, std::list<me_market_update>::iterator> md_at;
+  std::vector<std::deque<std::pair<uint64_t, std::string>>> md_owner;
+  uint64_t nsub = 0;  // slices the backend accepted since create (eng_mu): slice k's events are stamped k
   // --- background flusher
   std::thread flusher;
   std::condition_variable cv;  // with mu
@@ -605,6 +617,64 @@ static void put(char* dst, size_t cap, const std::string& v) {
   size_t k = v.size() < cap - 1 ? v.size() : cap - 1;
   memcpy(dst, v.data(), k);
   dst[k] = 0;
+}
+
+// ---- the market-data change stream ------------------------------------------------------------
+// Slice number k was accepted by the backend (eng_mu held): the symbols that own its records' books from
+// slice k on. A book's entry is added only when its symbol differs from the last one noted.
+static void md_note_owners(me_service* s, const Slice& sl, uint64_t k) {
+  std::lock_guard<std::mutex> lm(s->md_mu);
+  for (size_t i = 0; i < sl.size(); ++i) {
+    const uint32_t sid = sl.sid[i];
+    if (sid == kNoBook) continue;
+    if (sid >= s->md_owner.size()) s->md_owner.resize((size_t)sid + 1);
+    auto& h = s->md_owner[sid];
+    if (h.empty() || h.back().second != sl.meta[i].symbol) h.emplace_back(k, sl.meta[i].symbol);
+  }
+}
+
+// Read the backend's quote events and queue them, conflated (eng_mu held). An event is named by the symbol
+// that owned its book at slice `batches`; stamps never decrease, so older owners are dropped on the way.
+static int md_pull(me_service* s) {
+  std::vector<me_quote> buf(1024);
+  auto sat = [](int64_t v) { return (int32_t)(v > INT32_MAX ? INT32_MAX : v); };
+  for (;;) {
+    size_t n = 0, left = 0;
+    const int rc = s->eng ? me_quotes_read(s->eng, buf.data(), buf.size(), &n, &left)
+                          : s->m.quotes(s->m.ctx, buf.data(), buf.size(), &n, &left);
+    if (rc != ME_OK) return s->fail(rc, "market stream: reading the backend's quote feed failed: " + backend_err(s));
+    std::lock_guard<std::mutex> lm(s->md_mu);
+    for (size_t i = 0; i < n; ++i) {
+      const me_quote& q = buf[i];
+      if (q.symbol >= s->md_owner.size() || s->md_owner[q.symbol].empty()) continue;  // (a book no slice ever named)
+      auto& h = s->md_owner[q.symbol];
+      while (h.size() > 1 && h[1].first <= q.batches) h.pop_front();
+      const std::string& name = h.front().second;
+      me_market_update u;
+      memset(&u, 0, sizeof u);
+      put(u.symbol, sizeof u.symbol, name);
+      u.md.scale = 4;
+      if (q.flags & ME_QUOTE_HAS_BID) {
+        u.md.has_bid = 1;
+        u.md.best_bid = q.bid_price_q4;
+        u.md.bid_size = sat(q.bid_qty);
+      }
+      if (q.flags & ME_QUOTE_HAS_ASK) {
+        u.md.has_ask = 1;
+        u.md.best_ask = q.ask_price_q4;
+        u.md.ask_size = sat(q.ask_qty);
+      }
+      const std::string key = u.symbol;  // (the name as the update carries it)
+      auto it = s->md_at.find(key);
+      if (it != s->md_at.end()) {
+        *it->second = u;  // newer payload, same place
+      } else {
+        s->md_q.push_back(u);
+        s->md_at.emplace(key, std::prev(s->md_q.end()));
+      }
+    }
+    if (!left) return ME_OK;
+  }
 }
 
 // Close the open slice (mu held).
@@ -1222,6 +1292,7 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
     {
       std::lock_guard<std::mutex> le(s->eng_mu);
       r = backend_collect(s, fl.front());
+      if (r == ME_OK && s->md_on) (void)md_pull(s);  // (a failed read is in last_error; the slice is matched)
     }
     if (r != ME_OK) return lost(r, "engine lost an accepted slice: ");
     Inflight& f = fl.front();
@@ -1250,6 +1321,10 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
     {
       std::lock_guard<std::mutex> le(s->eng_mu);
       r = backend_submit(s, f, accepted);
+      if (accepted) {
+        ++s->nsub;
+        if (s->md_on) md_note_owners(s, f.sl, s->nsub);
+      }
     }
     if (r != ME_OK && !accepted) {  // refused: the slices before it go first, then it is split
       while (!fl.empty())
@@ -1479,6 +1554,65 @@ extern "C" int me_service_market_data(me_service* s, const char* symbol, me_mark
     out->best_ask = a.price_q4;
     out->ask_size = sat(a.total_qty);
   }
+  return ME_OK;
+}
+
+extern "C" int me_service_market_subscribe(me_service* s, int on) {
+  if (!s) return ME_E_INVALID;
+  std::lock_guard<std::mutex> lf(s->flush_mu);  // no slice is in flight while it is held
+  std::lock_guard<std::mutex> le(s->eng_mu);
+  if (!on) {
+    if (s->md_on && s->eng) me_quotes_enable(s->eng, 0);
+    std::lock_guard<std::mutex> lm(s->md_mu);
+    s->md_on = false;
+    s->md_q.clear();
+    s->md_at.clear();
+    s->md_owner.clear();
+    return ME_OK;
+  }
+  if (!s->eng && !s->m.quotes) return s->fail(ME_E_INVALID, "market stream: the backend has no quote feed");
+  if (s->eng) {
+    const int rc = me_quotes_enable(s->eng, std::max<uint64_t>(4ull * s->sym_cap, 1024));
+    if (rc != ME_OK) return s->fail(rc, "market stream: me_quotes_enable failed: " + backend_err(s));
+  }
+  std::vector<std::string> names;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    names = s->names;
+  }
+  {
+    std::lock_guard<std::mutex> lm(s->md_mu);
+    s->md_q.clear();
+    s->md_at.clear();
+    s->md_owner.assign(names.size(), {});
+    for (size_t i = 0; i < names.size(); ++i) s->md_owner[i].emplace_back(0, names[i]);
+    s->md_on = true;
+  }
+  return md_pull(s);  // the books as they stand
+}
+
+extern "C" int me_service_market_stream(me_service* s, const char* symbol, me_market_update* out, size_t cap,
+                                        size_t* n) {
+  if (n) *n = 0;
+  if (!s || (cap && !out)) return ME_E_INVALID;
+  std::lock_guard<std::mutex> lm(s->md_mu);
+  if (!s->md_on) return s->fail(ME_E_INVALID, "market stream: not subscribed (me_service_market_subscribe)");
+  size_t k = 0;
+  if (symbol && *symbol) {
+    auto it = s->md_at.find(std::string(symbol).substr(0, sizeof(out->symbol) - 1));
+    if (it != s->md_at.end() && cap) {
+      out[k++] = *it->second;
+      s->md_q.erase(it->second);
+      s->md_at.erase(it);
+    }
+  } else {
+    while (k < cap && !s->md_q.empty()) {
+      out[k++] = s->md_q.front();
+      s->md_at.erase(s->md_q.front().symbol);
+      s->md_q.pop_front();
+    }
+  }
+  if (n) *n = k;
   return ME_OK;
 }
 

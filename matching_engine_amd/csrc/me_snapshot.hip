@@ -210,6 +210,142 @@ __global__ __launch_bounds__(SNAP_T) void k_book_snapshot(BookDev bk, SnapReq rq
   }
 }
 
+// ---- top-of-book change feed (me_quotes_*, include/me_engine.h; StreamMarketData, proto:32,62-69) ----
+// Two launches behind every match launch of an engine with the feed on.
+//
+// k_quote_scan: one lane per symbol. It reads the symbol's state (64 B), walks each side of the window
+// from the best-level hint to the first occupied level (one 16-B Level when the hint is exact; an empty
+// level is stepped over, as k_book_snapshot does), falls back to the side's best far level (the last
+// occupied entry of its region: 16 B FarDir + 32 B FarLevel) only when the window side is empty, and
+// compares with the published quote (40 B). A symbol that differs writes its quote to `cand`; every
+// wave writes its ballot word. ~136 B read per symbol with an idle far side, 40 B written per change.
+//
+// k_quote_emit: one workgroup. It prefixes the words' popcounts (S / 64 words: 1,563 at 100,000
+// symbols, two block scans), checks the total against the free part of the log, and — only if it fits —
+// writes the events in symbol order (a wave per word, a lane per set bit: position = the word's offset
+// + the bits below the lane) and updates the published quotes. A job that does not fit changes nothing
+// but the deferral counters. The log and the control words' host copy are pinned host memory written
+// through the device mapping with plain vector stores; the tail is stored after a system-scope fence
+// behind the events, so a host that reads the tail first never sees an unwritten event.
+__device__ __forceinline__ bool quote_far_best(const BookDev& bk, uint32_t s, uint32_t side, uint32_t nfar,
+                                               long long& px, long long& qty) {
+  if (!nfar) return false;
+  const FarDir fd = bk.fdir[(size_t)s * 2u + side];
+  const FarLevel* far = bk.far + fd.off;
+  for (uint32_t n = min(nfar, fd.cap); n; --n) {
+    const long long t = far[n - 1].total;
+    if (t > 0) {
+      px = far[n - 1].price;
+      qty = t;
+      return true;
+    }
+  }
+  return false;
+}
+
+__global__ __launch_bounds__(256) void k_quote_scan(BookDev bk, QuoteDev q) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  const int L = (int)bk.L;
+  bool changed = false;
+  if (s < bk.S) {
+    const SymState st = bk.sym[s];
+    const Level* lv = bk.levels + (size_t)s * L;
+    QuoteTop c;
+    c.bid_px = c.ask_px = c.bid_qty = c.ask_qty = 0;
+    c.flags = 0;
+    c.pad = 0;
+    int lb = min(st.best_bid, L - 1);
+    long long t = 0;
+    while (lb >= 0 && (t = lv[lb].total) <= 0) --lb;
+    if (lb >= 0) {
+      c.bid_px = st.base + lb;
+      c.bid_qty = t;
+      c.flags |= ME_QUOTE_HAS_BID;
+    } else if (quote_far_best(bk, s, 0u, st.nfar[0], c.bid_px, c.bid_qty)) {
+      c.flags |= ME_QUOTE_HAS_BID;
+    }
+    int la = max(max(st.best_ask, 0), lb + 1);
+    t = 0;
+    while (la < L && (t = lv[la].total) <= 0) ++la;
+    if (la < L) {
+      c.ask_px = st.base + la;
+      c.ask_qty = t;
+      c.flags |= ME_QUOTE_HAS_ASK;
+    } else if (quote_far_best(bk, s, 1u, st.nfar[1], c.ask_px, c.ask_qty)) {
+      c.flags |= ME_QUOTE_HAS_ASK;
+    }
+    const QuoteTop p = q.pub[s];
+    changed = c.flags != p.flags || c.bid_px != p.bid_px || c.ask_px != p.ask_px || c.bid_qty != p.bid_qty ||
+              c.ask_qty != p.ask_qty;
+    if (changed) q.cand[s] = c;
+  }
+  const unsigned long long m = __ballot(changed);
+  const uint32_t w = s >> 6;
+  if ((threadIdx.x & 63u) == 0u && w < q.nw) q.mask[w] = m;
+}
+
+__global__ __launch_bounds__(SNAP_T) void k_quote_emit(BookDev bk, QuoteDev q) {
+  __shared__ uint32_t wsum[SNAP_T / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  // changed symbols before every word, and in all
+  uint32_t run = 0;
+  for (uint32_t base = 0; base < q.nw; base += SNAP_T) {
+    const uint32_t w = base + tid;
+    const uint32_t pc = w < q.nw ? (uint32_t)__popcll(q.mask[w]) : 0u;
+    uint32_t tot = 0;
+    const uint32_t ex = snap_block_excl_scan(pc, wsum, tot);
+    if (w < q.nw) q.woff[w] = run + ex;
+    run += tot;
+  }
+  const unsigned long long tail = q.ctl[QC_TAIL];
+  const unsigned long long used = tail - q.consumed;  // (consumed <= tail: the host reads only logged events)
+  const bool fit = used <= q.cap && run <= q.cap - used;
+  __syncthreads();  // the offsets are written, the tail is read
+  if (fit && run) {
+    for (uint32_t w = wv; w < q.nw; w += SNAP_T / 64) {
+      const unsigned long long m = q.mask[w];
+      if (!((m >> lane) & 1ull)) continue;
+      const uint32_t s = w * 64u + lane;
+      const uint32_t pos = q.woff[w] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      const QuoteTop c = q.cand[s];
+      me_quote ev;
+      ev.bid_price_q4 = c.bid_px;
+      ev.ask_price_q4 = c.ask_px;
+      ev.bid_qty = c.bid_qty;
+      ev.ask_qty = c.ask_qty;
+      ev.batches = q.batches;
+      ev.symbol = bk.gsym ? bk.gsym[s] : s;
+      ev.flags = c.flags;
+      q.log[(tail + pos) % q.cap] = ev;
+      q.pub[s] = c;
+    }
+    __threadfence_system();
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned long long groups = q.ctl[QC_GROUPS] + 1ull;
+    const unsigned long long deferred = q.ctl[QC_DEFERRED] + (fit ? 0ull : 1ull);
+    const unsigned long long ntail = fit ? tail + run : tail;
+    q.ctl[QC_TAIL] = ntail;
+    q.ctl[QC_GROUPS] = groups;
+    q.ctl[QC_DEFERRED] = deferred;
+    q.ctl[QC_PENDING] = fit ? 0ull : 1ull;
+    volatile unsigned long long* h = q.hctl;
+    h[QC_GROUPS] = groups;
+    h[QC_DEFERRED] = deferred;
+    h[QC_PENDING] = fit ? 0ull : 1ull;
+    __threadfence_system();
+    h[QC_TAIL] = ntail;
+  }
+}
+
+// The feed's job: scan + emit on st (behind the match launch whose quotes it takes).
+hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q) {
+  hipLaunchKernelGGL(k_quote_scan, dim3((bk.S + 255u) / 256u), dim3(256), 0, st, bk, q);
+  hipLaunchKernelGGL(k_quote_emit, dim3(1), dim3(SNAP_T), 0, st, bk, q);
+  return hipGetLastError();
+}
+
 hipError_t launch_book_snapshot(hipStream_t st, const BookDev& bk, const SnapReq& rq) {
   if (!rq.nsym || !rq.depth) return hipSuccess;
   hipLaunchKernelGGL(k_book_snapshot, dim3(rq.nsym * 2), dim3(SNAP_T), 0, st, bk, rq);

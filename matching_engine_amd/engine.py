@@ -352,6 +352,35 @@ class Engine:
         _check(self.lib, self.h, self.lib.me_admission_read(self.h, C.byref(r), C.byref(b), C.byref(x)))
         return {"resting": r.value, "bound": b.value, "exact_counts": x.value}
 
+    # -- top-of-book change feed (me_quotes_*)
+    def quotes_enable(self, cap_events: int):
+        """Turn the quote feed on with a log of cap_events events (raised to num_symbols), or off with 0.
+        Enabling takes every symbol's quote once at this point of the stream."""
+        _check(self.lib, self.h, self.lib.me_quotes_enable(self.h, int(cap_events)))
+
+    def quotes_read(self, cap: int = 0):
+        """(events QUOTE_DTYPE, left): up to `cap` logged events in order (0 = a buffer of num_symbols) and
+        how many stay unread. Launches no partial group; see me_quotes_read for what is there when."""
+        cap = int(cap) or self.num_symbols
+        out = np.zeros(cap, dtype=_abi.QUOTE_DTYPE)
+        n, left = C.c_size_t(0), C.c_size_t(0)
+        _check(self.lib, self.h, self.lib.me_quotes_read(self.h, ptr(out), cap, C.byref(n), C.byref(left)))
+        return out[: n.value], left.value
+
+    def quotes_drain(self) -> np.ndarray:
+        """Every logged event: reads until none is left (a deferred job's catch-up included)."""
+        parts = []
+        while True:
+            ev, left = self.quotes_read()
+            parts.append(ev)
+            if not left:
+                return np.concatenate(parts)
+
+    def quotes_stats(self) -> dict:
+        g, ev, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib, self.h, self.lib.me_quotes_stats(self.h, C.byref(g), C.byref(ev), C.byref(d)))
+        return {"groups": g.value, "events": ev.value, "deferred": d.value}
+
     # -- timing
     def timing_enable(self, period: int = 1):
         """HIP events on every `period`-th match launch (True = every launch, 0/False = off)."""

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (FILL_DTYPE, LEVEL_DTYPE, RESULT_DTYPE, MeBookOrder, MeCancelRequest, MeOrderRequest,
-                   MeOrderResponse, MeMarketData, MeOrderUpdate, ptr)
+                   MeOrderResponse, MeMarketData, MeMarketUpdate, MeOrderUpdate, ptr)
 
 
 class ServiceError(RuntimeError):
@@ -155,6 +155,35 @@ class MatchingEngineService:
         return {"symbol": symbol, "best_bid": m.best_bid, "best_ask": m.best_ask, "scale": m.scale,
                 "bid_size": m.bid_size, "ask_size": m.ask_size, "has_bid": bool(m.has_bid),
                 "has_ask": bool(m.has_ask)}
+
+    def market_subscribe(self, on: bool = True):
+        """StreamMarketData as a change stream (me_service_market_subscribe): enable the backend's quote
+        feed and queue the books' current tops. ServiceError (code ME_E_INVALID) without a feed."""
+        rc = self.lib.me_service_market_subscribe(self.h, 1 if on else 0)
+        if rc != 0:
+            e = ServiceError(f"market_subscribe failed ({rc}): {self.last_error()}")
+            e.code = rc
+            raise e
+
+    def market_stream(self, symbol=None, cap=4096) -> list:
+        """Drain the queued MarketDataUpdates (one symbol's, or all in first-change order): dicts shaped
+        like market_data()'s."""
+        out = []
+        buf = (MeMarketUpdate * cap)()
+        while True:
+            n = C.c_size_t(0)
+            rc = self.lib.me_service_market_stream(self.h, symbol.encode() if symbol else None, buf, cap, C.byref(n))
+            if rc != 0:
+                e = ServiceError(f"market_stream failed ({rc}): {self.last_error()}")
+                e.code = rc
+                raise e
+            for u in buf[: n.value]:
+                m = u.md
+                out.append({"symbol": u.symbol.decode(), "best_bid": m.best_bid, "best_ask": m.best_ask,
+                            "scale": m.scale, "bid_size": m.bid_size, "ask_size": m.ask_size,
+                            "has_bid": bool(m.has_bid), "has_ask": bool(m.has_ask)})
+            if n.value < cap:
+                return out
 
     def get_order_book(self, symbol, depth=10):
         bids = np.zeros(depth, dtype=LEVEL_DTYPE)
