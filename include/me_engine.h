@@ -378,7 +378,7 @@ int me_chunk_stats(me_engine* e, uint64_t* reclaims, uint64_t* high_water, uint6
 
 /* The matching paths the engine runs now (no reference counterpart: the reference has one CPU path).
  * *flags bit 0 (ME_PATH_GROUPED_AGG): launch groups of windows <= 128 levels go through the aggregate
- * path (k_agg_gwalk); bit 1 (ME_PATH_HOT_AGG): hot symbols of deeper windows do. */
+ * path (k_agg_gwalk2); bit 1 (ME_PATH_HOT_AGG): hot symbols of deeper windows do. */
 #define ME_PATH_GROUPED_AGG 1u
 #define ME_PATH_HOT_AGG 2u
 #define ME_PATH_GROUPED_CANCELS 4u /* the grouped walk covers cancels (k_agg_gwalk_cx) */

@@ -2216,7 +2216,7 @@ __global__ __launch_bounds__(256) void k_agg_out(BookDev bk, BatchDev bt, AggDev
 
 // ------------------------------------------------------------------ grouped launches (L <= 128)
 // The register-window path's groups of up to ME_GMAX bucketed batches, every symbol through the
-// aggregate path: k_agg_gwalk (one wave per symbol over its records of every batch of the group, from
+// aggregate path: k_agg_gwalk2 (one workgroup per symbol over its records of every batch of the group, from
 // the batches' buckets, in batch order) replaces k_match_reg's serial loop, logging 8-B events (AggGEv);
 // k_agg_gres (one workgroup per symbol) resolves every level's FIFO, places each batch's fills in its own
 // scratch (the symbol's slab, or the overflow region) and fills in the results the pipeline's tape job
@@ -2296,180 +2296,8 @@ __device__ __forceinline__ uint32_t a_ghand(const BookDev& bk, uint32_t s, uint3
   return rl32(idx, 0);
 }
 
-__global__ __launch_bounds__(64) void k_agg_gwalk(BookDev bk, AggGArgs ga, AggDev ag) {
-  __shared__ AStage stg;
-  const int lane = lane_id();
-  const int L = (int)bk.L;  // <= 128
-  const uint32_t ng = ga.ng;
-  for (uint32_t s = blockIdx.x; s < bk.S; s += gridDim.x) {
-    // lane g < ng: the symbol's records in batch g
-    const uint32_t gl = min((uint32_t)lane, ng - 1u);
-    const uint32_t nsv = (uint32_t)lane < ng ? ga.bcnt[gl][(size_t)s * BK_CNT_STRIDE] : 0u;
-    long long t = (long long)nsv;
-    const uint32_t total = (uint32_t)rli64(wave_incl_scan(t), 63);
-    const SymState st = bk.sym[s];
-    const long long base = rli64(st.base, 0);
-    const int bb0 = rli32(st.best_bid, 0), ba0 = rli32(st.best_ask, 0);
-    const uint32_t resting = rl32(st.resting, 0);
-    const uint32_t nfar0 = rl32(st.nfar[0], 0), nfar1 = rl32(st.nfar[1], 0);
-    gptr<AggSlot> slot = (gptr<AggSlot>)(ag.slot + s);
-    const uint32_t evneed = 3u * total + min((uint32_t)L, resting) + 64u;
-    uint32_t eb = 0;
-    if (total && lane == 0) eb = atomicAdd(&ag.ctr[AC_EV], evneed + 64u);
-    eb = (rl32(eb, 0) + 63u) & ~63u;
-    const bool eok = (unsigned long long)eb + evneed <= ag.ev_cap;
-    if (lane == 0) {
-      AggSlot o{};
-      o.s = s;
-      o.base = base;
-      o.ev_base = eb;
-      o.lo = evneed;  // the region: evneed 8-B events, then the records' seqs and positions [total] each
-      o.hi = total;   // (8 evneed + 8 total <= 16 evneed bytes: the region reserved in 16-B units)
-      o.free_head = st.free_head;
-      o.resting0 = resting;
-      o.bb = bb0;
-      o.ba = ba0;
-      o.active = 0;
-      o.hidx = NIL;
-      o.gs = bk.gsym ? bk.gsym[s] : s;
-      *slot = o;
-    }
-    if (!total) continue;
-    GR_STAMP(bk, s, 0);
-#ifdef ME_STAMPS
-    unsigned long long gw_t[4] = {0ull, 0ull, 0ull, 0ull}, gw_m = stamp_now();
-#endif
-    if (!eok || !a_reserve(ag, slot, resting, total)) {  // no room in the pools: the whole group of the
-                                                          // symbol goes to the continuation
-      const uint32_t g0 = (uint32_t)__builtin_ctzll(__ballot(nsv != 0u));
-      a_ghand(bk, s, g0, 0u, rl32(nsv, (int)g0), s * ga.slab, s * ga.slab + ga.slab);
-      continue;
-    }
-    // free chunks k_match_reg parked in fcache[s][0, nfree) join the front of the free list (one header
-    // store per lane), so k_agg_gres reuses them before it takes fresh chunks, and writes nfree = 0
-    {
-      const uint32_t nfc = min(rl32(st.nfree, 0), 64u);
-      if (nfc) {
-        const uint32_t fc = bk.fcache[(size_t)s * 64u + lane];
-        const uint32_t nx = (uint32_t)__shfl((int)fc, min(lane + 1, 63), 64);
-        if ((uint32_t)lane < nfc) bk.chunks[fc].hdr.next = (uint32_t)lane + 1u < nfc ? nx : st.free_head;
-        if (lane == 0) slot->free_head = fc;
-      }
-    }
-    LEvG w;
-    AggGEv* const log8 = reinterpret_cast<AggGEv*>(ag.ev + eb);
-    le_init(w, log8, 0u);  // (w.evp: relative to the region)
-    // the records' seqs (offset from the group's first) and grouped positions, in walk order
-    const gptr<uint32_t> rsq = vptr(reinterpret_cast<uint32_t*>(log8 + evneed));
-    const gptr<uint32_t> rjs = rsq + total;
-    const unsigned long long gmin = *ga.seq0;
-    uint32_t rbase = 0;
-    RWalk lw;
-    const bool lok = lw_init(lw, bk, s, bb0, ba0);  // else: the continuation from the first record
-    uint32_t hidx = NIL, gstop = ng;
-    // a batch's bucket is loaded while the batch before it runs (no HBM round trip between batches)
-    // (only the lanes of the bucket's records load: a 128-slot bucket holds ~64 at config 2)
-    const size_t bko = (size_t)s * BK_CAP;
-    BkRec n0{}, n1{};
-    auto bload = [&](uint32_t g) {
-      const uint32_t c = rl32(nsv, (int)g);
-      if ((uint32_t)lane < c) n0 = ga.b_rec[g][bko + lane];
-      if (64u + (uint32_t)lane < c) n1 = ga.b_rec[g][bko + 64 + lane];
-    };
-    bload(0);
-    for (uint32_t g = 0; g < ng; ++g) {
-      if (lane == 0) *a_gtab(ag.gev, s, g) = eb + w.evp;
-      const uint32_t cnt = rl32(nsv, (int)g);
-      const BkRec r0 = n0, r1 = n1;
-      if (g + 1u < ng) bload(g + 1u);
-      if (!cnt) continue;
-      if (cnt > (uint32_t)BK_CAP) {  // an overfull bucket: the continuation rescans the batch
-        hidx = a_ghand(bk, s, g, 0u, cnt, 0u, 0u);
-        gstop = g;
-        break;
-      }
-      if (lane == 0) ga.bcnt[g][(size_t)s * BK_CNT_STRIDE] = 0u;  // ready for a later group's bucket job
-      stg.seq[lane] = r0.seq;
-      stg.seq[64 + lane] = r1.seq;
-      stg.px[lane] = r0.px;
-      stg.px[64 + lane] = r1.px;
-      stg.qty[lane] = r0.qty;
-      stg.qty[64 + lane] = r1.qty;
-      stg.ok[lane] = r0.ok;
-      stg.ok[64 + lane] = r1.ok;
-      uint32_t k0 = (uint32_t)lane < cnt ? ((r0.ok & BK_IDX_MASK) << 7) | (uint32_t)lane : ~0u;
-      uint32_t k1 = 64u + (uint32_t)lane < cnt ? ((r1.ok & BK_IDX_MASK) << 7) | (64u + (uint32_t)lane) : ~0u;
-      if (cnt > 64u)
-        a_sort128(k0, k1);
-      else
-        k0 = a_sort64(k0, false);
-      wave_mem_order();
-      me_order_result* res = ga.res[g];
-      bool stop = false;
-      GW_T(0);
-      for (uint32_t blk = 0; blk < cnt; blk += 64) {
-        const uint32_t key = blk ? k1 : k0;
-        const bool v = blk + (uint32_t)lane < cnt;
-        const uint32_t sl = key & (BK_CAP - 1), oi = v ? key >> 7 : 0u;
-        const unsigned long long oseq = stg.seq[sl];
-        const long long opx = stg.px[sl];
-        const int oq = v ? stg.qty[sl] : 0;
-        const uint32_t okd = v ? stg.ok[sl] >> BK_KIND_SHIFT : 0u;
-        const uint32_t cntb = min(64u, cnt - blk);
-        uint32_t rj;
-        int olm;
-        const unsigned long long fastm = __ballot(a_classify(v, oseq, opx, oq, okd, base, L, nfar0, nfar1, rj, olm));
-        int rr = 0;
-        const bool adm = lok && lw_admit(lw, v ? oq : 0);
-        if (v) {
-          rsq[rbase + (uint32_t)lane] = (uint32_t)(oseq - gmin);
-          rjs[rbase + (uint32_t)lane] = (g << AGG_GSHIFT) | oi;
-        }
-        GW_T(1);
-        const uint32_t k = lw_block<AGG_GREC_SHIFT>(w, lw, oq, lw_cw(okd, olm, rj, L), rbase, adm ? fastm : 0ull,
-                                                     cntb, rr);
-        rbase += cntb;
-        GW_T(2);
-#ifdef ME_STAMPS
-        gw_t[3] += k;
-#endif
-        if (v && (uint32_t)lane < k) res[oi] = a_result(oq, okd, rj, rr);  // fills: k_agg_gres
-        if (k < cntb) {
-          hidx = a_ghand(bk, s, g, blk + k, cnt, 0u, 0u);  // scratch position: k_agg_gres
-          stop = true;
-          break;
-        }
-      }
-      if (stop) {
-        gstop = g;
-        break;
-      }
-    }
-    // the log's end for every batch from the stop on
-    for (uint32_t g = (gstop < ng ? gstop + 1u : ng) + (uint32_t)lane; g <= ng; g += 64)
-      *a_gtab(ag.gev, s, g) = eb + w.evp;
-    if (gstop < ng && lane == 0) *a_gtab(ag.gev, s, gstop + 1u) = eb + w.evp;
-    le_end(w);
-    if (lok) lw_end(lw, bk, s);  // (else the LDS copy is truncated and nothing was walked)
-    const int bb = lw.bb, ba = lw.ba;
-    if (lane == 0) {
-      slot->ev_cnt = w.evp;
-      slot->bb = bb;
-      slot->ba = ba;
-      slot->active = 1;
-      slot->hidx = hidx;
-      slot->pos = gstop;  // the batch the continuation starts in (ng: none)
-    }
-    GR_STAMP(bk, s, 1);
-#ifdef ME_STAMPS
-    if (lane == 0)
-      for (int q = 0; q < 4; ++q) bk.dbg[(size_t)s * 24u + q] = gw_t[q];
-#endif
-  }
-}
-
-// The same walk with its per-batch set-up on a second wave (ME_GW_HELPER, default on). The walker's batch
-// set-up — the bucket's load (and, gfx9's single in-order vmcnt, the wait for every store the last batch's
+// The walk's workgroup is two waves: the per-batch set-up runs on a helper wave. On one wave that set-up —
+// the bucket's load (and, gfx9's single in-order vmcnt, the wait for every store the last batch's
 // records issued), its LDS staging, the batch-order sort, the records' classification and control words,
 // the admission sums, the records' seq / position arrays — was ~110 of the ~615 cycles a record took on the
 // walker's chain (tools/gres_probe.py, profiles/r5/s2). Here wave 1 prepares batch g + 1 into one of two LDS
@@ -2489,10 +2317,11 @@ struct GwShared {
   uint32_t go, eb, stop[2];
 };
 
-__device__ __forceinline__ void gw_prepare(GwBuf& B, AStage& stg, const AggGArgs& ga, uint32_t g, uint32_t cnt,
-                                           size_t bko, long long base, int L, uint32_t nfar0, uint32_t nfar1,
-                                           gptr<uint32_t> rsq, gptr<uint32_t> rjs, unsigned long long gmin,
-                                           uint32_t& rbase) {
+// The head of the helper's batch set-up: the symbol's bucket of batch g (cnt <= BK_CAP records; only their
+// lanes load: a 128-slot bucket holds ~64 at config 2) staged in LDS, and the records' slots sorted into
+// batch order — k0 / k1: key (index in the batch << 7 | slot) of records lane and 64 + lane.
+__device__ __forceinline__ void gw_stage(AStage& stg, const AggGArgs& ga, uint32_t g, uint32_t cnt, size_t bko,
+                                         uint32_t& k0, uint32_t& k1) {
   const int lane = lane_id();
   BkRec r0{}, r1{};
   if ((uint32_t)lane < cnt) r0 = ga.b_rec[g][bko + lane];
@@ -2505,13 +2334,22 @@ __device__ __forceinline__ void gw_prepare(GwBuf& B, AStage& stg, const AggGArgs
   stg.qty[64 + lane] = r1.qty;
   stg.ok[lane] = r0.ok;
   stg.ok[64 + lane] = r1.ok;
-  uint32_t k0 = (uint32_t)lane < cnt ? ((r0.ok & BK_IDX_MASK) << 7) | (uint32_t)lane : ~0u;
-  uint32_t k1 = 64u + (uint32_t)lane < cnt ? ((r1.ok & BK_IDX_MASK) << 7) | (64u + (uint32_t)lane) : ~0u;
+  k0 = (uint32_t)lane < cnt ? ((r0.ok & BK_IDX_MASK) << 7) | (uint32_t)lane : ~0u;
+  k1 = 64u + (uint32_t)lane < cnt ? ((r1.ok & BK_IDX_MASK) << 7) | (64u + (uint32_t)lane) : ~0u;
   if (cnt > 64u)
     a_sort128(k0, k1);
   else
     k0 = a_sort64(k0, false);
   wave_mem_order();
+}
+
+__device__ __forceinline__ void gw_prepare(GwBuf& B, AStage& stg, const AggGArgs& ga, uint32_t g, uint32_t cnt,
+                                           size_t bko, long long base, int L, uint32_t nfar0, uint32_t nfar1,
+                                           gptr<uint32_t> rsq, gptr<uint32_t> rjs, unsigned long long gmin,
+                                           uint32_t& rbase) {
+  const int lane = lane_id();
+  uint32_t k0, k1;
+  gw_stage(stg, ga, g, cnt, bko, k0, k1);
   for (uint32_t blk = 0; blk < cnt; blk += 64) {
     const uint32_t key = blk ? k1 : k0;
     const bool v = blk + (uint32_t)lane < cnt;
@@ -2536,172 +2374,6 @@ __device__ __forceinline__ void gw_prepare(GwBuf& B, AStage& stg, const AggGArgs
       rjs[rbase + (uint32_t)lane] = (g << AGG_GSHIFT) | oi;
     }
     rbase += min(64u, cnt - blk);
-  }
-}
-
-__global__ __launch_bounds__(128) void k_agg_gwalk2(BookDev bk, AggGArgs ga, AggDev ag) {
-  __shared__ GwShared sh;
-  const int lane = lane_id();
-  const bool walker = auni((int)(threadIdx.x >> 6)) == 0;
-#if ME_WALK_PRIO
-  if (walker) __builtin_amdgcn_s_setprio(3);  // the chain before the helper waves sharing its SIMD
-#endif
-  const int L = (int)bk.L;  // <= 128
-  const uint32_t ng = ga.ng;
-  for (uint32_t s = blockIdx.x; s < bk.S; s += gridDim.x) {
-    const uint32_t gl = min((uint32_t)lane, ng - 1u);
-    const uint32_t nsv = (uint32_t)lane < ng ? ga.bcnt[gl][(size_t)s * BK_CNT_STRIDE] : 0u;
-    const uint32_t total = (uint32_t)rli64(wave_incl_scan((long long)nsv), 63);
-    const SymState st = bk.sym[s];
-    const long long base = rli64(st.base, 0);
-    const int bb0 = rli32(st.best_bid, 0), ba0 = rli32(st.best_ask, 0);
-    const uint32_t resting = rl32(st.resting, 0);
-    const uint32_t nfar0 = rl32(st.nfar[0], 0), nfar1 = rl32(st.nfar[1], 0);
-    gptr<AggSlot> slot = (gptr<AggSlot>)(ag.slot + s);
-    const uint32_t evneed = 3u * total + min((uint32_t)L, resting) + 64u;
-    if (walker) {
-      uint32_t eb = 0;
-      if (total && lane == 0) eb = atomicAdd(&ag.ctr[AC_EV], evneed + 64u);
-      eb = (rl32(eb, 0) + 63u) & ~63u;
-      const bool eok = (unsigned long long)eb + evneed <= ag.ev_cap;
-      if (lane == 0) {
-        AggSlot o{};
-        o.s = s;
-        o.base = base;
-        o.ev_base = eb;
-        o.lo = evneed;
-        o.hi = total;
-        o.free_head = st.free_head;
-        o.resting0 = resting;
-        o.bb = bb0;
-        o.ba = ba0;
-        o.active = 0;
-        o.hidx = NIL;
-        o.gs = bk.gsym ? bk.gsym[s] : s;
-        *slot = o;
-      }
-      bool go = total != 0u;
-      if (go && (!eok || !a_reserve(ag, slot, resting, total))) {  // no room: the whole group of the symbol
-        const uint32_t g0 = (uint32_t)__builtin_ctzll(__ballot(nsv != 0u));  // goes to the continuation
-        a_ghand(bk, s, g0, 0u, rl32(nsv, (int)g0), s * ga.slab, s * ga.slab + ga.slab);
-        go = false;
-      }
-      if (lane == 0) {
-        sh.go = go ? 1u : 0u;
-        sh.eb = eb;
-      }
-    }
-    __syncthreads();
-    const bool go = auniu(sh.go) != 0u;
-    const uint32_t eb = auniu(sh.eb);
-    __syncthreads();  // (the walker's next symbol overwrites go / eb)
-    if (!go) continue;
-    GR_STAMP(bk, s, 0);
-#ifdef ME_STAMPS
-    unsigned long long gw_t[4] = {0ull, 0ull, 0ull, 0ull}, gw_m = stamp_now();
-#endif
-    AggGEv* const log8 = reinterpret_cast<AggGEv*>(ag.ev + eb);
-    const gptr<uint32_t> rsq = vptr(reinterpret_cast<uint32_t*>(log8 + evneed));
-    const gptr<uint32_t> rjs = rsq + total;
-    const size_t bko = (size_t)s * BK_CAP;
-    if (walker) {
-      const uint32_t nfc = min(rl32(st.nfree, 0), 64u);
-      if (nfc) {  // k_match_reg's parked free chunks join the front of the free list (k_agg_gwalk)
-        const uint32_t fc = bk.fcache[(size_t)s * 64u + lane];
-        const uint32_t nx = (uint32_t)__shfl((int)fc, min(lane + 1, 63), 64);
-        if ((uint32_t)lane < nfc) bk.chunks[fc].hdr.next = (uint32_t)lane + 1u < nfc ? nx : st.free_head;
-        if (lane == 0) slot->free_head = fc;
-      }
-    } else {
-      uint32_t hrb = 0;
-      const unsigned long long gmin = *ga.seq0;
-      const uint32_t c0 = rl32(nsv, 0);
-      if (c0 && c0 <= (uint32_t)BK_CAP)
-        gw_prepare(sh.buf[0], sh.stg, ga, 0u, c0, bko, base, L, nfar0, nfar1, rsq, rjs, gmin, hrb);
-      __syncthreads();
-      for (uint32_t g = 0; g < ng; ++g) {
-        const uint32_t c = g + 1u < ng ? rl32(nsv, (int)(g + 1u)) : 0u;
-        if (c && c <= (uint32_t)BK_CAP)
-          gw_prepare(sh.buf[(g + 1u) & 1u], sh.stg, ga, g + 1u, c, bko, base, L, nfar0, nfar1, rsq, rjs, gmin, hrb);
-        __syncthreads();
-        if (auniu(sh.stop[g & 1u])) break;
-      }
-      continue;
-    }
-    LEvG w;
-    le_init(w, log8, 0u);
-    uint32_t rbase = 0;
-    RWalk lw;
-    const bool lok = lw_init(lw, bk, s, bb0, ba0);
-    uint32_t hidx = NIL, gstop = ng;
-    __syncthreads();  // batch 0 prepared
-    for (uint32_t g = 0; g < ng; ++g) {
-      if (lane == 0) *a_gtab(ag.gev, s, g) = eb + w.evp;
-      const uint32_t cnt = rl32(nsv, (int)g);
-      bool stop = false;
-      if (cnt > (uint32_t)BK_CAP) {  // an overfull bucket: the continuation rescans the batch
-        hidx = a_ghand(bk, s, g, 0u, cnt, 0u, 0u);
-        stop = true;
-      } else if (cnt) {
-        if (lane == 0) ga.bcnt[g][(size_t)s * BK_CNT_STRIDE] = 0u;  // ready for a later group's bucket job
-        const GwBuf& B = sh.buf[g & 1u];
-        me_order_result* res = ga.res[g];
-        GW_T(0);
-        for (uint32_t blk = 0; blk < cnt; blk += 64) {
-          const bool v = blk + (uint32_t)lane < cnt;
-          const uint32_t ocw = B.cw[blk + lane];
-          const int oq = B.oq[blk + lane];
-          const uint32_t oi = B.oi[blk + lane];
-          const unsigned long long fastm = rl64(B.fastm[blk >> 6], 0);
-          const uint32_t cntb = min(64u, cnt - blk);
-          int rr = 0;
-          bool adm = false;
-          if (lok) {
-            lw.ub += (unsigned long long)rli64(B.qsum[blk >> 6], 0);
-            adm = lw.ub < LW_CAP;
-          }
-          GW_T(1);
-          const uint32_t k = lw_block<AGG_GREC_SHIFT>(w, lw, oq, ocw, rbase, adm ? fastm : 0ull, cntb, rr);
-          rbase += cntb;
-          GW_T(2);
-#ifdef ME_STAMPS
-          gw_t[3] += k;
-#endif
-          if (v && (uint32_t)lane < k)
-            res[oi] = a_result(oq, (ocw & LW_MKT) ? 4u : 0u, ocw >> LW_RJ_SHIFT, rr);  // fills: k_agg_gres
-          if (k < cntb) {
-            hidx = a_ghand(bk, s, g, blk + k, cnt, 0u, 0u);  // scratch position: k_agg_gres
-            stop = true;
-            break;
-          }
-        }
-      }
-      if (lane == 0) sh.stop[g & 1u] = stop ? 1u : 0u;
-      __syncthreads();  // batch g + 1 prepared; the helper sees the stop
-      if (stop) {
-        gstop = g;
-        break;
-      }
-    }
-    for (uint32_t g = (gstop < ng ? gstop + 1u : ng) + (uint32_t)lane; g <= ng; g += 64)
-      *a_gtab(ag.gev, s, g) = eb + w.evp;
-    if (gstop < ng && lane == 0) *a_gtab(ag.gev, s, gstop + 1u) = eb + w.evp;
-    le_end(w);
-    if (lok) lw_end(lw, bk, s);
-    const int bb = lw.bb, ba = lw.ba;
-    if (lane == 0) {
-      slot->ev_cnt = w.evp;
-      slot->bb = bb;
-      slot->ba = ba;
-      slot->active = 1;
-      slot->hidx = hidx;
-      slot->pos = gstop;
-    }
-    GR_STAMP(bk, s, 1);
-#ifdef ME_STAMPS
-    if (lane == 0)
-      for (int q = 0; q < 4; ++q) bk.dbg[(size_t)s * 24u + q] = gw_t[q];
-#endif
   }
 }
 
@@ -2818,24 +2490,8 @@ __device__ __forceinline__ void gw_prepare_cx(GwBuf& B, const GwBuf& Bp, GwCx& X
                                               const GwRest& ri, unsigned long long gmin, uint32_t& rbase,
                                               uint32_t cut) {
   const int lane = lane_id();
-  BkRec r0{}, r1{};
-  if ((uint32_t)lane < cnt) r0 = ga.b_rec[g][bko + lane];
-  if (64u + (uint32_t)lane < cnt) r1 = ga.b_rec[g][bko + 64 + lane];
-  stg.seq[lane] = r0.seq;
-  stg.seq[64 + lane] = r1.seq;
-  stg.px[lane] = r0.px;
-  stg.px[64 + lane] = r1.px;
-  stg.qty[lane] = r0.qty;
-  stg.qty[64 + lane] = r1.qty;
-  stg.ok[lane] = r0.ok;
-  stg.ok[64 + lane] = r1.ok;
-  uint32_t k0 = (uint32_t)lane < cnt ? ((r0.ok & BK_IDX_MASK) << 7) | (uint32_t)lane : ~0u;
-  uint32_t k1 = 64u + (uint32_t)lane < cnt ? ((r1.ok & BK_IDX_MASK) << 7) | (64u + (uint32_t)lane) : ~0u;
-  if (cnt > 64u)
-    a_sort128(k0, k1);
-  else
-    k0 = a_sort64(k0, false);
-  wave_mem_order();
+  uint32_t k0, k1;
+  gw_stage(stg, ga, g, cnt, bko, k0, k1);
   const uint32_t rb0 = rbase;
   long long tgt[2] = {0ll, 0ll};
   bool isc[2] = {false, false};
@@ -3169,17 +2825,23 @@ __device__ __forceinline__ me_order_result a_result_cx(uint32_t rj, int rem) {
   return o;
 }
 
-__global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, AggDev ag) {
-  __shared__ GwShared sh;
-  __shared__ GwCx cx;
+// The grouped walk's skeleton, one body for both kernels: k_agg_gwalk2 (CX false) and k_agg_gwalk_cx (CX
+// true; X: its LDS, null for the plain walk). The per-symbol prologue, the hand-over to the helper, both
+// waves' batch loop frames, the log's tail and the slot's epilogue are the same; the cancel walk adds the
+// rest-info array of the symbol's region, the helper's target search (gw_prepare_cx for gw_prepare), the
+// per-level state and target descriptors of its chain (lw_block_cx for lw_block) and a cancel's result.
+template <bool CX>
+__device__ __forceinline__ void gw_symbols(const BookDev& bk, const AggGArgs& ga, const AggDev& ag, GwShared& sh,
+                                           GwCx* X) {
   const int lane = lane_id();
   const bool walker = auni((int)(threadIdx.x >> 6)) == 0;
 #if ME_WALK_PRIO
-  if (walker) __builtin_amdgcn_s_setprio(3);
+  if (walker) __builtin_amdgcn_s_setprio(3);  // the chain before the helper waves sharing its SIMD
 #endif
   const int L = (int)bk.L;  // <= 128
   const uint32_t ng = ga.ng;
   for (uint32_t s = blockIdx.x; s < bk.S; s += gridDim.x) {
+    // lane g < ng: the symbol's records in batch g
     const uint32_t gl = min((uint32_t)lane, ng - 1u);
     const uint32_t nsv = (uint32_t)lane < ng ? ga.bcnt[gl][(size_t)s * BK_CNT_STRIDE] : 0u;
     const uint32_t total = (uint32_t)rli64(wave_incl_scan((long long)nsv), 63);
@@ -3212,8 +2874,8 @@ __global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, A
         *slot = o;
       }
       bool go = total != 0u;
-      if (go && (!eok || !a_reserve(ag, slot, resting, total))) {
-        const uint32_t g0 = (uint32_t)__builtin_ctzll(__ballot(nsv != 0u));
+      if (go && (!eok || !a_reserve(ag, slot, resting, total))) {  // no room: the whole group of the symbol
+        const uint32_t g0 = (uint32_t)__builtin_ctzll(__ballot(nsv != 0u));  // goes to the continuation
         a_ghand(bk, s, g0, 0u, rl32(nsv, (int)g0), s * ga.slab, s * ga.slab + ga.slab);
         go = false;
       }
@@ -3225,17 +2887,21 @@ __global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, A
     __syncthreads();
     const bool go = auniu(sh.go) != 0u;
     const uint32_t eb = auniu(sh.eb);
-    __syncthreads();
+    __syncthreads();  // (the walker's next symbol overwrites go / eb)
     if (!go) continue;
     AggGEv* const log8 = reinterpret_cast<AggGEv*>(ag.ev + eb);
-    // the region: evneed 8-B events, then the records' seqs and positions [total] each, then (16-B aligned)
-    // their rest info [total] (8 evneed + 24 total + 16 <= 16 evneed bytes: evneed >= 3 total + 64)
+    // the region: evneed 8-B events, then the records' seqs (offsets from the group's first) and grouped
+    // positions in walk order [total] each, then (the cancel walk, 16-B aligned) their rest info [total]
+    // (8 evneed + 24 total + 16 <= 16 evneed bytes, the region reserved in 16-B units: evneed >= 3 total + 64)
     const gptr<uint32_t> rsq = vptr(reinterpret_cast<uint32_t*>(log8 + evneed));
     const gptr<uint32_t> rjs = rsq + total;
-    GwRest ri;
-    ri.r = vptr(reinterpret_cast<GwRi*>((reinterpret_cast<uintptr_t>(log8 + evneed) + 8ull * total + 15ull) & ~15ull));
+    [[maybe_unused]] GwRest ri{};
+    if constexpr (CX)
+      ri.r = vptr(reinterpret_cast<GwRi*>((reinterpret_cast<uintptr_t>(log8 + evneed) + 8ull * total + 15ull) & ~15ull));
     const size_t bko = (size_t)s * BK_CAP;
     if (walker) {
+      // free chunks k_match_reg parked in fcache[s][0, nfree) join the front of the free list (one header
+      // store per lane), so k_agg_gres reuses them before it takes fresh chunks, and writes nfree = 0
       const uint32_t nfc = min(rl32(st.nfree, 0), 64u);
       if (nfc) {
         const uint32_t fc = bk.fcache[(size_t)s * 64u + lane];
@@ -3243,37 +2909,40 @@ __global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, A
         if ((uint32_t)lane < nfc) bk.chunks[fc].hdr.next = (uint32_t)lane + 1u < nfc ? nx : st.free_head;
         if (lane == 0) slot->free_head = fc;
       }
-    } else {
+    } else {  // the helper: batch 0, then batch g + 1 while the walker walks batch g
       uint32_t hrb = 0;
       const unsigned long long gmin = *ga.seq0;
-      const uint32_t c0 = rl32(nsv, 0);
-      for (uint32_t j = (uint32_t)lane; j < ME_GMAX * BK_CAP / 32; j += 64) cx.tbit[j] = 0u;
-      if (lane == 0) cx.npre = 0u;
-      wave_mem_order();
+      if constexpr (CX) {
+        for (uint32_t j = (uint32_t)lane; j < ME_GMAX * BK_CAP / 32; j += 64) X->tbit[j] = 0u;
+        if (lane == 0) X->npre = 0u;
+        wave_mem_order();
+      }
 #ifdef ME_STAMPS
-      unsigned long long h_t = 0, h_m = stamp_now();
+      unsigned long long h_t = 0;
 #endif
-      if (c0 && c0 <= (uint32_t)BK_CAP)
-        gw_prepare_cx(sh.buf[0], sh.buf[1], cx, 0u, sh.stg, ga, bk, s, 0u, c0, bko, base, L, nfar0, nfar1, rsq, rjs,
-                      ri, gmin, hrb, 0u);
+      // batch g into buffer g & 1 (none past the group's end, for an empty or an overfull bucket); cut: the
+      // first record of the batch the walker walks meanwhile
+      auto prepare = [&](uint32_t g, uint32_t c, uint32_t cut) {
+        if (!c || c > (uint32_t)BK_CAP) return;
 #ifdef ME_STAMPS
-      h_t += stamp_now() - h_m;
+        const unsigned long long h_m = stamp_now();
 #endif
+        if constexpr (CX)
+          gw_prepare_cx(sh.buf[g & 1u], sh.buf[~g & 1u], *X, g & 1u, sh.stg, ga, bk, s, g, c, bko, base, L, nfar0,
+                        nfar1, rsq, rjs, ri, gmin, hrb, cut);
+        else
+          gw_prepare(sh.buf[g & 1u], sh.stg, ga, g, c, bko, base, L, nfar0, nfar1, rsq, rjs, gmin, hrb);
+#ifdef ME_STAMPS
+        h_t += stamp_now() - h_m;
+#endif
+      };
+      prepare(0u, rl32(nsv, 0), 0u);
       __syncthreads();
       for (uint32_t g = 0; g < ng; ++g) {
         const uint32_t c = g + 1u < ng ? rl32(nsv, (int)(g + 1u)) : 0u;
         // batch g's first record: when batch g + 1 is walked the ring holds batches g and g + 1
         const uint32_t cg = rl32(nsv, (int)g);
-        const uint32_t cut = hrb - (cg <= (uint32_t)BK_CAP ? cg : 0u);
-#ifdef ME_STAMPS
-        h_m = stamp_now();
-#endif
-        if (c && c <= (uint32_t)BK_CAP)
-          gw_prepare_cx(sh.buf[(g + 1u) & 1u], sh.buf[g & 1u], cx, (g + 1u) & 1u, sh.stg, ga, bk, s, g + 1u, c, bko,
-                        base, L, nfar0, nfar1, rsq, rjs, ri, gmin, hrb, cut);
-#ifdef ME_STAMPS
-        h_t += stamp_now() - h_m;
-#endif
+        prepare(g + 1u, c, hrb - (cg <= (uint32_t)BK_CAP ? cg : 0u));
         __syncthreads();
         if (auniu(sh.stop[g & 1u])) break;
       }
@@ -3287,17 +2956,19 @@ __global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, A
     unsigned long long gw_t[4] = {0ull, 0ull, 0ull, 0ull}, gw_m = stamp_now();
     unsigned long long gw_rt[10] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
 #else
-    unsigned long long* const gw_rt = nullptr;
+    [[maybe_unused]] unsigned long long* const gw_rt = nullptr;
 #endif
     LEvG w;
-    le_init(w, log8, 0u);
+    le_init(w, log8, 0u);  // (w.evp: relative to the region)
     uint32_t rbase = 0;
     RWalk lw;
-    const bool lok = lw_init(lw, bk, s, bb0, ba0);
-    GwLvR lv;  // the levels' initial totals (the ladder's, exact at its start), no rests or cancels yet
-    lv.t0[0] = lw.t0;
-    lv.t0[1] = lw.t1;
-    lv.rl[0] = lv.rl[1] = lv.n[0] = lv.n[1] = lv.xl[0] = lv.xl[1] = 0u;
+    const bool lok = lw_init(lw, bk, s, bb0, ba0);  // else: the continuation from the first record
+    [[maybe_unused]] GwLvR lv;  // the levels' initial totals (the ladder's, exact at its start), no rests or cancels yet
+    if constexpr (CX) {
+      lv.t0[0] = lw.t0;
+      lv.t0[1] = lw.t1;
+      lv.rl[0] = lv.rl[1] = lv.n[0] = lv.n[1] = lv.xl[0] = lv.xl[1] = 0u;
+    }
     uint32_t hidx = NIL, gstop = ng;
     GW_T(1);
     __syncthreads();  // batch 0 prepared
@@ -3306,11 +2977,11 @@ __global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, A
       if (lane == 0) *a_gtab(ag.gev, s, g) = eb + w.evp;
       const uint32_t cnt = rl32(nsv, (int)g);
       bool stop = false;
-      if (cnt > (uint32_t)BK_CAP) {
+      if (cnt > (uint32_t)BK_CAP) {  // an overfull bucket: the continuation rescans the batch
         hidx = a_ghand(bk, s, g, 0u, cnt, 0u, 0u);
         stop = true;
       } else if (cnt) {
-        if (lane == 0) ga.bcnt[g][(size_t)s * BK_CNT_STRIDE] = 0u;
+        if (lane == 0) ga.bcnt[g][(size_t)s * BK_CNT_STRIDE] = 0u;  // ready for a later group's bucket job
         const GwBuf& B = sh.buf[g & 1u];
         me_order_result* res = ga.res[g];
         for (uint32_t blk = 0; blk < cnt; blk += 64) {
@@ -3318,9 +2989,12 @@ __global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, A
           const uint32_t ocw = B.cw[blk + lane];
           const int oq = B.oq[blk + lane];
           const uint32_t oi = B.oi[blk + lane];
-          const uint32_t b2 = g & 1u;
-          const uint32_t c0v = cx.ct0[b2][blk + lane], c1v = cx.ct1[b2][blk + lane];
-          const uint32_t c2v = cx.ct2[b2][blk + lane], c3v = cx.ct3[b2][blk + lane];
+          [[maybe_unused]] uint32_t c0v = 0, c1v = 0, c2v = 0, c3v = 0;  // a cancel's target descriptor
+          if constexpr (CX) {
+            const uint32_t b2 = g & 1u;
+            c0v = X->ct0[b2][blk + lane], c1v = X->ct1[b2][blk + lane];
+            c2v = X->ct2[b2][blk + lane], c3v = X->ct3[b2][blk + lane];
+          }
           const unsigned long long fastm = rl64(B.fastm[blk >> 6], 0);
           const uint32_t cntb = min(64u, cnt - blk);
           int rr = 0;
@@ -3330,19 +3004,22 @@ __global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, A
             adm = lw.ub < LW_CAP;
           }
           GW_T(1);
-          const uint32_t k = lw_block_cx(w, lw, lv, cx, ri, oq, ocw, c0v, c1v, c2v, c3v, rbase, adm ? fastm : 0ull, cntb, rr,
-                                         gw_rt);
+          uint32_t k;
+          if constexpr (CX)
+            k = lw_block_cx(w, lw, lv, *X, ri, oq, ocw, c0v, c1v, c2v, c3v, rbase, adm ? fastm : 0ull, cntb, rr, gw_rt);
+          else
+            k = lw_block<AGG_GREC_SHIFT>(w, lw, oq, ocw, rbase, adm ? fastm : 0ull, cntb, rr);
+          rbase += cntb;
           GW_T(2);
 #ifdef ME_STAMPS
           gw_t[3] += k;
 #endif
-          rbase += cntb;
-          if (v && (uint32_t)lane < k) {
-            const uint32_t rj = (ocw >> LW_RJ_SHIFT) & LW_RJ_MASK;
-            res[oi] = (ocw & LW_CX) ? a_result_cx(rj, rr) : a_result(oq, (ocw & LW_MKT) ? 4u : 0u, rj, rr);
+          if (v && (uint32_t)lane < k) {  // fills: k_agg_gres
+            const uint32_t rj = CX ? (ocw >> LW_RJ_SHIFT) & LW_RJ_MASK : ocw >> LW_RJ_SHIFT;
+            res[oi] = CX && (ocw & LW_CX) ? a_result_cx(rj, rr) : a_result(oq, (ocw & LW_MKT) ? 4u : 0u, rj, rr);
           }
           if (k < cntb) {
-            hidx = a_ghand(bk, s, g, blk + k, cnt, 0u, 0u);
+            hidx = a_ghand(bk, s, g, blk + k, cnt, 0u, 0u);  // scratch position: k_agg_gres
             stop = true;
             break;
           }
@@ -3350,18 +3027,19 @@ __global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, A
       }
       if (lane == 0) sh.stop[g & 1u] = stop ? 1u : 0u;
       GW_T(1);
-      __syncthreads();
+      __syncthreads();  // batch g + 1 prepared; the helper sees the stop
       GW_T(0);
       if (stop) {
         gstop = g;
         break;
       }
     }
+    // the log's end for every batch from the stop on
     for (uint32_t g = (gstop < ng ? gstop + 1u : ng) + (uint32_t)lane; g <= ng; g += 64)
       *a_gtab(ag.gev, s, g) = eb + w.evp;
     if (gstop < ng && lane == 0) *a_gtab(ag.gev, s, gstop + 1u) = eb + w.evp;
     le_end(w);
-    if (lok) lw_end(lw, bk, s);
+    if (lok) lw_end(lw, bk, s);  // (else nothing was walked)
     const int bb = lw.bb, ba = lw.ba;
     if (lane == 0) {
       slot->ev_cnt = w.evp;
@@ -3369,16 +3047,28 @@ __global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, A
       slot->ba = ba;
       slot->active = 1;
       slot->hidx = hidx;
-      slot->pos = gstop;
+      slot->pos = gstop;  // the batch the continuation starts in (ng: none)
     }
     GR_STAMP(bk, s, 1);
 #ifdef ME_STAMPS
-    if (lane == 0)
+    if (lane == 0) {
       for (int q = 0; q < 4; ++q) bk.dbg[(size_t)s * 24u + q] = gw_t[q];
-    if (lane == 0)
-      for (int q = 0; q < 10; ++q) bk.dbg[(size_t)s * 24u + 6u + q] = gw_rt[q];
+      if constexpr (CX)
+        for (int q = 0; q < 10; ++q) bk.dbg[(size_t)s * 24u + 6u + q] = gw_rt[q];
+    }
 #endif
   }
+}
+
+__global__ __launch_bounds__(128) void k_agg_gwalk2(BookDev bk, AggGArgs ga, AggDev ag) {
+  __shared__ GwShared sh;
+  gw_symbols<false>(bk, ga, ag, sh, nullptr);
+}
+
+__global__ __launch_bounds__(128) void k_agg_gwalk_cx(BookDev bk, AggGArgs ga, AggDev ag) {
+  __shared__ GwShared sh;
+  __shared__ GwCx cx;
+  gw_symbols<true>(bk, ga, ag, sh, &cx);
 }
 
 // ------------------------------------------------------------------ grouped launches: one workgroup per symbol
@@ -4376,22 +4066,12 @@ hipError_t launch_agg_group(hipStream_t st, const BookDev& bk, const BatchDev* b
   ga.ng = ng;
   // one workgroup per symbol up to the grid cap, then symbols striding over the grid (blockIdx = symbol mod
   // grid: a symbol's walk and resolve run on the same XCD either way)
-  static const uint32_t gcap = [] {
-    const char* e = getenv("ME_AGG_GRID");
-    return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 65536u;
-  }();
-  const uint32_t grid = bk.S < gcap ? bk.S : gcap;
-  static const bool helper = [] {
-    const char* e = getenv("ME_GW_HELPER");
-    return !e || atoi(e) != 0;
-  }();
+  const uint32_t grid = bk.S < ag.gw_grid ? bk.S : ag.gw_grid;
   const bool cx = ag.gw_cx != 0u;  // groups with cancels: the walk that covers them, and its resolve
   if (cx)
     hipLaunchKernelGGL(k_agg_gwalk_cx, dim3(grid), dim3(128), 0, st, bk, ga, ag);
-  else if (helper)
-    hipLaunchKernelGGL(k_agg_gwalk2, dim3(grid), dim3(128), 0, st, bk, ga, ag);
   else
-    hipLaunchKernelGGL(k_agg_gwalk, dim3(grid), dim3(64), 0, st, bk, ga, ag);
+    hipLaunchKernelGGL(k_agg_gwalk2, dim3(grid), dim3(128), 0, st, bk, ga, ag);
   // the per-event LDS array (fill counts, 4 B per event) sized for 1.75 events per record of the group's
   // mean symbol plus slack; a longer log keeps it in HBM. Capped so the workgroup's LDS stays within 64 KB.
   uint64_t recs = 0;
@@ -4399,20 +4079,13 @@ hipError_t launch_agg_group(hipStream_t st, const BookDev& bk, const BatchDev* b
   uint64_t ne = (recs * 7u / 4u) / (bk.S ? bk.S : 1u) + 256u;  // (config 2: 1.4 events per record)
   ne = (ne + 63u) & ~63ull;
   // resolve workgroups of 8 waves, or of 4 for groups with few records per symbol (config 3's ~210: twice
-  // the workgroups in flight); ME_GRES_WAVES=4/8 forces either
-  static const int gw_env = [] {
-    const char* e = getenv("ME_GRES_WAVES");
-    return e ? atoi(e) : 0;
-  }();
+  // the workgroups in flight); ag.gres_waves (ME_GRES_WAVES=4/8) forces either
   const uint64_t per_sym = recs / (bk.S ? bk.S : 1u);
-  int nw = gw_env == 2 || gw_env == 4 || gw_env == 8 ? gw_env : per_sym < GR_FOUR_BELOW ? 4 : 8;
-  if (cx && nw == 2) nw = 4;  // (the 2-wave form is a measurement switch; the resolve with cancels has 4 or 8)
-  const size_t shb = nw == 2 ? sizeof(GrShared<2>) : nw == 4 ? sizeof(GrShared<4>) : sizeof(GrShared<GR_WAVES>);
+  const uint32_t nw = ag.gres_waves ? ag.gres_waves : per_sym < GR_FOUR_BELOW ? 4u : 8u;
+  const size_t shb = nw == 4 ? sizeof(GrShared<4>) : sizeof(GrShared<GR_WAVES>);
   const uint64_t ne_cap = ((64u << 10) - shb) / 4u & ~63ull;
   if (ne > ne_cap) ne = ne_cap;
-  if (nw == 2) {
-    hipLaunchKernelGGL((k_agg_gres<2, false>), dim3(grid), dim3(128), (size_t)ne * 4u, st, bk, ga, src, ag, (uint32_t)ne);
-  } else if (nw == 4) {
+  if (nw == 4) {
     if (cx)
       hipLaunchKernelGGL((k_agg_gres<4, true>), dim3(grid), dim3(256), (size_t)ne * 4u, st, bk, ga, src, ag, (uint32_t)ne);
     else

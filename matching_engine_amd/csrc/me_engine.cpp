@@ -569,7 +569,7 @@ extern "C" me_engine* me_create(const me_config* cfg) {
     const char* v = getenv("ME_HOT_MIN");
     const char* va = getenv("ME_HOT_AGG");
     e->hot.agg = L > 128 && L <= AGG_MAX_L && !(va && atoi(va) == 0);
-    // L <= 128: every symbol of a launch group through the aggregate path (k_agg_gwalk) instead of
+    // L <= 128: every symbol of a launch group through the aggregate path (k_agg_gwalk2) instead of
     // k_match_reg's serial loop — ME_REG_AGG=1 (measured per workload)
     // (unset: on when a batch holds >= 8 records per symbol and a group >= 256 — config 2's shape, 64 and
     // 2,048; config 3's ~10.5 and ~336 runs 1,296M vs 1,124M on k_match_reg at the driver's shape, 1,590M
@@ -588,6 +588,13 @@ extern "C" me_engine* me_create(const me_config* cfg) {
     const char* vc = getenv("ME_GW_CANCEL");
     e->hot.ag.gw_cx = e->hot.agg_reg && vc && atoi(vc) != 0 ? 1u : 0u;
     e->gw_cx_auto = e->hot.agg_reg && !vc;
+    // a grouped launch's grid: one workgroup per symbol up to ME_AGG_GRID (65,536), and its resolve's
+    // workgroups of ME_GRES_WAVES=4/8 waves (anything else: by the group's records per symbol)
+    const char* vg = getenv("ME_AGG_GRID");
+    e->hot.ag.gw_grid = vg && atoi(vg) > 0 ? (uint32_t)atoi(vg) : 65536u;
+    const char* vw = getenv("ME_GRES_WAVES");
+    const int gw = vw ? atoi(vw) : 0;
+    e->hot.ag.gres_waves = gw == 4 || gw == 8 ? (uint32_t)gw : 0u;
     if (const char* ve = getenv("ME_EARLY_FILL")) e->early_fill = (uint32_t)atoi(ve);  // (0: off)
     // the grouped aggregate path's side jobs on a stream of their own (ME_SIDE_STREAM=0: in line)
     const char* vs = getenv("ME_SIDE_STREAM");

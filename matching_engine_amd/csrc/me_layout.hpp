@@ -196,7 +196,7 @@ struct AggEv {       // one event of the log, in record order
   uint32_t pad;
 };
 constexpr uint32_t AGG_TAKE = 1u << 31;
-// Grouped launches (k_agg_gwalk -> k_agg_gres) log 8-B events: the level (L <= 128) and the record's
+// Grouped launches (k_agg_gwalk2 -> k_agg_gres) log 8-B events: the level (L <= 128) and the record's
 // number in the symbol's walk order (< ME_GMAX x BK_CAP) in one word. The records' seqs (offsets from the
 // group's first seq) and grouped positions sit beside the log in two arrays the walk writes 64 at a time,
 // so the resolve reads a seq from the symbol's own small array instead of gathering it from the batches.
@@ -267,10 +267,13 @@ struct AggDev {
   uint32_t lw_occ;             // k_agg_walk: ladders deeper than this search the next level through an LDS
                                // occupancy bitmap (0: the 64-level total scan at every depth)
   uint32_t gw_cx;              // grouped launches: the walk that covers cancels (k_agg_gwalk_cx) and its resolve
-  // grouped launches (register-window path, k_agg_gwalk): per symbol and batch of the group, [S][ME_GMAX + 1]
+  // grouped launches (register-window path, k_agg_gwalk2): per symbol and batch of the group, [S][ME_GMAX + 1]
   uint32_t* gev;               // the symbol's first log index of batch g (g = ng: the log's end)
   uint32_t* gex;               // the fill offset (k_agg_fin's scan) at gev
   uint32_t* gbase;             // scratch position of the symbol's first fill of batch g
+  // grouped launches, the launch's shape (launch_agg_group reads them, the kernels do not)
+  uint32_t gw_grid;            // workgroups at most (more symbols stride over the grid)
+  uint32_t gres_waves;         // k_agg_gres's waves per workgroup, 4 or 8 (0: by the group's records per symbol)
 };
 // Where the record of a log entry lives (k_agg_levels / k_agg_place read the seq of a rest there).
 struct AggSrc {
@@ -286,7 +289,7 @@ struct HotLaunch {
   hipStream_t st = nullptr;
   hipEvent_t fork = nullptr, join = nullptr;
   bool agg = false;  // the aggregate path (me_agg.hip) instead of k_match_hot
-  bool agg_reg = false;  // L <= 128: grouped launches through the aggregate path (me_agg.hip k_agg_gwalk)
+  bool agg_reg = false;  // L <= 128: grouped launches through the aggregate path (me_agg.hip k_agg_gwalk2)
   AggDev ag{};
   // grouped aggregate launches: the side jobs (bucketing of the next group, tapes of the one before) on
   // their own stream, forked before and joined after the group's walk / per-level launch / continuation

@@ -78,7 +78,6 @@ struct RegLds {
   long long tdummy[64];  // tot_add: the slots of lanes 1..63
   uint32_t cnext[RC];  // chunks[head].hdr.next of the cached head (kept in step with HBM)
   uint32_t free_head;  // overflow free list in HBM (hdr.next links), NIL if empty
-  uint32_t bump_cur, bump_end;  // chunk ids reserved from the global bump allocator
   uint32_t resting0;  // the symbol's resting orders when the wave started (ST_RESTING delta)
   uint32_t scan_cur, scan_cnt, scan_pos;  // rescan of an overfull bucket: next batch index, list fill, list read
   uint32_t mode;  // record source: 0 bucket, 1 rescan, 2 sort path (perm run [run_lo, run_lo + run_n))
@@ -1571,8 +1570,6 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
     if (lane == 0) {
       c.M->free_head = st.free_head;
       c.M->resting0 = st.resting;
-      c.M->bump_cur = 0;
-      c.M->bump_end = 0;
       c.M->nfar[0] = st.nfar[0];
       c.M->nfar[1] = st.nfar[1];
       c.M->horizon = sqs.horizon;
@@ -1887,11 +1884,6 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
     }
   }
   // ---- write the symbol back
-  {  // unused reserved chunks
-    uint32_t cur = ldsu(c.M->bump_cur);
-    const uint32_t end = ldsu(c.M->bump_end);
-    while (cur < end) reg_free(c, cur++);
-  }
   for (int row = 0; row < 2; ++row) {  // every valid cached head back to HBM (entry l holds the head of l)
     unsigned long long d = __ballot(((row ? c.hd.r1 : c.hd.r0) & HC) == 0u);  // cached heads
     while (d) {

@@ -1,5 +1,5 @@
 """Grouped launches through the aggregate path (ME_REG_AGG=1, windows of at most 128 levels): every
-symbol of a launch group walked on level totals by k_agg_gwalk (me_agg.hip), FIFOs resolved per level,
+symbol of a launch group walked on level totals by k_agg_gwalk2 (me_agg.hip), FIFOs resolved per level,
 each batch's fills placed in its own scratch — every batch's outputs bit-exact against the oracle, through
 the pipelined host path (per-batch results and tapes) and back-to-back device batches. Cancels, prices
 outside the window and overfull buckets hand a symbol's rest of the group to k_match_reg's continuation
@@ -205,12 +205,51 @@ def _peak_resting(orc, sc, batches):
     return peak
 
 
+@pytest.mark.parametrize("cx", [0, 1], ids=["plain", "cx"])
+def test_grouped_walk_symbols_stride_the_grid(me, orc, monkeypatch, cx):
+    """More symbols than workgroups (ME_AGG_GRID=5, 24 symbols): the walk's and the resolve's workgroup b takes
+    symbols b, b + 5, ... one after the other (5, 5, 5, 5 and 4 of them), the walker and its helper wave
+    meeting at the barriers of every one. Symbols 7 and 13 never have a record and symbol 22 (workgroup 2's
+    last) has none in the second group, so a workgroup skips a symbol between two it walks; symbol 11 gets one
+    LIMIT 10,000 ticks above its window in batch 5, so workgroup 1 hands a symbol off mid-group and goes on to
+    symbol 16. Config 2's stream on the plain walk, 30 % cancels and 15 % MARKETs on the walk with cancels
+    (a cancel whose target was dropped is UNKNOWN_ORDER for the engine and the oracle alike); 12 batches of
+    1,024 records in groups of 4, every batch against the oracle."""
+    monkeypatch.setenv("ME_AGG_GRID", "5")
+    monkeypatch.setenv("ME_GW_CANCEL", str(cx))
+    sc = (me.preset(5, num_symbols=24, levels=128, batch=1024, cancel_pct=30, market_pct=15) if cx
+          else me.preset(2, num_symbols=24, batch=1024))
+    st = me.Stream(sc)
+    base = st.base_prices()
+    batches = []
+    for k in range(12):
+        b = st.next(sc.batch)
+        drop = (b.symbol == 7) | (b.symbol == 13) | ((b.symbol == 22) & (4 <= k < 8))
+        batches.append(b.take(~drop))
+    # the far LIMIT: in place of a LIMIT of symbol 11 that no later cancel names
+    targets = set(np.concatenate([b.price_q4[(b.kind & 8) != 0] for b in batches]).tolist())
+    b = batches[5]
+    i = next(i for i in np.flatnonzero((b.symbol == 11) & ((b.kind & 0xC) == 0)) if int(b.seq[i]) not in targets)
+    b.kind[i] = me.kind(me.SIDE_SELL, me.TYPE_LIMIT, me.OP_NEW)
+    b.price_q4[i] = base[11] + sc.levels + 10_000
+    ob = orc.OracleBook(sc.num_symbols)
+    with _engine(me, sc, base, batches, batches_per_launch=4) as eng:
+        p = eng.paths()
+        assert p["grouped_agg"] and p["grouped_cancels"] == bool(cx), p
+        assert _check(eng, ob, batches, _pipelined(eng, batches, 9), f"grid stride cx={cx}") > 0
+        handoffs = eng.stats()["handoffs"]
+        print(f"grid stride cx={cx}: handoffs {handoffs}")
+        assert handoffs > 0
+        if cx:
+            assert handoffs * 16 <= 3 * sc.num_symbols, eng.stats()  # (3 launches; as tests/test_agg_cancels.py)
+
+
 @pytest.mark.parametrize("group", [1, 8])
 def test_agg_groups_cancels_tight_chunk_pool(me, orc, group):
     """One symbol, 40 % cancels and sweeping MARKETs, ME_REG_AGG=1: adds go through the walk, cancels
     hand the symbol to k_match_reg's continuation, which parks freed chunks in fcache. The pool holds
     only the stream's peak resting orders (+ the 2S slack and a few): every parked chunk must be reused
-    by the walk (k_agg_gwalk links them into the free list), or the pool runs dry."""
+    by the walk (k_agg_gwalk2 links them into the free list), or the pool runs dry."""
     sc = me.preset(5, num_symbols=1, levels=128, batch=512, cancel_pct=40, market_pct=15, market_qty_mult=3,
                    spread_ticks=8)
     st = me.Stream(sc)

@@ -67,7 +67,7 @@ def test_fuzz_case(me, seed):
 
 @pytest.mark.parametrize("seed", range(_SEEDS or 10))
 def test_fuzz_agg_case(me, seed, monkeypatch):
-    """ME_REG_AGG=1: every launch group through k_agg_gwalk (cancels, far prices and overfull buckets hand
+    """ME_REG_AGG=1: every launch group through k_agg_gwalk2 (cancels, far prices and overfull buckets hand
     symbols to k_match_reg's continuation mid-group), chunk pool max_resting + 2S."""
     monkeypatch.setenv("ME_REG_AGG", "1")
     _run_case(me, seed, True)

@@ -429,7 +429,7 @@ def test_cancelled_chunks_are_unlinked(me, orc, monkeypatch, reg_agg):
     """A level that never empties, with chunk after chunk filled and then cancelled: dead chunks
     (head, middle, tail) must be unlinked and reused, so a 4-chunk pool suffices for 30 rounds.
     ME_REG_AGG=1: the adds go through the grouped aggregate path and the cancels through k_match_reg's
-    continuation, which parks freed chunks in fcache — the walk must reuse them (k_agg_gwalk)."""
+    continuation, which parks freed chunks in fcache — the walk must reuse them (k_agg_gwalk2)."""
     monkeypatch.setenv("ME_REG_AGG", "1" if reg_agg == "cx" else reg_agg)
     monkeypatch.setenv("ME_GW_CANCEL", "1" if reg_agg == "cx" else "0")  # cx: the cancels inside the grouped walk
     B, S, L, M = me.SIDE_BUY, me.SIDE_SELL, me.TYPE_LIMIT, me.TYPE_MARKET

@@ -1,4 +1,4 @@
-"""Diagnostic: per-symbol timeline of a grouped aggregate launch (k_agg_gwalk, then k_agg_gres's phases) from
+"""Diagnostic: per-symbol timeline of a grouped aggregate launch (k_agg_gwalk2, then k_agg_gres's phases) from
 the -DME_STAMPS build's absolute s_memtime stamps (never the product).
 
     ME_ENGINE_LIB=matching_engine_amd/build/libme_engine_stamps.so python tools/gres_probe.py [--batches 20]
