@@ -23,6 +23,9 @@
  *   QUOTES   the top-of-book change feed (me_quotes_*, me_engine.h): every rank drains its shard's events
  *            and sends them to rank 0, which concatenates them in rank order (QUOTES_ENABLE turns every
  *            shard's feed on or off).
+ *            (The depth feed, me_depth_* in me_engine.h, has no collective yet: rank 0 fronting the shards'
+ *            depth feeds, and a me_cluster_matcher hook for me_service_depth_subscribe, is a later change; a
+ *            service over me_cluster_matcher answers ME_E_INVALID to me_service_depth_subscribe.)
  *   STOP     the serve loops return.
  * The service keeps two slices in flight through the matcher's submit / collect (SUBMIT of slice k+1
  * runs before COLLECT of slice k), so the shards match k+1 while rank 0 merges and persists k.

@@ -347,6 +347,59 @@ int me_quotes_read(me_engine* e, me_quote* out, size_t cap, size_t* n, size_t* l
  * finished (exact after me_sync). Any pointer may be NULL. ME_E_INVALID while the feed is off. */
 int me_quotes_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred);
 
+/* ---- depth feed: top-N price-level changes (market by price) ----------------------------------------
+ * The VIEW of (symbol, side) at depth D is that side's D best occupied price levels, best first, each as
+ * (price_q4, total_qty): window levels first, then far levels in price order (the order me_book_snapshot
+ * produces; DESIGN.md §3 Invariant I). D is fixed when the feed is enabled, 1 <= D <= ME_DEPTH_MAX. A
+ * side with fewer than D levels has a shorter view. total_qty is int64, as level totals are; price 0 and
+ * negative prices are prices, and a real level always has total_qty > 0.
+ *
+ * THE FEED DESCRIBES THE VIEW, NOT THE BOOK. It is conflated per launch group exactly like the quote feed
+ * above: after every match launch, at enable time and as a catch-up, a device job compares every side's
+ * view with the view last published for it. For a side that differs it logs
+ *   SET    (qty = the new total) for every price of the new view that the published view lacks or holds
+ *          with another total, and
+ *   DELETE (qty = 0) for every price of the published view that the new view lacks.
+ * A level that better levels pushed out of the top D is deleted although it still rests; when it comes
+ * back into the top D it is SET again. Events of one job ascend by local symbol id, bids before asks;
+ * inside a side they run in priority order with SETs and DELETEs merged (descending price for bids,
+ * ascending for asks). Jobs appear in launch order.
+ *
+ * Carried over from the quote feed unchanged: the published state starts empty and enabling runs one job
+ * at that point of the stream; `batches` has me_quote.batches' meaning; events are readable after
+ * me_collect(t) (those stamped <= t's ordinal) and after me_sync (all); a job whose events do not fit
+ * the free part of the log writes nothing, leaves the published views untouched and counts as deferred;
+ * a read that leaves the log empty while a deferral is outstanding runs a catch-up job. After me_sync and
+ * reads until *left == 0, applying every event ever read to a {price: qty} map per (symbol, side) gives
+ * exactly the top D levels of every book. The two feeds are independent: either, both or neither may be
+ * on; with both on the quote job runs first, and its events are what they are without the depth feed. */
+#define ME_DEPTH_MAX 32
+typedef struct me_depth_event { /* 32 B */
+  int64_t price_q4;
+  int64_t qty;      /* 0 = the level left the view */
+  uint64_t batches;
+  uint32_t symbol;  /* me_fill.symbol id space */
+  uint8_t side;     /* ME_SIDE_BUY / ME_SIDE_SELL */
+  uint8_t pad[3];   /* zero */
+} me_depth_event;
+/* depth == 0 or cap_events == 0 turns the feed off. depth > ME_DEPTH_MAX is ME_E_INVALID. The log's
+ * capacity is raised to at least 4 * depth * num_symbols events, the most one job can emit (2 * depth per
+ * side), so that one job always fits an empty log; a resulting capacity above 2^26 events (pinned host
+ * memory, 32 B each) is refused with ME_E_INVALID. Enabling waits for the work in flight and for its own
+ * first job and launches no partial group; enabling an enabled feed starts it afresh. A failing call
+ * leaves the feed off. */
+int me_depth_enable(me_engine* e, uint32_t depth, uint64_t cap_events);
+/* me_quotes_read's contract, for me_depth_event: at most `cap` events in order (out may be NULL when cap
+ * is 0); *n = events copied, *left = events logged and still unread; launches no partial group and waits
+ * for no job in flight, except that a read that leaves the log empty while a deferral is outstanding
+ * waits for the work in flight and, if that still holds, runs one catch-up job whose events follow in the
+ * same call as far as `cap` allows. *n and *left are written on every return. ME_E_INVALID while the feed
+ * is off. */
+int me_depth_read(me_engine* e, me_depth_event* out, size_t cap, size_t* n, size_t* left);
+/* Jobs run, events logged and jobs deferred since the feed was enabled (exact after me_sync). Any pointer
+ * may be NULL. ME_E_INVALID while the feed is off. */
+int me_depth_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred);
+
 /* Kernel timing. period >= 1: every period-th match-kernel launch records its own start and end
  * (hipExtLaunchKernelGGL events: no marker packets, though each timed launch still costs the
  * stream a few microseconds, hence the sampling); period <= 0: off. Resets the counters below. */

@@ -276,6 +276,33 @@ int me_service_market_subscribe(me_service* s, int on);
  * symbol's quote under the other's name. *n = updates written; ME_E_INVALID when not subscribed. */
 int me_service_market_stream(me_service* s, const char* symbol, me_market_update* out, size_t cap, size_t* n);
 
+/* The depth stream: the top-D book of every symbol whose top D levels changed in a matched slice, from the
+ * engine's depth feed (me_depth_*, me_engine.h). The engine sends deltas, the service materialises views: it
+ * applies the events to a view it keeps per symbol, so its queue is bounded by the number of symbols. */
+typedef struct me_depth_level {
+  int64_t price;
+  int32_t size; /* saturated to int32 */
+  int32_t pad;
+} me_depth_level;
+typedef struct me_depth_book {
+  char symbol[32];
+  int32_t scale; /* 4 */
+  uint32_t n_bids, n_asks;
+  uint32_t pad;
+  me_depth_level bids[ME_DEPTH_MAX], asks[ME_DEPTH_MAX]; /* best first */
+} me_depth_book;
+/* depth in 1..ME_DEPTH_MAX: me_depth_enable on the service's own engine (which must have been fresh when the
+ * service was created, as for me_service_market_subscribe) and queue the books as they stand; it waits for a
+ * running flush. A service backed by a me_matcher has no depth feed: ME_E_INVALID. depth == 0: the stream
+ * stops, the views and the queue are dropped. Independent of me_service_market_subscribe. */
+int me_service_depth_subscribe(me_service* s, uint32_t depth);
+/* Hand out the whole current top-D book of up to cap changed symbols, in first-change order (symbol NULL or
+ * "": every symbol; else only that symbol's book, the others stay queued). A symbol has at most one pending
+ * book: a newer change refreshes it in place and nothing is dropped. An emptied book is delivered once, with
+ * both counts 0. A book's events are named by the symbol that owned it at the slice they belong to, as
+ * me_service_market_stream's are. *n = books written; ME_E_INVALID when not subscribed. */
+int me_service_depth_stream(me_service* s, const char* symbol, me_depth_book* out, size_t cap, size_t* n);
+
 int me_service_last_error(const me_service* s, char* buf, size_t cap);
 
 #ifdef __cplusplus

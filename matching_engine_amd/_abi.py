@@ -116,6 +116,12 @@ QUOTE_DTYPE = np.dtype(
 )
 QUOTE_HAS_BID, QUOTE_HAS_ASK = 1, 2
 assert QUOTE_DTYPE.itemsize == 48
+# me_depth_event: one price-level change of a top-D view (qty 0 = the level left the view)
+DEPTH_DTYPE = np.dtype(
+    [("price_q4", "<i8"), ("qty", "<i8"), ("batches", "<u8"), ("symbol", "<u4"), ("side", "u1"), ("pad", "u1", (3,))]
+)
+DEPTH_MAX = 32
+assert DEPTH_DTYPE.itemsize == 32
 
 # every symbol include/me_engine.h declares -> (restype, argtypes)
 _P = C.c_void_p
@@ -167,6 +173,9 @@ PROTOTYPES = {
     "me_quotes_enable": (C.c_int, [_P, C.c_uint64]),
     "me_quotes_read": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "me_quotes_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "me_depth_enable": (C.c_int, [_P, C.c_uint32, C.c_uint64]),
+    "me_depth_read": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "me_depth_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_gen_create": (_P, [C.POINTER(MeGenParams)]),
     "me_gen_destroy": (None, [_P]),
     "me_gen_base_prices": (C.c_int, [_P, _P]),
@@ -276,6 +285,25 @@ class MeMarketUpdate(C.Structure):
 assert C.sizeof(MeMarketUpdate) == 72, "me_market_update layout"
 
 
+class MeDepthLevel(C.Structure):
+    _fields_ = [("price", C.c_int64), ("size", C.c_int32), ("pad", C.c_int32)]
+
+
+class MeDepthBook(C.Structure):
+    _fields_ = [
+        ("symbol", C.c_char * 32),
+        ("scale", C.c_int32),
+        ("n_bids", C.c_uint32),
+        ("n_asks", C.c_uint32),
+        ("pad", C.c_uint32),
+        ("bids", MeDepthLevel * DEPTH_MAX),
+        ("asks", MeDepthLevel * DEPTH_MAX),
+    ]
+
+
+assert C.sizeof(MeDepthLevel) == 16 and C.sizeof(MeDepthBook) == 48 + 2 * 16 * DEPTH_MAX, "me_depth_book layout"
+
+
 class MeBookOrder(C.Structure):
     _fields_ = [
         ("order_id", C.c_char * 32),
@@ -357,6 +385,8 @@ PROTOTYPES.update({
     "me_service_market_data": (C.c_int, [_P, C.c_char_p, C.POINTER(MeMarketData)]),
     "me_service_market_subscribe": (C.c_int, [_P, C.c_int]),
     "me_service_market_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeMarketUpdate), _SZ, C.POINTER(_SZ)]),
+    "me_service_depth_subscribe": (C.c_int, [_P, C.c_uint32]),
+    "me_service_depth_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeDepthBook), _SZ, C.POINTER(_SZ)]),
     "me_cluster_quotes_enable": (C.c_int, [_P, C.c_uint64]),
     "me_cluster_quotes": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "me_service_updates": (C.c_int, [_P, C.c_char_p, C.POINTER(MeOrderUpdate), _SZ, C.POINTER(_SZ)]),

@@ -24,6 +24,7 @@ static_assert(me::ME_C == ME_CHUNK_SLOTS, "chunk width mismatch");
 static_assert(sizeof(me_fill) == 32, "me_fill must be 32 B");
 static_assert(sizeof(me_order_result) == 20, "me_order_result must be 20 B");
 static_assert(sizeof(me_quote) == 48, "me_quote must be 48 B");
+static_assert(sizeof(me_depth_event) == 32, "me_depth_event must be 32 B");
 
 namespace me {
 hipError_t launch_sort_pass(hipStream_t st, const uint32_t* keys_in, const uint32_t* idx_in, uint32_t n,
@@ -49,6 +50,7 @@ hipError_t launch_tape_spill(hipStream_t st, const me_order_result* res, const u
 hipError_t launch_init_levels(hipStream_t st, Level* levels, size_t count);
 hipError_t launch_book_snapshot(hipStream_t st, const BookDev& bk, const SnapReq& rq);
 hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q);
+hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d);
 hipError_t launch_init_chunks(hipStream_t st, Chunk* chunks, size_t count);
 }  // namespace me
 
@@ -275,6 +277,12 @@ struct me_engine {
   me_quote* h_qlog = nullptr;
   unsigned long long* h_qctl = nullptr;
   uint64_t q_consumed = 0;  // events handed out by me_quotes_read
+  // depth feed (me_depth_*): off until enabled; the log and the control words' host copy as above
+  bool depth_on = false;
+  DepthDev dd{};
+  me_depth_event* h_dlog = nullptr;
+  unsigned long long* h_dctl = nullptr;
+  uint64_t d_consumed = 0;  // events handed out by me_depth_read
   uint64_t nmatched = 0;    // batches matched (enqueued match launches), host and device: the events' stamp
   uint32_t last_n = 0;
   uint32_t sq_idx = 0;  // seq-ring state the next k_seq_sweep reads (it writes the other one)
@@ -354,8 +362,22 @@ static void quotes_free(me_engine* e) {
   e->quotes_on = false;
 }
 
+static void depth_free(me_engine* e) {
+  void* dp[] = {e->dd.pub, e->dd.npub, e->dd.cand, e->dd.ncand, e->dd.cev, e->dd.nev, e->dd.off, e->dd.ctl};
+  for (void* p : dp)
+    if (p) (void)hipFree(p);
+  if (e->h_dlog) (void)hipHostFree(e->h_dlog);
+  if (e->h_dctl) (void)hipHostFree(e->h_dctl);
+  e->dd = DepthDev{};
+  e->h_dlog = nullptr;
+  e->h_dctl = nullptr;
+  e->d_consumed = 0;
+  e->depth_on = false;
+}
+
 static void free_all(me_engine* e) {
   quotes_free(e);
+  depth_free(e);
   void* ptrs[] = {e->bk.levels,   e->bk.occ,      e->bk.sym,      e->bk.chunks,     e->bk.tend,
                   e->bk.loc,      e->bk.chunk_top, e->bk.err,       (void*)e->bk.gsym,
                   e->d_tape,      e->d_tape_count, e->d_fills_acc, e->bk.dbg,      e->bk.fcache,
@@ -972,6 +994,17 @@ static int quotes_job(me_engine* e) {
   return ME_OK;
 }
 
+// The depth feed's job, wherever quotes_job runs and directly behind it: every side's top-D view against
+// the published one (me_snapshot.hip k_depth_scan / k_depth_offsets / k_depth_emit).
+static int depth_job(me_engine* e) {
+  DepthDev d = e->dd;
+  d.consumed = e->d_consumed;
+  d.batches = e->nmatched;
+  hipError_t he = launch_depth(e->stream, e->bk, d);
+  if (he != hipSuccess) return e->hip_fail(he, "depth feed launch");
+  return ME_OK;
+}
+
 // One launch of the pipelined register-ladder path: match group g_match (if any), bucket group nb
 // (if any) and clear the counters its batches will use, compact g_tape's tapes (if any) — then the
 // pipeline shifts by one group.
@@ -1063,6 +1096,10 @@ static int pipe_launch(me_engine* e, const me_engine::Group* nb) {
     e->nmatched += gm.n;
     if (e->quotes_on) {  // behind the group's match (side streams joined back), outside its timed span
       int rc = quotes_job(e);
+      if (rc) return rc;
+    }
+    if (e->depth_on) {
+      int rc = depth_job(e);
       if (rc) return rc;
     }
   }
@@ -1206,6 +1243,10 @@ static int enqueue_batch(me_engine* e, const uint64_t* seq, const int64_t* px, c
   e->nmatched++;
   if (e->quotes_on) {  // before the tape job: the slot's completion event then covers the batch's quotes
     rc = quotes_job(e);
+    if (rc) return rc;
+  }
+  if (e->depth_on) {
+    rc = depth_job(e);
     if (rc) return rc;
   }
   if (slot >= 0) {
@@ -1799,6 +1840,102 @@ extern "C" int me_quotes_stats(me_engine* e, uint64_t* groups, uint64_t* events,
   if (groups) *groups = h[QC_GROUPS];
   if (events) *events = h[QC_TAIL];
   if (deferred) *deferred = h[QC_DEFERRED];
+  return ME_OK;
+}
+
+// ---- depth feed (me_snapshot.hip k_depth_scan / k_depth_offsets / k_depth_emit) -------------------
+extern "C" int me_depth_enable(me_engine* e, uint32_t depth, uint64_t cap_events) {
+  if (!e) return ME_E_INVALID;
+  if (e->failed) return ME_E_STATE;
+  if (depth > ME_DEPTH_MAX) return e->fail(ME_E_INVALID, "me_depth_enable: depth above ME_DEPTH_MAX");
+  HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
+  const uint64_t S = e->bk.S, D = depth;
+  // one job emits at most 2 * depth events per side: it always fits an empty log
+  const uint64_t cap = std::max<uint64_t>(cap_events, 4 * D * S);
+  if (depth && cap_events && cap > (1ull << 26))
+    return e->fail(ME_E_INVALID, "me_depth_enable: the log's capacity resolves above 2^26 events");
+  if (e->depth_on) {  // jobs in flight write the log: wait for them before it goes
+    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    depth_free(e);
+  }
+  if (!depth || !cap_events) return ME_OK;
+  DepthDev& d = e->dd;
+  d.D = depth;
+  d.cap = cap;
+  const size_t ns = 2 * S;
+  hipError_t he;
+  if ((he = dalloc(&d.pub, ns * D)) != hipSuccess || (he = dalloc(&d.npub, ns)) != hipSuccess ||
+      (he = dalloc(&d.cand, ns * D)) != hipSuccess || (he = dalloc(&d.ncand, ns)) != hipSuccess ||
+      (he = dalloc(&d.cev, ns * 2 * D)) != hipSuccess || (he = dalloc(&d.nev, ns)) != hipSuccess ||
+      (he = dalloc(&d.off, ns)) != hipSuccess || (he = dalloc(&d.ctl, DC_N)) != hipSuccess ||
+      (he = hipHostMalloc((void**)&e->h_dlog, cap * sizeof(me_depth_event), hipHostMallocDefault)) != hipSuccess ||
+      (he = hipHostMalloc((void**)&e->h_dctl, 4 * 8, hipHostMallocDefault)) != hipSuccess ||
+      (he = hipHostGetDevicePointer((void**)&d.log, e->h_dlog, 0)) != hipSuccess ||
+      (he = hipHostGetDevicePointer((void**)&d.hctl, e->h_dctl, 0)) != hipSuccess ||
+      // the published state: every view empty
+      (he = hipMemsetAsync(d.npub, 0, ns * sizeof(uint32_t), e->stream)) != hipSuccess ||
+      (he = hipMemsetAsync(d.ctl, 0, DC_N * 8, e->stream)) != hipSuccess) {
+    depth_free(e);
+    return e->hip_fail(he, "me_depth_enable");
+  }
+  memset(e->h_dctl, 0, 4 * 8);
+  e->depth_on = true;
+  // the books as they stand at this point of the stream; a rare call, so it waits: the first read after it
+  // holds the whole initial state
+  int rc = depth_job(e);
+  hipError_t hs = rc ? hipSuccess : hipStreamSynchronize(e->stream);
+  if (rc || hs != hipSuccess) {  // a failed enable leaves the feed off, its state freed
+    if (rc) (void)hipStreamSynchronize(e->stream);  // (whatever part of the job was enqueued is done)
+    depth_free(e);
+    return rc ? rc : e->hip_fail(hs, "hipStreamSynchronize");
+  }
+  return ME_OK;
+}
+
+extern "C" int me_depth_read(me_engine* e, me_depth_event* out, size_t cap, size_t* n, size_t* left) {
+  if (n) *n = 0;
+  if (left) *left = 0;
+  if (!e) return ME_E_INVALID;
+  if (!e->depth_on) return e->fail(ME_E_INVALID, "the depth feed is off (me_depth_enable)");
+  if (cap && !out) return e->fail(ME_E_INVALID, "null output");
+  volatile unsigned long long* h = e->h_dctl;
+  uint64_t done = 0, tail;
+  for (bool caught_up = false;;) {
+    tail = h[DC_TAIL];
+    std::atomic_thread_fence(std::memory_order_acquire);  // the events were stored before the tail
+    const uint64_t k = std::min<uint64_t>(tail - e->d_consumed, cap - done);
+    const uint64_t at = e->d_consumed % e->dd.cap;
+    const uint64_t first = std::min<uint64_t>(k, e->dd.cap - at);
+    if (first) memcpy(out + done, e->h_dlog + at, first * sizeof(me_depth_event));
+    if (k > first) memcpy(out + done + first, e->h_dlog, (k - first) * sizeof(me_depth_event));
+    e->d_consumed += k;
+    done += k;
+    if (n) *n = (size_t)done;  // (kept current: an error below still tells the caller what it holds)
+    if (left) *left = (size_t)(tail - e->d_consumed);
+    if (tail != e->d_consumed || !h[DC_PENDING] || caught_up || e->failed) break;
+    // read empty with a deferral outstanding: once everything in flight is done and that still holds, one
+    // catch-up job (the log is empty, so it fits); its events follow in this call or count in *left
+    caught_up = true;
+    HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
+    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    if (h[DC_TAIL] == e->d_consumed && h[DC_PENDING]) {
+      int rc = depth_job(e);
+      if (rc) return rc;
+      HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    }
+  }
+  if (n) *n = (size_t)done;
+  if (left) *left = (size_t)(tail - e->d_consumed);
+  return ME_OK;
+}
+
+extern "C" int me_depth_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred) {
+  if (!e) return ME_E_INVALID;
+  if (!e->depth_on) return e->fail(ME_E_INVALID, "the depth feed is off (me_depth_enable)");
+  volatile unsigned long long* h = e->h_dctl;
+  if (groups) *groups = h[DC_JOBS];
+  if (events) *events = h[DC_TAIL];
+  if (deferred) *deferred = h[DC_DEFERRED];
   return ME_OK;
 }
 

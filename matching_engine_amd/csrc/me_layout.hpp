@@ -511,6 +511,36 @@ struct QuoteDev {
   uint32_t pad;
 };
 
+// ---- depth feed (me_snapshot.hip k_depth_scan / k_depth_offsets / k_depth_emit) ------
+// A side index is 2 * symbol + side (0 bids, 1 asks); D = depth levels per side. Everything below is
+// allocated by me_depth_enable and nothing before it.
+struct alignas(16) DepthLvl {
+  long long price, qty;
+};
+// Control words in HBM (DepthDev::ctl); the first four are mirrored into pinned memory (DepthDev::hctl) by
+// the last workgroup of every emit pass and mean what the quote feed's do. The rest belong to the job in
+// flight: the tail it started from, its event total, whether it fits (k_depth_offsets writes them for the
+// emit pass), and the count of emit workgroups that have finished.
+enum : uint32_t { DC_TAIL = 0, DC_JOBS = 1, DC_DEFERRED = 2, DC_PENDING = 3, DC_JOB_TAIL = 4, DC_JOB_TOTAL = 5,
+                  DC_JOB_FIT = 6, DC_DONE = 7, DC_N = 8 };
+struct DepthDev {
+  DepthLvl* pub;             // [2S][D] published views, best first
+  uint32_t* npub;            // [2S] their lengths
+  DepthLvl* cand;            // [2S][D] this job's views of the sides that differ
+  uint32_t* ncand;           // [2S]
+  DepthLvl* cev;             // [2S][2D] this job's events per side in priority order (qty 0 = DELETE)
+  uint32_t* nev;             // [2S] events per side (0: the side did not change)
+  uint32_t* off;             // [2S] events before each side
+  unsigned long long* ctl;   // [DC_N]
+  unsigned long long* hctl;  // [4] host-mapped copy of the first four
+  me_depth_event* log;       // [cap] host-mapped ring: event i sits at i % cap
+  unsigned long long cap;
+  unsigned long long consumed;  // events the host had read when the job was enqueued (<= the tail)
+  unsigned long long batches;   // the job's stamp
+  uint32_t D;
+  uint32_t pad;
+};
+
 constexpr int BK_CAP = 128;          // records per bucket (two 64-record blocks)
 constexpr int BK_KIND_SHIFT = 26;    // BkRec::ok: six kind bits (side, type, op, time in force) above the batch index
 constexpr uint32_t BK_KIND_BITS = 63u;

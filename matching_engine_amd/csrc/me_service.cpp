@@ -41,6 +41,7 @@
 #include <condition_variable>
 #include <deque>
 #include <list>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -252,6 +253,20 @@ struct me_service {
   std::list<me_market_update> md_q;
   std::unordered_map<std::string, std::list<me_market_update>::iterator> md_at;
   std::vector<std::deque<std::pair<uint64_t, std::string>>> md_owner;
+  // The depth stream (me_service_depth_subscribe / _stream), also under md_mu. The engine sends deltas, the
+  // service materialises views: dp_view holds every named symbol's top-D {price: qty} per side, dp_q the
+  // symbols whose view changed since they were last handed out, in first-change order (one entry each).
+  // dp_owner is the depth feed's own ownership history: the two feeds are read at different moments, and each
+  // pops only what its own stamps have passed.
+  struct DepthView {
+    std::map<int64_t, int64_t> side[2];  // [0] bids, [1] asks, ascending price
+  };
+  std::atomic<bool> dp_on{false};
+  uint32_t dp_depth = 0;
+  std::unordered_map<std::string, DepthView> dp_view;
+  std::list<std::string> dp_q;
+  std::unordered_map<std::string, std::list<std::string>::iterator> dp_at;
+  std::vector<std::deque<std::pair<uint64_t, std::string>>> dp_owner;
   uint64_t nsub = 0;  // slices the backend accepted since create (eng_mu): slice k's events are stamped k
   // --- background flusher
   std::thread flusher;
@@ -627,9 +642,59 @@ static void md_note_owners(me_service* s, const Slice& sl, uint64_t k) {
   for (size_t i = 0; i < sl.size(); ++i) {
     const uint32_t sid = sl.sid[i];
     if (sid == kNoBook) continue;
-    if (sid >= s->md_owner.size()) s->md_owner.resize((size_t)sid + 1);
-    auto& h = s->md_owner[sid];
-    if (h.empty() || h.back().second != sl.meta[i].symbol) h.emplace_back(k, sl.meta[i].symbol);
+    if (s->md_on) {
+      if (sid >= s->md_owner.size()) s->md_owner.resize((size_t)sid + 1);
+      auto& h = s->md_owner[sid];
+      if (h.empty() || h.back().second != sl.meta[i].symbol) h.emplace_back(k, sl.meta[i].symbol);
+    }
+    if (s->dp_on) {  // the depth feed's own history
+      if (sid >= s->dp_owner.size()) s->dp_owner.resize((size_t)sid + 1);
+      auto& h = s->dp_owner[sid];
+      if (h.empty() || h.back().second != sl.meta[i].symbol) h.emplace_back(k, sl.meta[i].symbol);
+    }
+  }
+}
+
+// (md_mu held) `name`'s view changed: it gets its place in the queue unless it has one
+static void dp_mark(me_service* s, const std::string& name) {
+  if (s->dp_at.count(name)) return;
+  s->dp_q.push_back(name);
+  s->dp_at.emplace(name, std::prev(s->dp_q.end()));
+}
+
+// Read the engine's depth events and apply them to the views (eng_mu held). Naming as in md_pull, by the
+// depth feed's own history. A book changes hands only when it is empty: the symbol that loses it ends
+// with an empty view, whatever the conflated events said.
+static int dp_pull(me_service* s) {
+  std::vector<me_depth_event> buf(4096);
+  for (;;) {
+    size_t n = 0, left = 0;
+    const int rc = me_depth_read(s->eng, buf.data(), buf.size(), &n, &left);
+    if (rc != ME_OK) return s->fail(rc, "depth stream: reading the engine's depth feed failed: " + backend_err(s));
+    std::lock_guard<std::mutex> lm(s->md_mu);
+    for (size_t i = 0; i < n; ++i) {
+      const me_depth_event& ev = buf[i];
+      if (ev.symbol >= s->dp_owner.size() || s->dp_owner[ev.symbol].empty()) continue;  // (a book no slice ever named)
+      auto& h = s->dp_owner[ev.symbol];
+      const size_t name_max = sizeof(((me_depth_book*)nullptr)->symbol) - 1;  // views are keyed as handed out
+      while (h.size() > 1 && h[1].first <= ev.batches) {
+        auto old = s->dp_view.find(h.front().second.substr(0, name_max));
+        if (old != s->dp_view.end() && (!old->second.side[0].empty() || !old->second.side[1].empty())) {
+          old->second.side[0].clear();
+          old->second.side[1].clear();
+          dp_mark(s, old->first);
+        }
+        h.pop_front();
+      }
+      const std::string name = h.front().second.substr(0, name_max);
+      auto& side = s->dp_view[name].side[ev.side == ME_SIDE_SELL ? 1 : 0];
+      if (ev.qty > 0)
+        side[ev.price_q4] = ev.qty;
+      else
+        side.erase(ev.price_q4);
+      dp_mark(s, name);
+    }
+    if (!left) return ME_OK;
   }
 }
 
@@ -1293,6 +1358,7 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
       std::lock_guard<std::mutex> le(s->eng_mu);
       r = backend_collect(s, fl.front());
       if (r == ME_OK && s->md_on) (void)md_pull(s);  // (a failed read is in last_error; the slice is matched)
+      if (r == ME_OK && s->dp_on) (void)dp_pull(s);
     }
     if (r != ME_OK) return lost(r, "engine lost an accepted slice: ");
     Inflight& f = fl.front();
@@ -1323,7 +1389,7 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
       r = backend_submit(s, f, accepted);
       if (accepted) {
         ++s->nsub;
-        if (s->md_on) md_note_owners(s, f.sl, s->nsub);
+        if (s->md_on || s->dp_on) md_note_owners(s, f.sl, s->nsub);
       }
     }
     if (r != ME_OK && !accepted) {  // refused: the slices before it go first, then it is split
@@ -1610,6 +1676,84 @@ extern "C" int me_service_market_stream(me_service* s, const char* symbol, me_ma
       out[k++] = s->md_q.front();
       s->md_at.erase(s->md_q.front().symbol);
       s->md_q.pop_front();
+    }
+  }
+  if (n) *n = k;
+  return ME_OK;
+}
+
+extern "C" int me_service_depth_subscribe(me_service* s, uint32_t depth) {
+  if (!s) return ME_E_INVALID;
+  std::lock_guard<std::mutex> lf(s->flush_mu);  // no slice is in flight while it is held
+  std::lock_guard<std::mutex> le(s->eng_mu);
+  auto reset = [&](bool on, uint32_t d) {
+    s->dp_on = on;
+    s->dp_depth = d;
+    s->dp_view.clear();
+    s->dp_q.clear();
+    s->dp_at.clear();
+    s->dp_owner.clear();
+  };
+  if (!depth) {
+    if (s->dp_on && s->eng) me_depth_enable(s->eng, 0, 0);
+    std::lock_guard<std::mutex> lm(s->md_mu);
+    reset(false, 0);
+    return ME_OK;
+  }
+  if (!s->eng) return s->fail(ME_E_INVALID, "depth stream: the matcher has no depth feed");
+  if (depth > ME_DEPTH_MAX) return s->fail(ME_E_INVALID, "depth stream: depth above ME_DEPTH_MAX");
+  // room for four jobs in which every level of every view changes
+  const int rc = me_depth_enable(s->eng, depth, std::max<uint64_t>(16ull * depth * s->sym_cap, 4096));
+  if (rc != ME_OK) return s->fail(rc, "depth stream: me_depth_enable failed: " + backend_err(s));
+  std::vector<std::string> names;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    names = s->names;
+  }
+  {
+    std::lock_guard<std::mutex> lm(s->md_mu);
+    reset(true, depth);
+    s->dp_owner.assign(names.size(), {});
+    for (size_t i = 0; i < names.size(); ++i) s->dp_owner[i].emplace_back(0, names[i]);
+  }
+  return dp_pull(s);  // the books as they stand
+}
+
+extern "C" int me_service_depth_stream(me_service* s, const char* symbol, me_depth_book* out, size_t cap, size_t* n) {
+  if (n) *n = 0;
+  if (!s || (cap && !out)) return ME_E_INVALID;
+  std::lock_guard<std::mutex> lm(s->md_mu);
+  if (!s->dp_on) return s->fail(ME_E_INVALID, "depth stream: not subscribed (me_service_depth_subscribe)");
+  auto sat = [](int64_t v) { return (int32_t)(v > INT32_MAX ? INT32_MAX : v); };
+  auto fill = [&](const std::string& name, me_depth_book& b) {  // the symbol's whole current view, best first
+    memset(&b, 0, sizeof b);
+    put(b.symbol, sizeof b.symbol, name);
+    b.scale = 4;
+    auto v = s->dp_view.find(name);
+    if (v == s->dp_view.end()) return;
+    for (auto it = v->second.side[0].rbegin(); it != v->second.side[0].rend() && b.n_bids < ME_DEPTH_MAX; ++it) {
+      b.bids[b.n_bids].price = it->first;
+      b.bids[b.n_bids++].size = sat(it->second);
+    }
+    for (auto it = v->second.side[1].begin(); it != v->second.side[1].end() && b.n_asks < ME_DEPTH_MAX; ++it) {
+      b.asks[b.n_asks].price = it->first;
+      b.asks[b.n_asks++].size = sat(it->second);
+    }
+    if (!b.n_bids && !b.n_asks) s->dp_view.erase(v);  // (an emptied book is handed out once, then forgotten)
+  };
+  size_t k = 0;
+  if (symbol && *symbol) {
+    auto it = s->dp_at.find(std::string(symbol).substr(0, sizeof(out->symbol) - 1));
+    if (it != s->dp_at.end() && cap) {
+      fill(it->first, out[k++]);
+      s->dp_q.erase(it->second);
+      s->dp_at.erase(it);
+    }
+  } else {
+    while (k < cap && !s->dp_q.empty()) {
+      fill(s->dp_q.front(), out[k++]);
+      s->dp_at.erase(s->dp_q.front());
+      s->dp_q.pop_front();
     }
   }
   if (n) *n = k;

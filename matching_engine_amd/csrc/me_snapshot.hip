@@ -346,6 +346,302 @@ hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q) {
   return hipGetLastError();
 }
 
+// ---- depth feed: top-D price-level changes (me_depth_*, include/me_engine.h) -------------------------
+// Three launches behind every match launch of an engine with the depth feed on.
+//
+// k_depth_scan: one wave per (symbol, side), four per workgroup. It gathers the side's view — the D best
+// occupied levels, window first, then far — diffs it against the published view and writes the side's
+// candidate events (at their ranks), its candidate view and its event count. A side whose window is empty
+// by the hints, with no far level and an empty published view, costs the 64-B state and one count.
+//   The window walk goes outward from the hint (a bound) in blocks of 64 levels: lane i
+// holds level 64 b + i, a ballot of total > 0 and a popcount of the bits of better priority compact the
+// occupied levels into the view. Windows of L <= 128 load every total of a block (two blocks at most);
+// deeper windows read the occ words, 64 words = 4,096 levels per load, visit only blocks with a set bit
+// and load only the totals under set bits: the total decides, a set bit over a total <= 0 is skipped.
+// The ask walk starts no lower than one level above the best bid found, as k_quote_scan's does.
+//   The diff stages both lists (<= 32 entries each, sorted) in LDS: lanes 0..31 own the new view's
+// entries, lanes 32..63 the published ones; each runs down the other list once for "is my price there,
+// with which total" and "how many of its entries beat my price". A new entry emits a SET unless published
+// with the same total, a published one a DELETE unless its price survives; an event's rank is the emitting
+// entries of its own list before it plus those of the other list with a better price: one ballot and
+// two popcounts, nothing is sorted.
+//
+// k_depth_offsets: one workgroup. Block scans, 1,024 counts a round with the running total carried from
+// round to round, turn the 2S counts into offsets and the job's total; the fit test is the quote feed's; it
+// leaves {tail, total, fit} for the emit pass.
+//
+// k_depth_emit: spread over the grid, at most 2,048 waves, each over a run of consecutive sides. Only when
+// the job fits, a wave copies the events of its changed sides to log[(tail + offset + rank) % cap] and their
+// candidate views over the published ones. A wave that wrote events fences once (system scope) behind all of
+// them, not once per side, and every workgroup counts itself done on a device-scope counter; the last one updates the control words, mirrors them to pinned memory, fences and
+// stores the host-visible tail: a host that reads the tail first never sees an unwritten event.
+constexpr int DEPTH_WAVES = 4;
+constexpr uint32_t DEPTH_EMIT_WAVES = 2048;  // waves of the emit pass at most (8 per CU)
+
+__device__ __forceinline__ void depth_wave_order() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
+
+// Block b of the window (levels 64 b .. 64 b + 63): the lanes of `gate` load their level's total; the
+// occupied ones go to view[found ..] in priority order (view may be null: a search). `best` takes the
+// first occupied level found.
+__device__ __forceinline__ void depth_take_block(const Level* lv, long long base, int b, unsigned long long gate,
+                                                 bool bid, DepthLvl* view, uint32_t want, uint32_t& found, int& best) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int l = b * 64 + lane;
+  long long t = 0;
+  if ((gate >> lane) & 1ull) t = lv[l].total;
+  const unsigned long long m = __ballot(t > 0);
+  if (!m) return;
+  const unsigned long long ahead = bid ? (lane == 63 ? 0ull : m >> (lane + 1)) : m & ((1ull << lane) - 1ull);
+  const uint32_t at = found + (uint32_t)__popcll(ahead);
+  if (t > 0 && at < want && view) {
+    DepthLvl x;
+    x.price = base + l;
+    x.qty = t;
+    view[at] = x;
+  }
+  if (found == 0u) best = bid ? b * 64 + 63 - __builtin_clzll(m) : b * 64 + __builtin_ctzll(m);
+  found = min(want, found + (uint32_t)__popcll(m));
+}
+
+// The window part of a view: from level `start` (inside the window) outward until `want` levels are
+// found or the window's edge is reached.
+__device__ __forceinline__ void depth_window(const BookDev& bk, uint32_t s, long long base, bool bid, int start,
+                                             DepthLvl* view, uint32_t want, uint32_t& found, int& best) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int W = (int)bk.Lwords;
+  const Level* lv = bk.levels + (size_t)s * bk.L;
+  const int sb = start & 63;
+  unsigned long long first = bid ? (sb == 63 ? ~0ull : (1ull << (sb + 1)) - 1ull) : ~0ull << sb;
+  int w0 = start >> 6;
+  if (bk.L <= 128u) {
+    for (int b = w0; (bid ? b >= 0 : b < W) && found < want; b += bid ? -1 : 1) {
+      depth_take_block(lv, base, b, first, bid, view, want, found, best);
+      first = ~0ull;
+    }
+    return;
+  }
+  const unsigned long long* oc = bk.occ + (size_t)s * bk.Lwords;
+  while (bid ? w0 >= 0 : w0 < W) {
+    const int wi = bid ? w0 - lane : w0 + lane;
+    unsigned long long word = wi >= 0 && wi < W ? oc[wi] : 0ull;
+    if (lane == 0) word &= first;
+    first = ~0ull;
+    unsigned long long nz = __ballot(word != 0ull);
+    while (nz && found < want) {
+      const int j = __builtin_ctzll(nz);
+      nz &= nz - 1ull;
+      const unsigned long long g = (unsigned long long)__shfl((long long)word, j, 64);
+      depth_take_block(lv, base, bid ? w0 - j : w0 + j, g, bid, view, want, found, best);
+    }
+    if (found >= want) break;
+    w0 += bid ? -64 : 64;
+  }
+}
+
+__global__ __launch_bounds__(DEPTH_WAVES * 64) void k_depth_scan(BookDev bk, DepthDev d) {
+  __shared__ DepthLvl s_new[DEPTH_WAVES][ME_DEPTH_MAX];
+  __shared__ DepthLvl s_pub[DEPTH_WAVES][ME_DEPTH_MAX];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t sidx = blockIdx.x * DEPTH_WAVES + wv;
+  if (sidx >= 2u * bk.S) return;  // (whole waves leave: the kernel has no block barrier)
+  const uint32_t s = sidx >> 1;
+  const bool bid = (sidx & 1u) == 0u;
+  const uint32_t D = d.D;
+  const int L = (int)bk.L;
+  const SymState st = bk.sym[s];
+  const uint32_t nfar_hint = st.nfar[bid ? 0 : 1];
+  const bool win = bid ? st.best_bid >= 0 : st.best_ask < L;
+  const uint32_t np = min(d.npub[sidx], D);
+  if (!win && !nfar_hint && !np) {  // idle: nothing rests by the hints, nothing is published
+    if (lane == 0) d.nev[sidx] = 0;
+    return;
+  }
+  DepthLvl* nv = s_new[wv];
+  DepthLvl* pv = s_pub[wv];
+  // the published view and the far region's place do not depend on the walk: their loads go out ahead of it
+  DepthLvl pubv{};
+  if (lane < np) pubv = d.pub[(size_t)sidx * D + lane];
+  FarDir fd{};
+  if (nfar_hint) fd = bk.fdir[(size_t)s * 2u + (bid ? 0u : 1u)];
+  // ---- gather the view
+  uint32_t n = 0;
+  if (win) {
+    int best = -1;
+    if (bid) {
+      depth_window(bk, s, st.base, true, min(st.best_bid, L - 1), nv, D, n, best);
+    } else {
+      int lb = -1;
+      if (st.best_bid >= 0) {  // the best bid found: the ask walk starts above it
+        uint32_t one = 0;
+        depth_window(bk, s, st.base, true, min(st.best_bid, L - 1), nullptr, 1u, one, lb);
+      }
+      const int la = max(max(st.best_ask, 0), lb + 1);
+      if (la < L) depth_window(bk, s, st.base, false, la, nv, D, n, best);
+    }
+  }
+  if (n < D && nfar_hint) {  // complete it from the far region: entries from the end, occupied ones only
+    const FarLevel* far = bk.far + fd.off;
+    const uint32_t nfar = min(nfar_hint, fd.cap);
+    for (uint32_t k = 0; k < nfar && n < D; k += 64u) {
+      const uint32_t i = k + lane;
+      long long t = 0, px = 0;
+      if (i < nfar) {
+        const FarLevel f = far[nfar - 1u - i];
+        t = f.total;
+        px = f.price;
+      }
+      const unsigned long long m = __ballot(t > 0);
+      const uint32_t at = n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (t > 0 && at < D) {
+        DepthLvl x;
+        x.price = px;
+        x.qty = t;
+        nv[at] = x;
+      }
+      n = min(D, n + (uint32_t)__popcll(m));
+    }
+  }
+  if (lane < np) pv[lane] = pubv;
+  depth_wave_order();
+  // ---- diff: lanes 0..31 own the new entries, lanes 32..63 the published ones
+  const bool is_new = lane < 32u;
+  const uint32_t idx = lane & 31u;
+  const uint32_t mine_n = is_new ? n : np, other_n = is_new ? np : n;
+  const DepthLvl* other = is_new ? pv : nv;
+  const bool valid = idx < mine_n;
+  DepthLvl me_{};
+  if (valid) me_ = is_new ? nv[idx] : pv[idx];
+  bool there = false;
+  long long there_qty = 0;
+  uint32_t better = 0;  // entries of the other list with a better price (they form its head: it is sorted)
+  for (uint32_t k = 0; k < other_n; ++k) {
+    const DepthLvl o = other[k];
+    if (o.price == me_.price) {
+      there = true;
+      there_qty = o.qty;
+    }
+    better += bid ? o.price > me_.price : o.price < me_.price;
+  }
+  const bool emits = valid && (is_new ? !(there && there_qty == me_.qty) : !there);
+  const unsigned long long em = __ballot(emits);
+  const uint32_t em_new = (uint32_t)em, em_pub = (uint32_t)(em >> 32);
+  const uint32_t ne = (uint32_t)__popcll(em);
+  if (emits) {
+    const uint32_t own = is_new ? em_new : em_pub, oth = is_new ? em_pub : em_new;
+    const uint32_t rank = (uint32_t)__popc(own & ((1u << idx) - 1u)) +
+                          (uint32_t)__popc(oth & (better >= 32u ? ~0u : (1u << better) - 1u));
+    DepthLvl ev;
+    ev.price = me_.price;
+    ev.qty = is_new ? me_.qty : 0;
+    d.cev[(size_t)sidx * 2u * D + rank] = ev;
+  }
+  if (ne) {
+    if (lane < n) d.cand[(size_t)sidx * D + lane] = nv[lane];
+    if (lane == 0) d.ncand[sidx] = n;
+  }
+  if (lane == 0) d.nev[sidx] = ne;
+}
+
+__global__ __launch_bounds__(SNAP_T) void k_depth_offsets(BookDev bk, DepthDev d) {
+  __shared__ uint32_t wsum[SNAP_T / 64];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t ns = 2u * bk.S;
+  uint32_t run = 0;
+  for (uint32_t base = 0; base < ns; base += SNAP_T) {  // `run` carries the rounds before this one
+    const uint32_t i = base + tid;
+    const uint32_t c = i < ns ? d.nev[i] : 0u;
+    uint32_t tot = 0;
+    const uint32_t ex = snap_block_excl_scan(c, wsum, tot);
+    if (i < ns) d.off[i] = run + ex;
+    run += tot;
+  }
+  if (tid == 0) {
+    const unsigned long long tail = d.ctl[DC_TAIL];
+    const unsigned long long used = tail - d.consumed;  // (consumed <= tail: the host reads only logged events)
+    d.ctl[DC_JOB_TAIL] = tail;
+    d.ctl[DC_JOB_TOTAL] = run;
+    d.ctl[DC_JOB_FIT] = used <= d.cap && run <= d.cap - used ? 1ull : 0ull;
+  }
+}
+
+__global__ __launch_bounds__(DEPTH_WAVES * 64) void k_depth_emit(BookDev bk, DepthDev d, uint32_t spw) {
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t ns = 2u * bk.S, D = d.D;
+  const bool fit = d.ctl[DC_JOB_FIT] != 0ull;
+  const unsigned long long total = d.ctl[DC_JOB_TOTAL];
+  if (fit && total) {
+    const unsigned long long tail = d.ctl[DC_JOB_TAIL];
+    // this wave's sides [lo, hi): 64 counts per load, then the changed sides one after the other
+    const uint32_t lo = min(ns, (blockIdx.x * DEPTH_WAVES + wv) * spw), hi = min(ns, lo + spw);
+    bool wrote = false;
+    for (uint32_t base = lo; base < hi; base += 64u) {
+      const uint32_t i = base + lane;
+      const uint32_t c = i < hi ? d.nev[i] : 0u;
+      unsigned long long m = __ballot(c != 0u);
+      wrote |= m != 0ull;
+      while (m) {
+        const int j = __builtin_ctzll(m);
+        m &= m - 1ull;
+        const uint32_t sidx = base + (uint32_t)j, s = sidx >> 1;
+        const uint32_t ne = min((uint32_t)__shfl((int)c, j, 64), 2u * D);
+        if (lane < ne) {
+          const DepthLvl x = d.cev[(size_t)sidx * 2u * D + lane];
+          me_depth_event ev;
+          ev.price_q4 = x.price;
+          ev.qty = x.qty;
+          ev.batches = d.batches;
+          ev.symbol = bk.gsym ? bk.gsym[s] : s;
+          ev.side = (sidx & 1u) ? ME_SIDE_SELL : ME_SIDE_BUY;
+          ev.pad[0] = ev.pad[1] = ev.pad[2] = 0;
+          d.log[(tail + d.off[sidx] + lane) % d.cap] = ev;
+        }
+        // (the published view is read by the next job's scan only, a later launch: no fence for it)
+        const uint32_t nc = min(d.ncand[sidx], D);
+        if (lane < nc) d.pub[(size_t)sidx * D + lane] = d.cand[(size_t)sidx * D + lane];
+        if (lane == 0) d.npub[sidx] = nc;
+      }
+    }
+    if (wrote) __threadfence_system();  // one fence per wave, behind all the events it wrote
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long before = atomicAdd(&d.ctl[DC_DONE], 1ull);
+    if (before + 1ull == gridDim.x) {  // the last workgroup: every event of the job is behind a fence
+      __threadfence_system();
+      const unsigned long long tail = d.ctl[DC_JOB_TAIL];
+      const unsigned long long jobs = d.ctl[DC_JOBS] + 1ull;
+      const unsigned long long deferred = d.ctl[DC_DEFERRED] + (fit ? 0ull : 1ull);
+      const unsigned long long ntail = fit ? tail + total : tail;
+      d.ctl[DC_TAIL] = ntail;
+      d.ctl[DC_JOBS] = jobs;
+      d.ctl[DC_DEFERRED] = deferred;
+      d.ctl[DC_PENDING] = fit ? 0ull : 1ull;
+      d.ctl[DC_DONE] = 0ull;
+      volatile unsigned long long* h = d.hctl;
+      h[DC_JOBS] = jobs;
+      h[DC_DEFERRED] = deferred;
+      h[DC_PENDING] = fit ? 0ull : 1ull;
+      __threadfence_system();
+      h[DC_TAIL] = ntail;
+    }
+  }
+}
+
+// The depth feed's job: scan + offsets + emit on st (behind the match launch whose books it reads). The emit
+// pass runs at most DEPTH_EMIT_WAVES waves, each over a run of consecutive sides: its cost is the events it
+// writes and one system-scope fence per wave that wrote any, not one per side.
+hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d) {
+  const uint32_t ns = 2u * bk.S;
+  const uint32_t grid = (ns + DEPTH_WAVES - 1u) / DEPTH_WAVES;
+  const uint32_t spw = (ns + DEPTH_EMIT_WAVES - 1u) / DEPTH_EMIT_WAVES;  // sides per emit wave (>= 1)
+  const uint32_t ewaves = (ns + spw - 1u) / spw;
+  hipLaunchKernelGGL(k_depth_scan, dim3(grid), dim3(DEPTH_WAVES * 64), 0, st, bk, d);
+  hipLaunchKernelGGL(k_depth_offsets, dim3(1), dim3(SNAP_T), 0, st, bk, d);
+  hipLaunchKernelGGL(k_depth_emit, dim3((ewaves + DEPTH_WAVES - 1u) / DEPTH_WAVES), dim3(DEPTH_WAVES * 64), 0, st, bk, d,
+                     spw);
+  return hipGetLastError();
+}
+
 hipError_t launch_book_snapshot(hipStream_t st, const BookDev& bk, const SnapReq& rq) {
   if (!rq.nsym || !rq.depth) return hipSuccess;
   hipLaunchKernelGGL(k_book_snapshot, dim3(rq.nsym * 2), dim3(SNAP_T), 0, st, bk, rq);

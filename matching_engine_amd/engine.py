@@ -381,6 +381,37 @@ class Engine:
         _check(self.lib, self.h, self.lib.me_quotes_stats(self.h, C.byref(g), C.byref(ev), C.byref(d)))
         return {"groups": g.value, "events": ev.value, "deferred": d.value}
 
+    # -- depth feed (me_depth_*)
+    def depth_enable(self, depth: int, cap_events: int):
+        """Turn the depth feed on: the `depth` best levels per side (<= 32), a log of cap_events events (raised
+        to 4 * depth * num_symbols); depth or cap_events 0 turns it off. Enabling takes every view once at this
+        point of the stream."""
+        _check(self.lib, self.h, self.lib.me_depth_enable(self.h, int(depth), int(cap_events)))
+        self._depth = int(depth) if cap_events else 0
+
+    def depth_read(self, cap: int = 0):
+        """(events DEPTH_DTYPE, left): up to `cap` logged events in order (0 = a buffer of one job's most) and
+        how many stay unread. Launches no partial group; see me_depth_read for what is there when."""
+        cap = int(cap) or max(1, 4 * getattr(self, "_depth", 1) * self.num_symbols)
+        out = np.zeros(cap, dtype=_abi.DEPTH_DTYPE)
+        n, left = C.c_size_t(0), C.c_size_t(0)
+        _check(self.lib, self.h, self.lib.me_depth_read(self.h, ptr(out), cap, C.byref(n), C.byref(left)))
+        return out[: n.value], left.value
+
+    def depth_drain(self) -> np.ndarray:
+        """Every logged event: reads until none is left (a deferred job's catch-up included)."""
+        parts = []
+        while True:
+            ev, left = self.depth_read()
+            parts.append(ev)
+            if not left:
+                return np.concatenate(parts)
+
+    def depth_stats(self) -> dict:
+        g, ev, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib, self.h, self.lib.me_depth_stats(self.h, C.byref(g), C.byref(ev), C.byref(d)))
+        return {"groups": g.value, "events": ev.value, "deferred": d.value}
+
     # -- timing
     def timing_enable(self, period: int = 1):
         """HIP events on every `period`-th match launch (True = every launch, 0/False = off)."""

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (FILL_DTYPE, LEVEL_DTYPE, RESULT_DTYPE, MeBookOrder, MeCancelRequest, MeOrderRequest,
-                   MeOrderResponse, MeMarketData, MeMarketUpdate, MeOrderUpdate, ptr)
+                   MeOrderResponse, MeMarketData, MeMarketUpdate, MeDepthBook, MeOrderUpdate, ptr)
 
 
 class ServiceError(RuntimeError):
@@ -155,6 +155,34 @@ class MatchingEngineService:
         return {"symbol": symbol, "best_bid": m.best_bid, "best_ask": m.best_ask, "scale": m.scale,
                 "bid_size": m.bid_size, "ask_size": m.ask_size, "has_bid": bool(m.has_bid),
                 "has_ask": bool(m.has_ask)}
+
+    def depth_subscribe(self, depth: int):
+        """The depth stream (me_service_depth_subscribe): enable the engine's depth feed at `depth` levels per
+        side and queue the books as they stand; 0 turns it off. ServiceError (code ME_E_INVALID) on a matcher."""
+        rc = self.lib.me_service_depth_subscribe(self.h, int(depth))
+        if rc != 0:
+            e = ServiceError(f"depth_subscribe failed ({rc}): {self.last_error()}")
+            e.code = rc
+            raise e
+
+    def depth_stream(self, symbol=None, cap=256) -> list:
+        """Drain the queued top-D books (one symbol's, or all in first-change order): dicts with symbol, scale,
+        bids and asks as lists of (price, size), best first."""
+        out = []
+        buf = (MeDepthBook * cap)()
+        while True:
+            n = C.c_size_t(0)
+            rc = self.lib.me_service_depth_stream(self.h, symbol.encode() if symbol else None, buf, cap, C.byref(n))
+            if rc != 0:
+                e = ServiceError(f"depth_stream failed ({rc}): {self.last_error()}")
+                e.code = rc
+                raise e
+            for b in buf[: n.value]:
+                out.append({"symbol": b.symbol.decode(), "scale": b.scale,
+                            "bids": [(b.bids[i].price, b.bids[i].size) for i in range(b.n_bids)],
+                            "asks": [(b.asks[i].price, b.asks[i].size) for i in range(b.n_asks)]})
+            if n.value < cap:
+                return out
 
     def market_subscribe(self, on: bool = True):
         """StreamMarketData as a change stream (me_service_market_subscribe): enable the backend's quote
