@@ -39,7 +39,9 @@ enum { ME_SIDE_UNSPECIFIED = 0, ME_SIDE_BUY = 1, ME_SIDE_SELL = 2 };
 /* OrderType (proto/matching_engine.proto:11-14). Any value != LIMIT is treated as MARKET,
  * mirroring type_str / the LIMIT-only price check (matching_engine_service.cpp:50,78). */
 enum { ME_TYPE_LIMIT = 0, ME_TYPE_MARKET = 1 };
-/* Operation carried by a batch record. CANCEL is a build extension (no reference RPC). */
+/* Operation carried by a batch record. CANCEL is a build extension (no reference RPC).
+ * A REDUCE has no op value of its own: it is a CANCEL record (bit 3) whose type bit (bit 2) is set as
+ * well, ME_KIND_REDUCE below. */
 enum { ME_OP_NEW = 0, ME_OP_CANCEL = 1 };
 /* OrderUpdate.Status (proto/matching_engine.proto:79-85). */
 enum {
@@ -56,7 +58,7 @@ enum {
   ME_RJ_BAD_SIDE = 2,      /* side not BUY/SELL (reference: CHECK side IN (1,2) -> "DB insert failed") */
   ME_RJ_OUT_OF_WINDOW = 3, /* retired: every int64 price is accepted (never produced) */
   ME_RJ_BAD_SYMBOL = 4,    /* symbol id >= num_symbols */
-  ME_RJ_UNKNOWN_ORDER = 5, /* CANCEL target is not a live resting order of this symbol */
+  ME_RJ_UNKNOWN_ORDER = 5, /* CANCEL / REDUCE target is not a live resting order of this symbol */
   ME_RJ_BAD_SEQ = 6,       /* seq == 0 (no OID is 0: the counter starts at 1, storage.cpp:254-267) */
   ME_RJ_CAPACITY = 7,      /* service only: a LIMIT the shard could not admit while its books hold
                               max_resting orders (me_service.h; never produced by the engine) */
@@ -83,6 +85,21 @@ enum { ME_TIF_GTC = 0, ME_TIF_IOC = 1, ME_TIF_FOK = 2, ME_TIF_POST_ONLY = 3 };
  * bits 4-5 time in force (ME_TIF_*; 0 = GTC), bits 6-7 reserved and ignored. */
 #define ME_KIND(side, type, op) ((uint8_t)(((side) & 3) | (((type) & 1) << 2) | (((op) & 1) << 3)))
 #define ME_KIND_TIF(side, type, op, tif) ((uint8_t)(ME_KIND(side, type, op) | (((tif) & 3) << 4)))
+
+/* REDUCE (build extension): a record whose kind has bits 3 and 2 both set takes `qty` off
+ * the resting order whose seq is in price_q4 and leaves it where it is. Side and time-in-force bits are
+ * ignored, as on a CANCEL, and the seq rule is the CANCEL's. With the target holding r and qty = d:
+ *   d <= 0    REJECTED / ME_RJ_BAD_QTY, whether or not the target lives (after BAD_SYMBOL, before
+ *             UNKNOWN_ORDER).
+ *   no live resting order of this symbol has that seq: REJECTED / ME_RJ_UNKNOWN_ORDER, as for a CANCEL.
+ *   d >= r    exactly a CANCEL: ME_ST_CANCELED, remaining_qty = r (the quantity removed).
+ *   d <  r    the order keeps its slot, its seq and its place in the level's FIFO and holds r - d; the
+ *             level total drops by d, the resting count is unchanged. ME_ST_NEW, remaining_qty = r - d
+ *             (what still rests), filled_qty 0, fill_count 0, reason NONE. The status tells the two
+ *             outcomes apart; the quantity removed is d here.
+ * A REDUCE never rests and admission control does not count it. There is no increase and no price change:
+ * those lose time priority by definition and stay "cancel + new order". */
+#define ME_KIND_REDUCE ((uint8_t)0x0D)
 
 /* Slots per FIFO chunk (one wave-wide load of a level's queue). */
 #define ME_CHUNK_SLOTS 16
@@ -151,8 +168,8 @@ typedef struct me_config {
  * Checked on the device: a violation fails the batch with ME_E_INVALID. */
 typedef struct me_order_soa {
   const uint64_t* seq;      /* numeric OID of the record */
-  const int64_t* price_q4;  /* NEW: normalized Q4 price (ignored for MARKET); CANCEL: target seq */
-  const int32_t* qty;       /* NEW: quantity (wire int32, proto:44); CANCEL: ignored */
+  const int64_t* price_q4;  /* NEW: normalized Q4 price (ignored for MARKET); CANCEL, REDUCE: target seq */
+  const int32_t* qty;       /* NEW: quantity (wire int32, proto:44); CANCEL: ignored; REDUCE: quantity to take off */
   const uint32_t* symbol;   /* local symbol id */
   const uint8_t* kind;      /* ME_KIND(side, type, op) / ME_KIND_TIF(side, type, op, tif) */
 } me_order_soa;
@@ -167,7 +184,8 @@ typedef struct me_fill {
 } me_fill;
 
 /* Per-record outcome (20 B). For CANCEL records: status CANCELED and remaining_qty = the
- * quantity removed from the book, or REJECTED/UNKNOWN_ORDER. */
+ * quantity removed from the book, or REJECTED/UNKNOWN_ORDER. For REDUCE records: the same, or status NEW
+ * and remaining_qty = what the target still holds (ME_KIND_REDUCE above). */
 typedef struct me_order_result {
   int32_t filled_qty;
   int32_t remaining_qty;  /* GTC / POST_ONLY LIMIT: resting remainder; MARKET, IOC, FOK: discarded remainder */
@@ -411,11 +429,12 @@ int me_timing_read(me_engine* e, double* match_ms, double* pipeline_ms, uint64_t
                    uint64_t* fills, uint64_t* orders);
 
 /* Event counters since me_create: handoffs = symbols the register-window kernel handed to its
- * continuation launch (a far price level, a re-centre, a cancel of a far or very old order). */
+ * continuation launch (a far price level, a re-centre, a cancel of a far or very old order, a FOK,
+ * POST_ONLY or REDUCE record). */
 int me_stats_read(me_engine* e, uint64_t* handoffs);
 /* The same for deep windows (L > 128): hot_handoffs = hot symbols whose walk (k_agg_walk / k_match_hot) gave
  * the rest of a batch to the generic record loop (k_match_hot_cont): a cancel, a price outside the window, a
- * taker while far levels exist, a FOK or POST_ONLY record, no room in the walk's pools. */
+ * taker while far levels exist, a FOK or POST_ONLY record, a REDUCE, no room in the walk's pools. */
 int me_hot_stats_read(me_engine* e, uint64_t* hot_handoffs);
 
 /* Far levels (price levels outside a symbol's window; unbounded since round 5): moves =

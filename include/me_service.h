@@ -209,11 +209,32 @@ typedef struct me_cancel_request {
  * the removed quantity, or REJECTED when the target was not resting on that symbol). */
 int me_service_cancel_order(me_service* s, const me_cancel_request* req, me_order_response* resp);
 
+/* ReduceOrder request (build extension): take `quantity` off a resting order and leave it where it is in
+ * its price level's queue (me_engine.h ME_KIND_REDUCE; an increase or a price change stays "cancel + new
+ * order"). */
+typedef struct me_reduce_request {
+  const char* client_id;
+  const char* symbol;
+  const char* order_id; /* "OID-<n>" of the order to reduce */
+  int32_t quantity;     /* the quantity to take off, > 0 */
+} me_reduce_request;
+
+/* CancelOrder's contract with one more in-band check after "symbol is required": "quantity must be > 0"
+ * (SubmitOrder's text). The same owner rule, no OID consumed, success=1 with order_id = the TARGET's id.
+ * The outcome arrives as an OrderUpdate after the flush: when `quantity` is below what the target holds,
+ * one update for the TARGET to its owner with the target's own status (NEW if it never traded, else
+ * PARTIALLY_FILLED), fill price and quantity 0 and remaining_quantity = what still rests; when it covers
+ * the target, exactly a cancel's CANCELED (remaining = removed qty); REJECTED to the requester when the
+ * target was not resting on that symbol. The orders row keeps its status and its remaining_quantity drops
+ * by `quantity`; a restart rebuilds the book from it, so the order comes back reduced and in its place. */
+int me_service_reduce_order(me_service* s, const me_reduce_request* req, me_order_response* resp);
+
 /* OrderUpdate (proto:71-91). Events per flushed record, in slice order: for each fill the maker's
  * update then the taker's (fill price/qty, remaining after the fill, PARTIALLY_FILLED / FILLED);
  * then a closing taker update when no fill closed it (NEW resting, CANCELED market / IOC remainder or
  * FOK kill, REJECTED — a POST_ONLY that would cross included); a cancel record emits CANCELED
- * (remaining = removed qty) or REJECTED for its target. */
+ * (remaining = removed qty) or REJECTED for its target; a reduce record the same, or its target's own
+ * status with the reduced remainder (me_service_reduce_order). */
 typedef struct me_order_update {
   char order_id[32];
   char client_id[64];

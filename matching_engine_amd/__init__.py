@@ -5,7 +5,7 @@ this package is the thin Python view used by tests and bench.py. Build: ``make -
 """
 from ._abi import (  # noqa: F401
     FILL_DTYPE, RESULT_DTYPE, LEVEL_DTYPE, BOOK_ENTRY_DTYPE, LIB_PATH, kind, load,
-    SIDE_BUY, SIDE_SELL, SIDE_UNSPECIFIED, TYPE_LIMIT, TYPE_MARKET, OP_NEW, OP_CANCEL,
+    SIDE_BUY, SIDE_SELL, SIDE_UNSPECIFIED, TYPE_LIMIT, TYPE_MARKET, OP_NEW, OP_CANCEL, OP_REDUCE, KIND_REDUCE,
     ST_NEW, ST_PARTIALLY_FILLED, ST_FILLED, ST_CANCELED, ST_REJECTED,
     RJ_NONE, RJ_BAD_QTY, RJ_BAD_SIDE, RJ_OUT_OF_WINDOW, RJ_BAD_SYMBOL, RJ_UNKNOWN_ORDER, RJ_BAD_SEQ,
     RJ_CAPACITY, RJ_WOULD_CROSS, RJ_BAD_TIF, TIF_GTC, TIF_IOC, TIF_FOK, TIF_POST_ONLY,

@@ -18,6 +18,10 @@ LIB_PATH = os.environ.get("ME_ENGINE_LIB") or os.path.join(_HERE, "libme_engine.
 SIDE_UNSPECIFIED, SIDE_BUY, SIDE_SELL = 0, 1, 2
 TYPE_LIMIT, TYPE_MARKET = 0, 1
 OP_NEW, OP_CANCEL = 0, 1
+# A REDUCE has no ME_OP_* value of its own: it is a CANCEL record with the type bit set (ME_KIND_REDUCE).
+# OP_REDUCE is kind()'s spelling of that: its bit 1 becomes the type bit, so kind(side, op=OP_REDUCE) & 0x0C == 0x0C.
+OP_REDUCE = 3
+KIND_REDUCE = 0x0D
 ST_NEW, ST_PARTIALLY_FILLED, ST_FILLED, ST_CANCELED, ST_REJECTED = 0, 1, 2, 3, 4
 RJ_NONE, RJ_BAD_QTY, RJ_BAD_SIDE, RJ_OUT_OF_WINDOW, RJ_BAD_SYMBOL, RJ_UNKNOWN_ORDER, RJ_BAD_SEQ, RJ_CAPACITY = range(8)
 RJ_WOULD_CROSS, RJ_BAD_TIF = 8, 9
@@ -27,8 +31,8 @@ CHUNK_SLOTS = 16
 
 
 def kind(side: int, otype: int = TYPE_LIMIT, op: int = OP_NEW, tif: int = TIF_GTC) -> int:
-    """ME_KIND_TIF(side, type, op, tif) (ME_KIND with tif = 0)."""
-    return (side & 3) | ((otype & 1) << 2) | ((op & 1) << 3) | ((tif & 3) << 4)
+    """ME_KIND_TIF(side, type, op, tif) (ME_KIND with tif = 0); op = OP_REDUCE sets bits 3 and 2."""
+    return (side & 3) | (((otype | (op >> 1)) & 1) << 2) | ((op & 1) << 3) | ((tif & 3) << 4)
 
 
 # ---- structs ---------------------------------------------------------------------------------
@@ -250,6 +254,15 @@ class MeCancelRequest(C.Structure):
     ]
 
 
+class MeReduceRequest(C.Structure):
+    _fields_ = [
+        ("client_id", C.c_char_p),
+        ("symbol", C.c_char_p),
+        ("order_id", C.c_char_p),
+        ("quantity", C.c_int32),
+    ]
+
+
 class MeOrderUpdate(C.Structure):
     _fields_ = [
         ("order_id", C.c_char * 32),
@@ -382,6 +395,7 @@ PROTOTYPES.update({
     "me_service_order_book": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ),
                                         C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ)]),
     "me_service_cancel_order": (C.c_int, [_P, C.POINTER(MeCancelRequest), C.POINTER(MeOrderResponse)]),
+    "me_service_reduce_order": (C.c_int, [_P, C.POINTER(MeReduceRequest), C.POINTER(MeOrderResponse)]),
     "me_service_market_data": (C.c_int, [_P, C.c_char_p, C.POINTER(MeMarketData)]),
     "me_service_market_subscribe": (C.c_int, [_P, C.c_int]),
     "me_service_market_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeMarketUpdate), _SZ, C.POINTER(_SZ)]),

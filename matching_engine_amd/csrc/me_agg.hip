@@ -2503,14 +2503,16 @@ __device__ __forceinline__ void gw_prepare_cx(GwBuf& B, const GwBuf& Bp, GwCx& X
     const long long opx = stg.px[sl];
     const int oq = v ? stg.qty[sl] : 0;
     const uint32_t okd = v ? stg.ok[sl] >> BK_KIND_SHIFT : 0u;
-    const bool cancel = v && ((okd >> 3) & 1u);
+    // a REDUCE (bits 3 and 2) is no cancel here: a_classify leaves it uncovered, so the walk stops at it
+    // and the symbol goes to the continuation; it gets no LW_CX and no target lookup
+    const bool cancel = v && (okd & 12u) == 8u, cxr = v && ((okd >> 3) & 1u);
     uint32_t rj;
     int olm;
     const bool cov = a_classify(v, oseq, opx, oq, okd, base, L, nfar0, nfar1, rj, olm);
     const unsigned long long fastm = __ballot(cov || cancel);
-    const long long qs = rli64(wave_incl_scan(cancel ? 0ll : (long long)(uint32_t)max(oq, 0)), 63);
+    const long long qs = rli64(wave_incl_scan(cxr ? 0ll : (long long)(uint32_t)max(oq, 0)), 63);
     B.cw[blk + lane] = cancel ? LW_CX : lw_cw(okd, olm, rj, L);
-    B.oq[blk + lane] = cancel ? 0 : oq;
+    B.oq[blk + lane] = cxr ? 0 : oq;
     B.oi[blk + lane] = oi;
     if (lane == 0) {
       B.fastm[blk >> 6] = fastm;

@@ -304,10 +304,12 @@ __device__ bool far_rest(C& c, uint32_t k, long long p, unsigned long long seq, 
 // Cancel the live order in slot `slot` of chunk ch (quantity q) of the far level at price p, side k.
 // qv: the chunk's live quantities (lanes 0..15, 0 elsewhere); nxt / prv: its FIFO links. The caller
 // verified owner, seq and liveness. A chunk left without live orders is unlinked and freed; a level
-// left empty leaves the array.
+// left empty leaves the array. d: the quantity to take off (a cancel: INT32_MAX, "all"). d < q is a partial
+// REDUCE: after the same level search the slot and the far level's total shrink by d and the
+// chunk, the FIFO and the array stay as they are. Returns q.
 template <class C>
 __device__ uint32_t far_cancel(C& c, uint32_t k, long long p, uint32_t ch, uint32_t slot, int q, int qv,
-                               uint32_t nxt, uint32_t prv) {
+                               uint32_t nxt, uint32_t prv, int d) {
   const int lane = lane_id();
   const gptr<FarLevel> a = far_arr(c, k);
   const gptr<Chunk> chunks = c.fchunks();
@@ -322,6 +324,12 @@ __device__ uint32_t far_cancel(C& c, uint32_t k, long long p, uint32_t ch, uint3
   if (e.price != p) {
     c.ferr(ERR_INCONSISTENT);
     return 0;
+  }
+  if (d < q) {
+    if (lane == 0) chunks[ch].qty[slot] = q - d;
+    e.total -= d;
+    far_put(a, pos, e);
+    return (uint32_t)q;
   }
   if (lane == 0) chunks[ch].qty[slot] = 0;
   e.total -= q;

@@ -826,10 +826,12 @@ __device__ __forceinline__ void cancel_window(WaveCtx& c, int lvl, uint32_t ch, 
   c.resting_delta -= 1;
 }
 
-// Cancel the live resting order `tgt` of this symbol. Returns the removed qty, 0 if not live. The
+// Take d off the live resting order `tgt` of this symbol (a CANCEL passes INT32_MAX, "all"). Returns the
+// quantity r it held, 0 if not live. d >= r removes the order; d < r (a partial REDUCE)
+// leaves it in its slot holding r - d: nothing is unlinked, the resting count stays. The
 // seq ring names its slot unless a later seq overwrote the entry, in which case an order older than
 // the horizon is in the old-order table; every candidate slot is verified (owner, seq, qty > 0).
-__device__ __forceinline__ int cancel_order(WaveCtx& c, unsigned long long tgt) {
+__device__ __forceinline__ int cancel_order(WaveCtx& c, unsigned long long tgt, int d) {
   const BookDev& bk = c.bk;
   const int lane = lane_id();
   const bool act = lane < ME_C;
@@ -858,7 +860,20 @@ __device__ __forceinline__ int cancel_order(WaveCtx& c, unsigned long long tgt) 
         const int q = rli32(qv, (int)slot);
         if (q <= 0) return 0;
         const uint32_t nxt = rl32(hd.next, 0), prv = rl32(hd.prev, 0);
-        if (!inw) return (int)far_cancel(c, price < c.base ? 0u : 1u, price, ch, slot, q, qv, nxt, prv);
+        if (!inw) return (int)far_cancel(c, price < c.base ? 0u : 1u, price, ch, slot, q, qv, nxt, prv, d);
+        if (d < q) {  // partial: the slot and the level total shrink, nothing else changes
+          Level L = c.lad.get(lvl);
+          L.total -= d;
+          if (E) cache_mark_dirty(c, lvl);
+          if (lane == 0) {
+            if (E)
+              E->qty[slot] = q - d;
+            else
+              cq_at(bk.chunks, (size_t)ch * ME_C + slot) = q - d;
+          }
+          c.lad.set(lvl, L);
+          return q;
+        }
         cancel_window(c, lvl, ch, slot, q, qv, nxt, prv, E);
         return q;
       }
@@ -1135,8 +1150,12 @@ __device__ __forceinline__ RecOut generic_record(WaveCtx& c, unsigned long long 
   const uint32_t tif = kd_tif(kind);
   const unsigned long long fstart = c.wptr;
   if (cancel) {
-    const int got = cancel_order(c, (unsigned long long)px);
+    const bool reduce = market;  // bits 3 and 2: a REDUCE takes q off its target, a CANCEL ignores q
+    if (reduce && q <= 0) return rec_out(0, 0, 0, ME_ST_REJECTED, ME_RJ_BAD_QTY, fstart);
+    const int d = reduce ? q : INT32_MAX;
+    const int got = cancel_order(c, (unsigned long long)px, d);
     STAMP_ADD(c, PH_CANCEL);
+    if (got > d) return rec_out(0, got - d, 0, ME_ST_NEW, ME_RJ_NONE, fstart);  // what still rests
     return got > 0 ? rec_out(0, got, 0, ME_ST_CANCELED, ME_RJ_NONE, fstart)
                    : rec_out(0, 0, 0, ME_ST_REJECTED, ME_RJ_UNKNOWN_ORDER, fstart);
   }

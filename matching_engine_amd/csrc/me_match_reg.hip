@@ -536,11 +536,15 @@ __device__ __forceinline__ bool reg_rest(RegCtx& c, int lvl, unsigned long long 
 // kSlow = false (k_match_reg<false>): a window order named by its ring entry is cancelled here; every
 // other case (a far level, a stale ring entry of an order older than the horizon) returns HANDOFF
 // before anything changed, and the continuation launch (kSlow = true) does the whole cancel.
+// d: the quantity to take off (a CANCEL passes INT32_MAX, "all"). d below the order's quantity is a partial
+// REDUCE: the slot and the level total shrink by d and nothing else changes; the return is
+// still the quantity the order held. Only the continuation executes one (make_cw hands a REDUCE off), so
+// the common launch carries no code for it.
 constexpr uint32_t HANDOFF = 0xFFFFFFFFu;
 // gh: the ring entry read for the whole block at its start (NIL: none); a slot it names is verified like
 // any other, and one that does not hold tgt sends the cancel to the ring as if there were no hint.
 template <bool kSlow>
-__device__ __forceinline__ uint32_t reg_cancel(RegCtx& c, unsigned long long tgt, uint32_t gh) {
+__device__ __forceinline__ uint32_t reg_cancel(RegCtx& c, unsigned long long tgt, uint32_t gh, uint32_t d) {
   const int lane = lane_id();
   const bool act = lane < ME_C;
   if (tgt == 0ull) return 0;
@@ -581,10 +585,23 @@ __device__ __forceinline__ uint32_t reg_cancel(RegCtx& c, unsigned long long tgt
         if (q <= 0) return 0;
         const uint32_t nxt = rl32(hdr.next, 0), prv = rl32(hdr.prev, 0);
         if (ME_UNLIKELY(!inw)) {  // a far level (me_far.hpp)
-          if constexpr (kSlow)
-            return far_cancel(c, prc < rli64(c.base, 0) ? 0u : 1u, prc, ch, slot, q, qv, nxt, prv);
-          else
+          if constexpr (kSlow) {
+            return far_cancel(c, prc < rli64(c.base, 0) ? 0u : 1u, prc, ch, slot, q, qv, nxt, prv, (int)d);
+          } else {
             return HANDOFF;
+          }
+        }
+        if constexpr (kSlow) {
+          if (ME_UNLIKELY(d < (uint32_t)q)) {  // partial: the order keeps its slot and its place
+            if (lane == 0) {
+              if (in_cache)
+                c.M->cq[ce(lvl)][slot] = q - (int)d;
+              else
+                c.chunks[ch].qty[slot] = q - (int)d;
+            }
+            tot_add(c, lvl, -(long long)d);
+            return (uint32_t)q;
+          }
         }
         const uint32_t t = c.tl.get(lvl);
         const uint32_t h = hv == NIL ? NIL : (hv & ~HC);
@@ -1366,7 +1383,9 @@ __device__ __forceinline__ uint32_t make_cw(long long opx, uint32_t kd, long lon
   const bool far = !cancel && (market || (buy ? above : (!inw && !above)));
   const bool out = !market && !cancel && !inw;
   const uint32_t tif = cancel ? 0u : kd_tif(kd);
-  const bool hand = out || (market && ((far_nz >> (buy ? 1 : 0)) & 1u)) || tif >= (uint32_t)ME_TIF_FOK;
+  // (a REDUCE, bits 3 and 2, is the continuation's: no reduce code in the common launch)
+  const bool hand = cancel ? market
+                           : out || (market && ((far_nz >> (buy ? 1 : 0)) & 1u)) || tif >= (uint32_t)ME_TIF_FOK;
   return (uint32_t)(lim + 1) | (buy ? CW_BUY : 0u) | (market ? CW_MKT : 0u) | (cancel ? CW_CXL : 0u) |
          (far ? CW_FAR : 0u) | (out ? CW_OUT : 0u) | (hand ? CW_HAND : 0u) |
          (!cancel && kd_norest(kd) ? CW_NR : 0u) | (tif == (uint32_t)ME_TIF_FOK ? CW_FOK : 0u) |
@@ -1696,7 +1715,9 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
         const uint32_t side = kd & 3u;
         const bool cancel = (kd >> 3) & 1u;
         rj = ME_RJ_NONE;
-        if (!cancel) {
+        if (cancel) {
+          if ((kd & 4u) && oq <= 0) rj = ME_RJ_BAD_QTY;  // a REDUCE takes qty off its target; a CANCEL ignores it
+        } else {
           if (oq <= 0)
             rj = ME_RJ_BAD_QTY;
           else if (side != ME_SIDE_BUY && side != ME_SIDE_SELL)
@@ -1747,7 +1768,9 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
           const unsigned long long tgt = (unsigned long long)rli64(opx_, k);
           // (a target an earlier record of this block rested as: its block-start ring entry is stale)
           const bool inblk = __ballot(lane < k && oseq_ == tgt) != 0ull;
-          outq = reg_cancel<kSlow>(c, tgt, inblk ? NIL : rl32(gpre, k));
+          // the quantity to take off: a REDUCE's own (continuation only), else all
+          const uint32_t dq = kSlow && (ctl & CW_MKT) ? (uint32_t)rli32(oq_, k) : (uint32_t)INT32_MAX;
+          outq = reg_cancel<kSlow>(c, tgt, inblk ? NIL : rl32(gpre, k), dq);
           if (!kSlow && ME_UNLIKELY(outq == HANDOFF)) {
             stop = (uint32_t)k;
             handoff = true;
@@ -1843,8 +1866,11 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
           r.status = ME_ST_REJECTED;
         } else if (cancel) {
           r.filled_qty = 0;
-          r.remaining_qty = (int)out_q;
-          r.status = out_q ? ME_ST_CANCELED : ME_ST_REJECTED;
+          // a partial REDUCE (out_q, the quantity the target held, above its qty): NEW, what still rests
+          // (the continuation's: the common launch hands a REDUCE off before it gets a result)
+          const bool part = kSlow && (kd_ & 4u) && out_q > (uint32_t)oq_;
+          r.remaining_qty = part ? (int)out_q - oq_ : (int)out_q;
+          r.status = part ? ME_ST_NEW : out_q ? ME_ST_CANCELED : ME_ST_REJECTED;
           r.reason = out_q ? ME_RJ_NONE : ME_RJ_UNKNOWN_ORDER;
         } else {
           const int rem = oq_ - (int)out_q;

@@ -140,8 +140,10 @@ struct Pending {
   std::string client;
   std::string symbol;
   int32_t side;
-  bool cancel;      // CancelOrder record (build extension): target = the order it removes
+  bool cancel;      // CancelOrder / ReduceOrder record (build extensions): target = the order it names
   uint64_t target;
+  bool reduce = false;  // of a cancel-type record: a ReduceOrder (ME_KIND_REDUCE), taking d off its target
+  int32_t d = 0;
 };
 
 // The symbol id of a cancel whose symbol holds no book: out of the backend's range, so the record is
@@ -194,6 +196,7 @@ struct Live {
   std::string symbol;
   int32_t remaining;
   uint32_t sid;  // its book (reference-counted: a book with live orders is never handed over)
+  bool filled = false;  // it has traded: a reduce reports it PARTIALLY_FILLED, else NEW
 };
 
 constexpr size_t kMaxQueuedUpdates = size_t(1) << 24;  // oldest events are dropped beyond this
@@ -279,6 +282,7 @@ struct me_service {
   sqlite3_stmt* st_upd = nullptr;
   sqlite3_stmt* st_fill = nullptr;
   sqlite3_stmt* st_maker = nullptr;
+  sqlite3_stmt* st_reduce = nullptr;  // an earlier slice's order, reduced in place: remaining only
   sqlite3_stmt* st_ins_k = nullptr;   // kRows-row INSERT INTO orders
   sqlite3_stmt* st_fill_k = nullptr;  // kRows-row INSERT INTO fills
   bool failed = false;  // the engine lost a slice it had accepted: nothing more can be matched
@@ -295,9 +299,9 @@ struct me_service {
 };
 
 static void close_db(me_service* s) {
-  for (sqlite3_stmt* st : {s->st_ins, s->st_upd, s->st_fill, s->st_maker, s->st_ins_k, s->st_fill_k})
+  for (sqlite3_stmt* st : {s->st_ins, s->st_upd, s->st_fill, s->st_maker, s->st_reduce, s->st_ins_k, s->st_fill_k})
     if (st) g_sql.finalize(st);
-  s->st_ins = s->st_upd = s->st_fill = s->st_maker = s->st_ins_k = s->st_fill_k = nullptr;
+  s->st_ins = s->st_upd = s->st_fill = s->st_maker = s->st_reduce = s->st_ins_k = s->st_fill_k = nullptr;
   if (s->db) g_sql.close(s->db);
   s->db = nullptr;
 }
@@ -346,6 +350,7 @@ static bool open_db(me_service* s, const char* path, std::string& err) {
   const char* maker =
       "UPDATE orders SET remaining_quantity=remaining_quantity-?, status=CASE WHEN remaining_quantity-?=0 "
       "THEN 2 ELSE 1 END, updated_ts=? WHERE order_id=?";
+  const char* reduce = "UPDATE orders SET remaining_quantity=remaining_quantity-?, updated_ts=? WHERE order_id=?";
   // multi-row forms: one statement step per kRows rows
   auto rows = [](const char* head, const char* tuple) {
     std::string q(head);
@@ -361,6 +366,7 @@ static bool open_db(me_service* s, const char* path, std::string& err) {
          chk(g_sql.prepare_v2(s->db, upd, -1, &s->st_upd, nullptr), "prepare update") &&
          chk(g_sql.prepare_v2(s->db, fill, -1, &s->st_fill, nullptr), "prepare fill") &&
          chk(g_sql.prepare_v2(s->db, maker, -1, &s->st_maker, nullptr), "prepare maker") &&
+         chk(g_sql.prepare_v2(s->db, reduce, -1, &s->st_reduce, nullptr), "prepare reduce") &&
          chk(g_sql.prepare_v2(s->db, ins_k.c_str(), -1, &s->st_ins_k, nullptr), "prepare insert rows") &&
          chk(g_sql.prepare_v2(s->db, fill_k.c_str(), -1, &s->st_fill_k, nullptr), "prepare fill rows");
 }
@@ -424,7 +430,7 @@ static int flush_closed(me_service* s, bool take_open, size_t limit, struct Flus
 static bool load_resting(me_service* s, std::string& err) {
   sqlite3_stmt* q = nullptr;
   if (!sql_ok(g_sql.prepare_v2(s->db,
-                               "SELECT order_id, client_id, symbol, side, price, remaining_quantity FROM orders "
+                               "SELECT order_id, client_id, symbol, side, price, remaining_quantity, status FROM orders "
                                "WHERE status IN (0, 1) AND remaining_quantity > 0 AND order_id LIKE 'OID-%' "
                                "ORDER BY CAST(SUBSTR(order_id, 5) AS INTEGER)",
                                -1, &q, nullptr))) {
@@ -475,7 +481,8 @@ static bool load_resting(me_service* s, std::string& err) {
     cur.meta.push_back(Pending{cl ? cl : "", symbol, side, false, 0});
     {
       std::lock_guard<std::mutex> lv(s->live_mu);
-      s->live[oid] = Live{cl ? cl : "", symbol, (int32_t)rem, sid};
+      // (PARTIALLY_FILLED in the row: it traded in an earlier run)
+      s->live[oid] = Live{cl ? cl : "", symbol, (int32_t)rem, sid, g_sql.column_int64(q, 6) == ME_ST_PARTIALLY_FILLED};
     }
     ref_add(s, sid, 1);
     s->recovered++;
@@ -846,19 +853,26 @@ static uint64_t parse_oid(const char* s) {
   return v;
 }
 
-extern "C" int me_service_cancel_order(me_service* s, const me_cancel_request* r, me_order_response* resp) {
+// CancelOrder and ReduceOrder: the same checks, owner rule, stream position and record, apart from the kind
+// byte and the quantity (reduce: take d off the target; a cancel's qty is 0 and ignored).
+static int cancel_or_reduce(me_service* s, const char* client_id, const char* symbol_c, const char* order_id,
+                            bool reduce, int32_t d, me_order_response* resp) {
   memset(resp, 0, sizeof(*resp));
-  const char* symbol = r->symbol ? r->symbol : "";
+  const char* symbol = symbol_c ? symbol_c : "";
   if (!symbol[0]) {
     put(resp->error_message, sizeof resp->error_message, "symbol is required");
     return 0;
   }
-  const uint64_t target = parse_oid(r->order_id);
+  if (reduce && d <= 0) {  // SubmitOrder's check and text (:72-77)
+    put(resp->error_message, sizeof resp->error_message, "quantity must be > 0");
+    return 0;
+  }
+  const uint64_t target = parse_oid(order_id);
   if (!target) {
     put(resp->error_message, sizeof resp->error_message, "order_id is invalid");
     return 0;
   }
-  const std::string client = r->client_id ? r->client_id : "";
+  const std::string client = client_id ? client_id : "";
   const std::string sym(symbol);
   std::lock_guard<std::mutex> lk(s->mu);
   {  // only the order's owner may cancel it
@@ -879,9 +893,18 @@ extern "C" int me_service_cancel_order(me_service* s, const me_cancel_request* r
   put(resp->order_id, sizeof resp->order_id, "OID-" + std::to_string(target));
   resp->success = 1;
   ref_add(s, sid, 1);
-  append(s, id, (int64_t)target, 0, sid, ME_KIND(ME_SIDE_BUY, ME_TYPE_LIMIT, ME_OP_CANCEL),
-         Pending{client, sym, 0, true, target});
+  append(s, id, (int64_t)target, reduce ? d : 0, sid,
+         reduce ? ME_KIND_REDUCE : ME_KIND(ME_SIDE_BUY, ME_TYPE_LIMIT, ME_OP_CANCEL),
+         Pending{client, sym, 0, true, target, reduce, reduce ? d : 0});
   return 0;
+}
+
+extern "C" int me_service_cancel_order(me_service* s, const me_cancel_request* r, me_order_response* resp) {
+  return cancel_or_reduce(s, r->client_id, r->symbol, r->order_id, false, 0, resp);
+}
+
+extern "C" int me_service_reduce_order(me_service* s, const me_reduce_request* r, me_order_response* resp) {
+  return cancel_or_reduce(s, r->client_id, r->symbol, r->order_id, true, r->quantity, resp);
 }
 
 extern "C" size_t me_service_pending(const me_service* s) {
@@ -943,7 +966,13 @@ static void emit_updates(me_service* s, const Slice& sl, const me_order_result* 
       const me_order_result& r = res[i];
       if (m.cancel) {
         auto it = s->live.find(m.target);
-        if (r.status == ME_ST_CANCELED && it != s->live.end()) {
+        if (m.reduce && r.status == ME_ST_NEW && it != s->live.end()) {
+          // reduced in place: the target's own status, to its owner; it stays live and keeps its book
+          Live& tg = it->second;
+          tg.remaining = r.remaining_qty;
+          push_update(s, m.target, tg.client, tg.symbol, tg.filled ? ME_ST_PARTIALLY_FILLED : ME_ST_NEW, 0, 0,
+                      r.remaining_qty);
+        } else if (r.status == ME_ST_CANCELED && it != s->live.end()) {
           push_update(s, m.target, it->second.client, it->second.symbol, ME_ST_CANCELED, 0, 0, r.remaining_qty);
           live_erase(it);
         } else {
@@ -961,6 +990,7 @@ static void emit_updates(me_service* s, const Slice& sl, const me_order_result* 
         if (it != s->live.end()) {
           Live& mk = it->second;
           mk.remaining -= fl.qty;
+          mk.filled = true;
           push_update(s, fl.maker_seq, mk.client, mk.symbol,
                       mk.remaining > 0 ? ME_ST_PARTIALLY_FILLED : ME_ST_FILLED, fl.price_q4, fl.qty, mk.remaining);
           if (mk.remaining <= 0) live_erase(it);
@@ -983,8 +1013,9 @@ static void emit_updates(me_service* s, const Slice& sl, const me_order_result* 
         auto it = s->live.find(oid);
         if (it != s->live.end()) {
           it->second.remaining = r.remaining_qty;
+          it->second.filled |= r.fill_count != 0;
         } else {
-          s->live[oid] = Live{m.client, m.symbol, r.remaining_qty, sl.sid[i]};
+          s->live[oid] = Live{m.client, m.symbol, r.remaining_qty, sl.sid[i], r.fill_count != 0};
           ref_add(s, sl.sid[i], 1);
         }
       } else {
@@ -1042,6 +1073,7 @@ static bool persist(me_service* s, const Slice& sl, const me_order_result* res, 
   std::vector<int32_t> fst(n), frem(n);
   std::unordered_map<uint64_t, long long> ext_fill;       // earlier order -> quantity filled now
   std::vector<std::pair<uint64_t, int32_t>> ext_cancel;   // earlier order -> quantity the cancel removed
+  std::vector<std::pair<uint64_t, int32_t>> ext_reduce;   // earlier order -> quantity a partial reduce took off
   auto find = [&](uint64_t q) -> long {  // row of order q in this slice (seqs ascend), or -1
     auto it = std::lower_bound(sl.seq.begin(), sl.seq.end(), q);
     if (it == sl.seq.end() || *it != q) return -1;
@@ -1052,6 +1084,14 @@ static bool persist(me_service* s, const Slice& sl, const me_order_result* res, 
   for (size_t i = 0; i < n; ++i) {
     const Pending& m = sl.meta[i];
     if (m.cancel) {
+      if (m.reduce && res[i].status == ME_ST_NEW) {  // reduced in place: the remainder shrinks, the status stays
+        const long j = find(m.target);
+        if (j >= 0)
+          frem[j] -= m.d;
+        else
+          ext_reduce.emplace_back(m.target, m.d);
+        continue;
+      }
       if (res[i].status != ME_ST_CANCELED) continue;
       const long j = find(m.target);
       if (j >= 0) {
@@ -1132,7 +1172,16 @@ static bool persist(me_service* s, const Slice& sl, const me_order_result* res, 
       step(s->st_ins, "insert order");
     }
   }
-  // ---- earlier slices' rows: fills first (an order is filled before it can be canceled), then cancels
+  // ---- earlier slices' rows: partial reduces first (remaining only; fills and reduces of one order commute
+  // in the remainder, but the maker statement derives FILLED from "remaining reaches 0", which holds only with
+  // the reduces already in), then fills (an order is filled before it can be canceled), then cancels
+  for (size_t k = 0; ok && k < ext_reduce.size(); ++k) {
+    const std::string toid = "OID-" + std::to_string(ext_reduce[k].first);
+    g_sql.bind_int64(s->st_reduce, 1, ext_reduce[k].second);
+    g_sql.bind_int64(s->st_reduce, 2, ts);
+    g_sql.bind_text(s->st_reduce, 3, toid.c_str(), -1, SQLITE_TRANSIENT);
+    step(s->st_reduce, "reduce order");
+  }
   for (auto it = ext_fill.begin(); ok && it != ext_fill.end(); ++it) {
     const std::string moid = "OID-" + std::to_string(it->first);
     g_sql.bind_int64(s->st_maker, 1, it->second);

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (FILL_DTYPE, LEVEL_DTYPE, RESULT_DTYPE, MeBookOrder, MeCancelRequest, MeOrderRequest,
+from ._abi import (FILL_DTYPE, LEVEL_DTYPE, RESULT_DTYPE, MeBookOrder, MeCancelRequest, MeOrderRequest, MeReduceRequest,
                    MeOrderResponse, MeMarketData, MeMarketUpdate, MeDepthBook, MeOrderUpdate, ptr)
 
 
@@ -87,6 +87,17 @@ class MatchingEngineService:
         req = MeCancelRequest(client_id.encode(), symbol.encode(), order_id.encode())
         resp = MeOrderResponse()
         self.lib.me_service_cancel_order(self.h, C.byref(req), C.byref(resp))
+        return {"order_id": resp.order_id.decode(), "success": bool(resp.success),
+                "error_message": resp.error_message.decode(), "grpc_status": resp.grpc_status}
+
+    def reduce_order(self, client_id, symbol, order_id, quantity) -> dict:
+        """ReduceOrder (build extension, me_service.h): queue a reduction of a resting order's quantity by
+        `quantity`; the order keeps its place in the queue. The outcome arrives as an OrderUpdate after the
+        flush: the target's own status with the smaller remaining_quantity, or CANCELED when `quantity`
+        covers what was left."""
+        req = MeReduceRequest(client_id.encode(), symbol.encode(), order_id.encode(), quantity)
+        resp = MeOrderResponse()
+        self.lib.me_service_reduce_order(self.h, C.byref(req), C.byref(resp))
         return {"order_id": resp.order_id.decode(), "success": bool(resp.success),
                 "error_message": resp.error_message.decode(), "grpc_status": resp.grpc_status}
 
