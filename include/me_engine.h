@@ -466,6 +466,47 @@ int me_admission_read(me_engine* e, uint64_t* resting, uint64_t* bound, uint64_t
  * a slice all-or-none (cluster.ShardedMatcher) ask every engine first. */
 int me_admission_check(me_engine* e, uint64_t n_rest, int* ok);
 
+/* ---- raw export of the resident book: DIAGNOSTIC (tests/book_audit.py) -----------------
+ * Not part of the service boundary and no reference counterpart: the device arrays of the book exactly as
+ * the kernels left them, for an offline audit of their redundant fields. Both calls first bring the pipeline
+ * to the point me_book_dump does (every enqueued batch matched, the stream idle); the copy is a plain
+ * device-to-host copy, no kernel runs. The layout of the entries is me_layout.hpp's, not an ABI: me_debug_info
+ * reports sizeof of every exported struct so that a reader fails loudly when one drifts. */
+enum {
+  ME_DBG_LEVELS = 0, /* Level [S][L] */
+  ME_DBG_OCC,        /* u64 [S][L / 64] */
+  ME_DBG_TEND,       /* u8 [S][L] */
+  ME_DBG_SYM,        /* SymState [S] */
+  ME_DBG_CHUNKS,     /* Chunk [nchunks] */
+  ME_DBG_FCACHE,     /* u32 [S][fcache_row] */
+  ME_DBG_LOC,        /* u32 [ring_mask + 1] */
+  ME_DBG_OLD,        /* OldEnt [old_mask + 1] */
+  ME_DBG_SQ,         /* SeqState [2]; the matchers read entry me_debug_info.sq_idx */
+  ME_DBG_FAR,        /* FarLevel [far_entries] */
+  ME_DBG_FDIR,       /* FarDir [S][2] */
+  ME_DBG_FAR_CTL,    /* u64 [n_far_ctl] */
+  ME_DBG_CHUNK_TOP,  /* u32 [1] */
+  ME_DBG_RECL,       /* u32 [nchunks] */
+  ME_DBG_CPOOL,      /* u32 [n_cpool] */
+  ME_DBG_STATS,      /* u64 [n_stats] */
+  ME_DBG_ERR,        /* u32 [1] */
+  ME_DBG_ARRAYS
+};
+typedef struct me_debug_info {
+  uint64_t num_symbols, levels, level_words, nchunks, ring_mask, old_mask;
+  uint64_t far_levels;  /* inline far entries per (symbol, side) */
+  uint64_t far_half;    /* entries of each arena half */
+  uint64_t far_inline;  /* end of the inline regions = start of half 0 */
+  uint64_t far_entries; /* far_inline + 2 * far_half */
+  uint64_t sq_idx, chunk_slots, fcache_row, n_far_ctl, n_cpool, n_stats;
+  uint64_t sizeof_level, sizeof_symstate, sizeof_chunk, sizeof_farlevel, sizeof_fardir, sizeof_oldent,
+      sizeof_seqstate;
+} me_debug_info;
+int me_debug_layout(me_engine* e, me_debug_info* out);
+/* Array `which` (ME_DBG_*) into dst[0, cap); *bytes (may be NULL) receives its size. cap smaller than the
+ * array: ME_E_INVALID, nothing copied (dst NULL and cap 0 ask for the size alone and return ME_OK). */
+int me_debug_export(me_engine* e, uint32_t which, void* dst, size_t cap, size_t* bytes);
+
 /* Last error text of e (or of the last failed me_create when e == NULL). */
 int me_last_error(const me_engine* e, char* buf, size_t cap);
 

@@ -127,6 +127,55 @@ DEPTH_DTYPE = np.dtype(
 DEPTH_MAX = 32
 assert DEPTH_DTYPE.itemsize == 32
 
+
+# ---- raw export of the resident book (me_debug_layout / me_debug_export: diagnostic) -------------------
+class MeDebugInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "num_symbols", "levels", "level_words", "nchunks", "ring_mask", "old_mask", "far_levels", "far_half",
+        "far_inline", "far_entries", "sq_idx", "chunk_slots", "fcache_row", "n_far_ctl", "n_cpool", "n_stats",
+        "sizeof_level", "sizeof_symstate", "sizeof_chunk", "sizeof_farlevel", "sizeof_fardir", "sizeof_oldent",
+        "sizeof_seqstate")]
+
+
+# me_layout.hpp's structs restated (Engine.debug_export checks every itemsize against me_debug_info)
+DBG_LEVEL_DTYPE = np.dtype([("total", "<i8"), ("head", "<u4"), ("tail", "<u4")])
+DBG_SYM_DTYPE = np.dtype([("base", "<i8"), ("best_bid", "<i4"), ("best_ask", "<i4"), ("free_head", "<u4"),
+                          ("resting", "<u4"), ("nfree", "<u4"), ("nfar", "<u4", (2,)), ("pad", "<u4", (7,))])  # alignas(64): 64 B
+assert (DBG_LEVEL_DTYPE.itemsize, DBG_SYM_DTYPE.itemsize) == (16, 64)
+DBG_CHUNK_DTYPE = np.dtype([("next", "<u4"), ("prev", "<u4"), ("price", "<i8"), ("owner", "<u4"),
+                            ("pad", "<u4", (11,)), ("qty", "<i4", (CHUNK_SLOTS,)), ("seq", "<u8", (CHUNK_SLOTS,))])
+DBG_FAR_DTYPE = np.dtype([("price", "<i8"), ("total", "<i8"), ("head", "<u4"), ("tail", "<u4"), ("tend", "<u4"),
+                          ("pad", "<u4")])
+DBG_FDIR_DTYPE = np.dtype([("off", "<u8"), ("cap", "<u4"), ("pad", "<u4")])
+DBG_OLD_DTYPE = np.dtype([("epoch", "<u4"), ("slot", "<u4"), ("seq", "<u8")])
+DBG_SQ_DTYPE = np.dtype([("horizon", "<u8"), ("last", "<u8"), ("epoch", "<u4"), ("pad", "<u4", (3,))])
+assert (DBG_CHUNK_DTYPE.itemsize, DBG_FAR_DTYPE.itemsize, DBG_FDIR_DTYPE.itemsize, DBG_OLD_DTYPE.itemsize,
+        DBG_SQ_DTYPE.itemsize) == (256, 32, 16, 16, 32)
+# name -> (ME_DBG_* index, dtype, me_debug_info field holding sizeof of the struct or None)
+DBG_ARRAYS = {
+    "levels": (0, DBG_LEVEL_DTYPE, "sizeof_level"),
+    "occ": (1, np.dtype("<u8"), None),
+    "tend": (2, np.dtype("u1"), None),
+    "sym": (3, DBG_SYM_DTYPE, "sizeof_symstate"),
+    "chunks": (4, DBG_CHUNK_DTYPE, "sizeof_chunk"),
+    "fcache": (5, np.dtype("<u4"), None),
+    "loc": (6, np.dtype("<u4"), None),
+    "old": (7, DBG_OLD_DTYPE, "sizeof_oldent"),
+    "sq": (8, DBG_SQ_DTYPE, "sizeof_seqstate"),
+    "far": (9, DBG_FAR_DTYPE, "sizeof_farlevel"),
+    "fdir": (10, DBG_FDIR_DTYPE, "sizeof_fardir"),
+    "far_ctl": (11, np.dtype("<u8"), None),
+    "chunk_top": (12, np.dtype("<u4"), None),
+    "recl": (13, np.dtype("<u4"), None),
+    "cpool": (14, np.dtype("<u4"), None),
+    "stats": (15, np.dtype("<u8"), None),
+    "err": (16, np.dtype("<u4"), None),
+}
+# indices into the exported counter arrays (me_layout.hpp ST_*, FC_*, CP_*)
+DBG_ST_RESTING = 1
+DBG_FC_TOP0, DBG_FC_TOP1, DBG_FC_HALF = 0, 1, 2
+DBG_CP_NRECL, DBG_CP_FRESH = 0, 1
+
 # every symbol include/me_engine.h declares -> (restype, argtypes)
 _P = C.c_void_p
 _SZ = C.c_size_t
@@ -172,6 +221,8 @@ PROTOTYPES = {
     "me_far_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_chunk_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_paths_read": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "me_debug_layout": (C.c_int, [_P, C.POINTER(MeDebugInfo)]),
+    "me_debug_export": (C.c_int, [_P, C.c_uint32, _P, _SZ, C.POINTER(_SZ)]),
     "me_admission_read": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_admission_check": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int)]),
     "me_quotes_enable": (C.c_int, [_P, C.c_uint64]),

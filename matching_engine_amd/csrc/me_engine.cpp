@@ -2190,6 +2190,74 @@ extern "C" int me_chunk_stats(me_engine* e, uint64_t* reclaims, uint64_t* high_w
   return ME_OK;
 }
 
+// ---- raw export of the resident book (diagnostic: tests/book_audit.py) -------------------------------
+extern "C" int me_debug_layout(me_engine* e, me_debug_info* out) {
+  if (!e || !out) return ME_E_INVALID;
+  int rc = me_sync(e);
+  if (rc) return rc;
+  const BookDev& bk = e->bk;
+  memset(out, 0, sizeof *out);
+  out->num_symbols = bk.S;
+  out->levels = bk.L;
+  out->level_words = bk.Lwords;
+  out->nchunks = bk.nchunks;
+  out->ring_mask = bk.ring_mask;
+  out->old_mask = bk.old_mask;
+  out->far_levels = bk.fcap;
+  out->far_half = bk.far_half;
+  out->far_inline = 2ull * bk.S * bk.fcap;
+  out->far_entries = out->far_inline + 2ull * bk.far_half;
+  out->sq_idx = bk.sq_idx;
+  out->chunk_slots = ME_C;
+  out->fcache_row = 64;
+  out->n_far_ctl = FC_N;
+  out->n_cpool = CP_N;
+  out->n_stats = ME_STATS;
+  out->sizeof_level = sizeof(Level);
+  out->sizeof_symstate = sizeof(SymState);
+  out->sizeof_chunk = sizeof(Chunk);
+  out->sizeof_farlevel = sizeof(FarLevel);
+  out->sizeof_fardir = sizeof(FarDir);
+  out->sizeof_oldent = sizeof(OldEnt);
+  out->sizeof_seqstate = sizeof(SeqState);
+  return ME_OK;
+}
+
+extern "C" int me_debug_export(me_engine* e, uint32_t which, void* dst, size_t cap, size_t* bytes) {
+  if (!e) return ME_E_INVALID;
+  if (which >= (uint32_t)ME_DBG_ARRAYS) return e->fail(ME_E_INVALID, "me_debug_export: no such array");
+  int rc = me_sync(e);
+  if (rc) return rc;
+  const BookDev& bk = e->bk;
+  const size_t S = bk.S, L = bk.L;
+  const void* src = nullptr;
+  size_t nb = 0;
+  switch (which) {
+    case ME_DBG_LEVELS: src = bk.levels, nb = S * L * sizeof(Level); break;
+    case ME_DBG_OCC: src = bk.occ, nb = S * bk.Lwords * 8; break;
+    case ME_DBG_TEND: src = bk.tend, nb = S * L; break;
+    case ME_DBG_SYM: src = bk.sym, nb = S * sizeof(SymState); break;
+    case ME_DBG_CHUNKS: src = bk.chunks, nb = (size_t)bk.nchunks * sizeof(Chunk); break;
+    case ME_DBG_FCACHE: src = bk.fcache, nb = S * 64 * sizeof(uint32_t); break;
+    case ME_DBG_LOC: src = bk.loc, nb = (size_t)(bk.ring_mask + 1) * sizeof(uint32_t); break;
+    case ME_DBG_OLD: src = bk.old, nb = (size_t)(bk.old_mask + 1) * sizeof(OldEnt); break;
+    case ME_DBG_SQ: src = bk.sq, nb = 2 * sizeof(SeqState); break;
+    case ME_DBG_FAR: src = bk.far, nb = (size_t)(2ull * S * bk.fcap + 2ull * bk.far_half) * sizeof(FarLevel); break;
+    case ME_DBG_FDIR: src = bk.fdir, nb = 2 * S * sizeof(FarDir); break;
+    case ME_DBG_FAR_CTL: src = bk.far_ctl, nb = FC_N * sizeof(unsigned long long); break;
+    case ME_DBG_CHUNK_TOP: src = bk.chunk_top, nb = sizeof(uint32_t); break;
+    case ME_DBG_RECL: src = bk.recl, nb = (size_t)bk.nchunks * sizeof(uint32_t); break;
+    case ME_DBG_CPOOL: src = bk.cpool, nb = CP_N * sizeof(uint32_t); break;
+    case ME_DBG_STATS: src = bk.stats, nb = ME_STATS * sizeof(unsigned long long); break;
+    default: src = bk.err, nb = sizeof(uint32_t); break;
+  }
+  if (bytes) *bytes = nb;
+  if (!dst) return cap ? e->fail(ME_E_INVALID, "me_debug_export: no destination") : ME_OK;
+  if (cap < nb) return e->fail(ME_E_INVALID, "me_debug_export: capacity smaller than the array");
+  HIP_TRY(hipMemcpy(dst, src, nb, hipMemcpyDeviceToHost), "D2H debug export");
+  return ME_OK;
+}
+
 extern "C" int me_paths_read(const me_engine* e, uint32_t* flags) {
   if (!e || !flags) return ME_E_INVALID;
   *flags = (e->hot.agg_reg ? ME_PATH_GROUPED_AGG : 0u) | (e->bk.hot_min && e->hot.agg ? ME_PATH_HOT_AGG : 0u) |

@@ -338,6 +338,33 @@ class Engine:
         _check(self.lib, self.h, self.lib.me_paths_read(self.h, C.byref(f)))
         return {"grouped_agg": bool(f.value & 1), "hot_agg": bool(f.value & 2), "grouped_cancels": bool(f.value & 4)}
 
+    def debug_export(self, which=None) -> dict:
+        """DIAGNOSTIC (me_debug_layout / me_debug_export): the resident book's device arrays as the kernels
+        left them, after everything enqueued was matched. Returns {"info": the me_debug_info fields, name:
+        structured array ...} for the names in `which` (default: every array of _abi.DBG_ARRAYS); per-symbol
+        arrays come back shaped [S][...]. Raises when a struct's size differs from its dtype's here."""
+        info = _abi.MeDebugInfo()
+        _check(self.lib, self.h, self.lib.me_debug_layout(self.h, C.byref(info)))
+        inf = {n: int(getattr(info, n)) for n, _ in _abi.MeDebugInfo._fields_}
+        for name, (_, dt, szf) in _abi.DBG_ARRAYS.items():
+            if szf is not None and inf[szf] != dt.itemsize:
+                raise RuntimeError(f"debug_export: {name}: the library's {szf} = {inf[szf]}, the dtype holds {dt.itemsize} B")
+        if inf["chunk_slots"] != _abi.CHUNK_SLOTS or inf["fcache_row"] != 64:
+            raise RuntimeError(f"debug_export: chunk_slots / fcache_row drifted: {inf}")
+        S, L, W = inf["num_symbols"], inf["levels"], inf["level_words"]
+        shapes = {"levels": (S, L), "occ": (S, W), "tend": (S, L), "fcache": (S, inf["fcache_row"]), "fdir": (S, 2)}
+        out = {"info": inf}
+        for name in (which if which is not None else _abi.DBG_ARRAYS):
+            idx, dt, _ = _abi.DBG_ARRAYS[name]
+            nb = C.c_size_t(0)
+            _check(self.lib, self.h, self.lib.me_debug_export(self.h, idx, None, 0, C.byref(nb)))
+            if nb.value % dt.itemsize:
+                raise RuntimeError(f"debug_export: {name}: {nb.value} B is no multiple of {dt.itemsize}")
+            a = np.zeros(nb.value // dt.itemsize, dtype=dt)
+            _check(self.lib, self.h, self.lib.me_debug_export(self.h, idx, ptr(a), a.nbytes, C.byref(nb)))
+            out[name] = a.reshape(shapes[name]) if name in shapes else a
+        return out
+
     def admits(self, b: Batch) -> bool:
         """Would submit_batch(b) be admitted now (me_admission_check)? Nothing is enqueued."""
         n_rest = int(np.count_nonzero(((b.kind & 0x0C) == 0) & ((((b.kind >> 4) ^ (b.kind >> 5)) & 1) == 0)))
