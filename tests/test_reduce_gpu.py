@@ -15,6 +15,7 @@ from tests import cancel_targets as ct
 from tests import reduce_model as rm
 from tests import tif_model as tm
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
+from tests.big_qty import Script
 from tests.reduce_model import INT32_MAX, KIND_REDUCE, ReduceBook
 from tests.test_tif_gpu import _b, _env, _pipelined
 from tests.tif_model import kind
@@ -70,31 +71,6 @@ def _step(eng, model, a, ctx, me):
     assert_fills_equal(f, fo, ctx)
     _check_books(eng, model, ctx)
     return ro, fo
-
-
-class Script:
-    """Records appended in stream order; a cancel or reduce repeats the last seq."""
-
-    def __init__(self, seq0=1):
-        self.next = seq0
-        self.r = []
-
-    def new(self, s, side, px, q, market=False, tif=0):
-        self.r.append((self.next, px, q, s, kind(side, 1 if market else 0, 0, tif)))
-        self.next += 1
-        return self.next - 1
-
-    def cancel(self, s, target):
-        self.r.append((max(self.next - 1, 1), ct.to_i64(target), 0, s, kind(BUY, 0, 1)))
-
-    def reduce(self, s, target, d, kd=KIND_REDUCE):
-        self.r.append((max(self.next - 1, 1), ct.to_i64(target), d, s, kd))
-        return len(self.r) - 1
-
-    def take(self):
-        a = tm.Arrays(*[[x[i] for x in self.r] for i in range(5)])
-        self.r = []
-        return a
 
 
 def _st(r):
