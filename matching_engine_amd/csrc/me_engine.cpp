@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "me_engine.h"
+#include "me_feed.hpp"
 #include "me_layout.hpp"
 
 static_assert(me::ME_C == ME_CHUNK_SLOTS, "chunk width mismatch");
@@ -154,6 +155,46 @@ struct SlotMeta {
 };
 static_assert(sizeof(SlotMeta) == 16, "SlotMeta");
 
+// Host side of a feed's event ring (FeedRing, me_layout.hpp): off until enabled. The log and the control
+// words' host copy are pinned and device-mapped: ring.log / ring.hctl are the device's addresses of h_log /
+// h_ctl. ring.consumed counts the events handed out by read: a job is enqueued with the ring as it stands,
+// so the device sees no less free space than there is, and never reads host memory.
+template <class Ev>
+struct Feed {
+  bool on = false;
+  Ev* h_log = nullptr;
+  unsigned long long* h_ctl = nullptr;
+  FeedRing<Ev> ring{};
+
+  // A log of cap events and nctl >= FR_N control words, cleared (ctl on st); on an error the caller frees.
+  hipError_t alloc(hipStream_t st, uint64_t cap, size_t nctl = FR_N) {
+    hipError_t he;
+    ring.cap = cap;
+    if ((he = hipMalloc((void**)&ring.ctl, nctl * sizeof *ring.ctl)) != hipSuccess ||
+        (he = hipHostMalloc((void**)&h_log, cap * sizeof(Ev), hipHostMallocDefault)) != hipSuccess ||
+        (he = hipHostMalloc((void**)&h_ctl, FR_N * sizeof *h_ctl, hipHostMallocDefault)) != hipSuccess ||
+        (he = hipHostGetDevicePointer((void**)&ring.log, h_log, 0)) != hipSuccess ||
+        (he = hipHostGetDevicePointer((void**)&ring.hctl, h_ctl, 0)) != hipSuccess ||
+        (he = hipMemsetAsync(ring.ctl, 0, nctl * sizeof *ring.ctl, st)) != hipSuccess)
+      return he;
+    memset(h_ctl, 0, FR_N * sizeof *h_ctl);
+    return hipSuccess;
+  }
+  void free() {
+    if (ring.ctl) (void)hipFree(ring.ctl);
+    if (h_log) (void)hipHostFree(h_log);
+    if (h_ctl) (void)hipHostFree(h_ctl);
+    *this = Feed{};
+  }
+  int read(me_engine* e, Ev* out, size_t cap, size_t* n, size_t* left, int (*run_job)(me_engine*));
+  void stats(uint64_t* jobs, uint64_t* events, uint64_t* deferred) const {
+    const volatile unsigned long long* h = h_ctl;
+    if (jobs) *jobs = h[FR_JOBS];
+    if (events) *events = h[FR_TAIL];
+    if (deferred) *deferred = h[FR_DEFERRED];
+  }
+};
+
 // One slot of the host-batch pipeline (me_submit_host / me_collect).
 struct HostSlot {
   char* h_in = nullptr;   // pinned staging: the batch packed as seq[n] px[n] qty[n] sym[n] kind[n]
@@ -270,19 +311,12 @@ struct me_engine {
     uint32_t* err = nullptr;
     size_t sym_cap = 0, lv_cap = 0, n_cap = 0, ord_cap = 0, nord_cap = 0, err_cap = 0;
   } snap;
-  // top-of-book change feed (me_quotes_*): off until enabled. The log and the control words' host copy
-  // are pinned and device-mapped (qd.log / qd.hctl are the device's addresses of h_qlog / h_qctl).
-  bool quotes_on = false;
+  // top-of-book change feed (me_quotes_*) and depth feed (me_depth_*): each its event ring and its own
+  // device arrays (qd.ring / dd.ring are filled in per job, from the Feed)
+  Feed<me_quote> quotes;
   QuoteDev qd{};
-  me_quote* h_qlog = nullptr;
-  unsigned long long* h_qctl = nullptr;
-  uint64_t q_consumed = 0;  // events handed out by me_quotes_read
-  // depth feed (me_depth_*): off until enabled; the log and the control words' host copy as above
-  bool depth_on = false;
+  Feed<me_depth_event> depth;
   DepthDev dd{};
-  me_depth_event* h_dlog = nullptr;
-  unsigned long long* h_dctl = nullptr;
-  uint64_t d_consumed = 0;  // events handed out by me_depth_read
   uint64_t nmatched = 0;    // batches matched (enqueued match launches), host and device: the events' stamp
   uint32_t last_n = 0;
   uint32_t sq_idx = 0;  // seq-ring state the next k_seq_sweep reads (it writes the other one)
@@ -350,29 +384,63 @@ static int set_create_err(const std::string& s) {
 }
 
 static void quotes_free(me_engine* e) {
-  void* dp[] = {e->qd.pub, e->qd.cand, e->qd.mask, e->qd.woff, e->qd.ctl};
+  void* dp[] = {e->qd.pub, e->qd.cand, e->qd.mask, e->qd.woff};
   for (void* p : dp)
     if (p) (void)hipFree(p);
-  if (e->h_qlog) (void)hipHostFree(e->h_qlog);
-  if (e->h_qctl) (void)hipHostFree(e->h_qctl);
   e->qd = QuoteDev{};
-  e->h_qlog = nullptr;
-  e->h_qctl = nullptr;
-  e->q_consumed = 0;
-  e->quotes_on = false;
+  e->quotes.free();
 }
 
 static void depth_free(me_engine* e) {
-  void* dp[] = {e->dd.pub, e->dd.npub, e->dd.cand, e->dd.ncand, e->dd.cev, e->dd.nev, e->dd.off, e->dd.ctl};
+  void* dp[] = {e->dd.pub, e->dd.npub, e->dd.cand, e->dd.ncand, e->dd.cev, e->dd.nev, e->dd.off};
   for (void* p : dp)
     if (p) (void)hipFree(p);
-  if (e->h_dlog) (void)hipHostFree(e->h_dlog);
-  if (e->h_dctl) (void)hipHostFree(e->h_dctl);
   e->dd = DepthDev{};
-  e->h_dlog = nullptr;
-  e->h_dctl = nullptr;
-  e->d_consumed = 0;
-  e->depth_on = false;
+  e->depth.free();
+}
+
+// Up to `cap` logged events in order to `out`; *n and *left (either may be null) are kept current before
+// anything that can fail, so an error still tells the caller what it holds.
+template <class Ev>
+int Feed<Ev>::read(me_engine* e, Ev* out, size_t cap, size_t* n, size_t* left, int (*run_job)(me_engine*)) {
+  if (cap && !out) return e->fail(ME_E_INVALID, "null output");
+  volatile unsigned long long* h = h_ctl;
+  uint64_t done = 0;
+  for (bool caught_up = false;;) {
+    const uint64_t tail = h[FR_TAIL];
+    std::atomic_thread_fence(std::memory_order_acquire);  // the events were stored before the tail
+    const uint64_t k = feed_copy_out(h_log, ring.cap, ring.consumed, tail, out + done, cap - done);
+    ring.consumed += k;
+    done += k;
+    if (n) *n = (size_t)done;
+    if (left) *left = (size_t)(tail - ring.consumed);
+    if (tail != ring.consumed || !h[FR_PENDING] || caught_up || e->failed) return ME_OK;
+    // read empty with a deferral outstanding (as far as the device has got): once everything in flight
+    // is done and that still holds, one catch-up job — the log is empty, so it fits — and its events
+    // follow in this same call (or count in *left)
+    caught_up = true;
+    HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
+    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    if (h[FR_TAIL] == ring.consumed && h[FR_PENDING]) {
+      int rc = run_job(e);
+      if (rc) return rc;
+      HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    }
+  }
+}
+
+// The first job of a feed just allocated: the books as they stand now. A rare call, so it waits: the first
+// read holds the whole initial state. A failure frees the feed (`release`) once what was enqueued is done.
+template <class Ev>
+static int feed_start(me_engine* e, Feed<Ev>& f, int (*run_job)(me_engine*), void (*release)(me_engine*)) {
+  f.on = true;
+  int rc = run_job(e);
+  const hipError_t hs = hipStreamSynchronize(e->stream);
+  if (rc || hs != hipSuccess) {
+    release(e);
+    return rc ? rc : e->hip_fail(hs, "hipStreamSynchronize");
+  }
+  return ME_OK;
 }
 
 static void free_all(me_engine* e) {
@@ -983,14 +1051,12 @@ static void bucket_job(const me_engine* e, const me_engine::Pend& p, AuxBucket& 
 }
 
 // The feed's job behind a match launch (or at enable / catch-up time): every symbol's quote against the
-// published one, on the engine stream. `consumed` is the host's count now: the device sees no less free
-// space than there is, and never reads host memory.
+// published one, on the engine stream.
 static int quotes_job(me_engine* e) {
   QuoteDev q = e->qd;
-  q.consumed = e->q_consumed;
-  q.batches = e->nmatched;
-  hipError_t he = launch_quotes(e->stream, e->bk, q);
-  if (he != hipSuccess) return e->hip_fail(he, "quote feed launch");
+  q.ring = e->quotes.ring;
+  q.ring.batches = e->nmatched;
+  HIP_TRY(launch_quotes(e->stream, e->bk, q), "quote feed launch");
   return ME_OK;
 }
 
@@ -998,10 +1064,9 @@ static int quotes_job(me_engine* e) {
 // the published one (me_snapshot.hip k_depth_scan / k_depth_offsets / k_depth_emit).
 static int depth_job(me_engine* e) {
   DepthDev d = e->dd;
-  d.consumed = e->d_consumed;
-  d.batches = e->nmatched;
-  hipError_t he = launch_depth(e->stream, e->bk, d);
-  if (he != hipSuccess) return e->hip_fail(he, "depth feed launch");
+  d.ring = e->depth.ring;
+  d.ring.batches = e->nmatched;
+  HIP_TRY(launch_depth(e->stream, e->bk, d), "depth feed launch");
   return ME_OK;
 }
 
@@ -1094,11 +1159,11 @@ static int pipe_launch(me_engine* e, const me_engine::Group* nb) {
   }
   if (gm.n) {
     e->nmatched += gm.n;
-    if (e->quotes_on) {  // behind the group's match (side streams joined back), outside its timed span
+    if (e->quotes.on) {  // behind the group's match (side streams joined back), outside its timed span
       int rc = quotes_job(e);
       if (rc) return rc;
     }
-    if (e->depth_on) {
+    if (e->depth.on) {
       int rc = depth_job(e);
       if (rc) return rc;
     }
@@ -1241,11 +1306,11 @@ static int enqueue_batch(me_engine* e, const uint64_t* seq, const int64_t* px, c
   e->adm_matched += nadm;
   e->adm_at[++e->launch_no % me_engine::ADM_RING] = e->adm_matched;
   e->nmatched++;
-  if (e->quotes_on) {  // before the tape job: the slot's completion event then covers the batch's quotes
+  if (e->quotes.on) {  // before the tape job: the slot's completion event then covers the batch's quotes
     rc = quotes_job(e);
     if (rc) return rc;
   }
-  if (e->depth_on) {
+  if (e->depth.on) {
     rc = depth_job(e);
     if (rc) return rc;
   }
@@ -1757,7 +1822,7 @@ extern "C" int me_quotes_enable(me_engine* e, uint64_t cap_events) {
   if (!e) return ME_E_INVALID;
   if (e->failed) return ME_E_STATE;
   HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
-  if (e->quotes_on) {  // jobs in flight write the log: wait for them before it goes
+  if (e->quotes.on) {  // jobs in flight write the log: wait for them before it goes
     HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
     quotes_free(e);
   }
@@ -1770,76 +1835,30 @@ extern "C" int me_quotes_enable(me_engine* e, uint64_t cap_events) {
     return e->fail(ME_E_INVALID, "me_quotes_enable: cap_events above max(64 * num_symbols, 2^24)");
   QuoteDev& q = e->qd;
   q.nw = (uint32_t)((S + 63) / 64);
-  q.cap = cap;
   hipError_t he;
   if ((he = dalloc(&q.pub, S)) != hipSuccess || (he = dalloc(&q.cand, S)) != hipSuccess ||
       (he = dalloc(&q.mask, q.nw)) != hipSuccess || (he = dalloc(&q.woff, q.nw)) != hipSuccess ||
-      (he = dalloc(&q.ctl, QC_N)) != hipSuccess ||
-      (he = hipHostMalloc((void**)&e->h_qlog, cap * sizeof(me_quote), hipHostMallocDefault)) != hipSuccess ||
-      (he = hipHostMalloc((void**)&e->h_qctl, QC_N * 8, hipHostMallocDefault)) != hipSuccess ||
-      (he = hipHostGetDevicePointer((void**)&q.log, e->h_qlog, 0)) != hipSuccess ||
-      (he = hipHostGetDevicePointer((void**)&q.hctl, e->h_qctl, 0)) != hipSuccess ||
+      (he = e->quotes.alloc(e->stream, cap)) != hipSuccess ||
       // the published state: both sides absent
-      (he = hipMemsetAsync(q.pub, 0, S * sizeof(QuoteTop), e->stream)) != hipSuccess ||
-      (he = hipMemsetAsync(q.ctl, 0, QC_N * 8, e->stream)) != hipSuccess) {
+      (he = hipMemsetAsync(q.pub, 0, S * sizeof(QuoteTop), e->stream)) != hipSuccess) {
     quotes_free(e);
     return e->hip_fail(he, "me_quotes_enable");
   }
-  memset(e->h_qctl, 0, QC_N * 8);
-  e->quotes_on = true;
-  // the books as they stand at this point of the stream; a rare call, so it waits: the first read after it
-  // holds the whole initial state
-  int rc = quotes_job(e);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
-  return ME_OK;
+  return feed_start(e, e->quotes, quotes_job, quotes_free);
 }
 
 extern "C" int me_quotes_read(me_engine* e, me_quote* out, size_t cap, size_t* n, size_t* left) {
   if (n) *n = 0;
   if (left) *left = 0;
   if (!e) return ME_E_INVALID;
-  if (!e->quotes_on) return e->fail(ME_E_INVALID, "the quote feed is off (me_quotes_enable)");
-  if (cap && !out) return e->fail(ME_E_INVALID, "null output");
-  volatile unsigned long long* h = e->h_qctl;
-  uint64_t done = 0, tail;
-  for (bool caught_up = false;;) {
-    tail = h[QC_TAIL];
-    std::atomic_thread_fence(std::memory_order_acquire);  // the events were stored before the tail
-    const uint64_t k = std::min<uint64_t>(tail - e->q_consumed, cap - done);
-    const uint64_t at = e->q_consumed % e->qd.cap;
-    const uint64_t first = std::min<uint64_t>(k, e->qd.cap - at);
-    if (first) memcpy(out + done, e->h_qlog + at, first * sizeof(me_quote));
-    if (k > first) memcpy(out + done + first, e->h_qlog, (k - first) * sizeof(me_quote));
-    e->q_consumed += k;
-    done += k;
-    if (n) *n = (size_t)done;  // (kept current: an error below still tells the caller what it holds)
-    if (left) *left = (size_t)(tail - e->q_consumed);
-    if (tail != e->q_consumed || !h[QC_PENDING] || caught_up || e->failed) break;
-    // read empty with a deferral outstanding (as far as the device has got): once everything in flight
-    // is done and that still holds, one catch-up job — the log is empty, so it fits — and its events
-    // follow in this same call (or count in *left)
-    caught_up = true;
-    HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
-    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
-    if (h[QC_TAIL] == e->q_consumed && h[QC_PENDING]) {
-      int rc = quotes_job(e);
-      if (rc) return rc;
-      HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
-    }
-  }
-  if (n) *n = (size_t)done;
-  if (left) *left = (size_t)(tail - e->q_consumed);
-  return ME_OK;
+  if (!e->quotes.on) return e->fail(ME_E_INVALID, "the quote feed is off (me_quotes_enable)");
+  return e->quotes.read(e, out, cap, n, left, quotes_job);
 }
 
 extern "C" int me_quotes_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred) {
   if (!e) return ME_E_INVALID;
-  if (!e->quotes_on) return e->fail(ME_E_INVALID, "the quote feed is off (me_quotes_enable)");
-  volatile unsigned long long* h = e->h_qctl;
-  if (groups) *groups = h[QC_GROUPS];
-  if (events) *events = h[QC_TAIL];
-  if (deferred) *deferred = h[QC_DEFERRED];
+  if (!e->quotes.on) return e->fail(ME_E_INVALID, "the quote feed is off (me_quotes_enable)");
+  e->quotes.stats(groups, events, deferred);
   return ME_OK;
 }
 
@@ -1854,88 +1873,39 @@ extern "C" int me_depth_enable(me_engine* e, uint32_t depth, uint64_t cap_events
   const uint64_t cap = std::max<uint64_t>(cap_events, 4 * D * S);
   if (depth && cap_events && cap > (1ull << 26))
     return e->fail(ME_E_INVALID, "me_depth_enable: the log's capacity resolves above 2^26 events");
-  if (e->depth_on) {  // jobs in flight write the log: wait for them before it goes
+  if (e->depth.on) {  // jobs in flight write the log: wait for them before it goes
     HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
     depth_free(e);
   }
   if (!depth || !cap_events) return ME_OK;
   DepthDev& d = e->dd;
   d.D = depth;
-  d.cap = cap;
   const size_t ns = 2 * S;
   hipError_t he;
   if ((he = dalloc(&d.pub, ns * D)) != hipSuccess || (he = dalloc(&d.npub, ns)) != hipSuccess ||
       (he = dalloc(&d.cand, ns * D)) != hipSuccess || (he = dalloc(&d.ncand, ns)) != hipSuccess ||
       (he = dalloc(&d.cev, ns * 2 * D)) != hipSuccess || (he = dalloc(&d.nev, ns)) != hipSuccess ||
-      (he = dalloc(&d.off, ns)) != hipSuccess || (he = dalloc(&d.ctl, DC_N)) != hipSuccess ||
-      (he = hipHostMalloc((void**)&e->h_dlog, cap * sizeof(me_depth_event), hipHostMallocDefault)) != hipSuccess ||
-      (he = hipHostMalloc((void**)&e->h_dctl, 4 * 8, hipHostMallocDefault)) != hipSuccess ||
-      (he = hipHostGetDevicePointer((void**)&d.log, e->h_dlog, 0)) != hipSuccess ||
-      (he = hipHostGetDevicePointer((void**)&d.hctl, e->h_dctl, 0)) != hipSuccess ||
+      (he = dalloc(&d.off, ns)) != hipSuccess || (he = e->depth.alloc(e->stream, cap, DJ_N)) != hipSuccess ||
       // the published state: every view empty
-      (he = hipMemsetAsync(d.npub, 0, ns * sizeof(uint32_t), e->stream)) != hipSuccess ||
-      (he = hipMemsetAsync(d.ctl, 0, DC_N * 8, e->stream)) != hipSuccess) {
+      (he = hipMemsetAsync(d.npub, 0, ns * sizeof(uint32_t), e->stream)) != hipSuccess) {
     depth_free(e);
     return e->hip_fail(he, "me_depth_enable");
   }
-  memset(e->h_dctl, 0, 4 * 8);
-  e->depth_on = true;
-  // the books as they stand at this point of the stream; a rare call, so it waits: the first read after it
-  // holds the whole initial state
-  int rc = depth_job(e);
-  hipError_t hs = rc ? hipSuccess : hipStreamSynchronize(e->stream);
-  if (rc || hs != hipSuccess) {  // a failed enable leaves the feed off, its state freed
-    if (rc) (void)hipStreamSynchronize(e->stream);  // (whatever part of the job was enqueued is done)
-    depth_free(e);
-    return rc ? rc : e->hip_fail(hs, "hipStreamSynchronize");
-  }
-  return ME_OK;
+  return feed_start(e, e->depth, depth_job, depth_free);
 }
 
 extern "C" int me_depth_read(me_engine* e, me_depth_event* out, size_t cap, size_t* n, size_t* left) {
   if (n) *n = 0;
   if (left) *left = 0;
   if (!e) return ME_E_INVALID;
-  if (!e->depth_on) return e->fail(ME_E_INVALID, "the depth feed is off (me_depth_enable)");
-  if (cap && !out) return e->fail(ME_E_INVALID, "null output");
-  volatile unsigned long long* h = e->h_dctl;
-  uint64_t done = 0, tail;
-  for (bool caught_up = false;;) {
-    tail = h[DC_TAIL];
-    std::atomic_thread_fence(std::memory_order_acquire);  // the events were stored before the tail
-    const uint64_t k = std::min<uint64_t>(tail - e->d_consumed, cap - done);
-    const uint64_t at = e->d_consumed % e->dd.cap;
-    const uint64_t first = std::min<uint64_t>(k, e->dd.cap - at);
-    if (first) memcpy(out + done, e->h_dlog + at, first * sizeof(me_depth_event));
-    if (k > first) memcpy(out + done + first, e->h_dlog, (k - first) * sizeof(me_depth_event));
-    e->d_consumed += k;
-    done += k;
-    if (n) *n = (size_t)done;  // (kept current: an error below still tells the caller what it holds)
-    if (left) *left = (size_t)(tail - e->d_consumed);
-    if (tail != e->d_consumed || !h[DC_PENDING] || caught_up || e->failed) break;
-    // read empty with a deferral outstanding: once everything in flight is done and that still holds, one
-    // catch-up job (the log is empty, so it fits); its events follow in this call or count in *left
-    caught_up = true;
-    HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
-    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
-    if (h[DC_TAIL] == e->d_consumed && h[DC_PENDING]) {
-      int rc = depth_job(e);
-      if (rc) return rc;
-      HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
-    }
-  }
-  if (n) *n = (size_t)done;
-  if (left) *left = (size_t)(tail - e->d_consumed);
-  return ME_OK;
+  if (!e->depth.on) return e->fail(ME_E_INVALID, "the depth feed is off (me_depth_enable)");
+  return e->depth.read(e, out, cap, n, left, depth_job);
 }
 
 extern "C" int me_depth_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred) {
   if (!e) return ME_E_INVALID;
-  if (!e->depth_on) return e->fail(ME_E_INVALID, "the depth feed is off (me_depth_enable)");
-  volatile unsigned long long* h = e->h_dctl;
-  if (groups) *groups = h[DC_JOBS];
-  if (events) *events = h[DC_TAIL];
-  if (deferred) *deferred = h[DC_DEFERRED];
+  if (!e->depth.on) return e->fail(ME_E_INVALID, "the depth feed is off (me_depth_enable)");
+  e->depth.stats(groups, events, deferred);
   return ME_OK;
 }
 

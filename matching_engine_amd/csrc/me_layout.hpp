@@ -483,6 +483,23 @@ struct SnapReq {
   uint32_t* err;             // set on a corrupt chain
 };
 
+// ---- the feeds' event ring -----------------------------------------------------------
+// Both feeds log into a bounded ring in pinned, device-mapped memory: event i sits at log[i % cap]. Four
+// control words are kept in HBM (ctl) and mirrored into pinned memory (hctl) by the one thread that ends a
+// job (me_snapshot.hip feed_publish): events ever logged (the ring's tail), jobs run, jobs deferred, a
+// deferral outstanding. A job is all or nothing: one that does not fit cap - (tail - consumed) changes
+// nothing but the deferral words.
+enum : uint32_t { FR_TAIL = 0, FR_JOBS = 1, FR_DEFERRED = 2, FR_PENDING = 3, FR_N = 4 };
+template <class Ev>
+struct FeedRing {
+  Ev* log;                   // [cap] host-mapped ring
+  unsigned long long* ctl;   // [FR_N], then the feed's own words (the depth feed's DJ_*)
+  unsigned long long* hctl;  // [FR_N] host-mapped copy
+  unsigned long long cap;
+  unsigned long long consumed;  // events the host had read when the job was enqueued (<= the tail)
+  unsigned long long batches;   // the job's stamp: batches matched when it was enqueued
+};
+
 // ---- top-of-book change feed (me_snapshot.hip k_quote_scan / k_quote_emit) -----------
 // A symbol's quote: the best occupied level of each side (flags bit 0 has_bid, bit 1 has_ask; an absent
 // side has price and quantity 0). qpub [S] holds the quote last published for every symbol.
@@ -493,21 +510,13 @@ struct alignas(8) QuoteTop {
   uint32_t pad;
 };
 static_assert(sizeof(QuoteTop) == 40, "QuoteTop is 40 B");
-// Control words of the feed, kept in HBM (QuoteDev::ctl) and mirrored into pinned memory (QuoteDev::hctl)
-// by every emit pass: events ever logged (the ring's tail), jobs run, jobs deferred, a deferral outstanding.
-enum : uint32_t { QC_TAIL = 0, QC_GROUPS = 1, QC_DEFERRED = 2, QC_PENDING = 3, QC_N = 4 };
 struct QuoteDev {
+  FeedRing<me_quote> ring;
   QuoteTop* pub;             // [S] last published quote
   QuoteTop* cand;            // [S] this job's quote of the symbols that differ from pub
   unsigned long long* mask;  // [nw] one ballot word per 64 symbols: bit set <=> the symbol differs
   uint32_t* woff;            // [nw] changed symbols before each word
-  unsigned long long* ctl;   // [QC_N]
-  unsigned long long* hctl;  // [QC_N] host-mapped copy
-  me_quote* log;             // [cap] host-mapped ring: event i sits at i % cap
-  unsigned long long cap;
-  unsigned long long consumed;  // events the host had read when the job was enqueued (<= the tail)
-  unsigned long long batches;   // the job's stamp: batches matched so far
-  uint32_t nw;                  // ceil(S / 64)
+  uint32_t nw;               // ceil(S / 64)
   uint32_t pad;
 };
 
@@ -517,13 +526,12 @@ struct QuoteDev {
 struct alignas(16) DepthLvl {
   long long price, qty;
 };
-// Control words in HBM (DepthDev::ctl); the first four are mirrored into pinned memory (DepthDev::hctl) by
-// the last workgroup of every emit pass and mean what the quote feed's do. The rest belong to the job in
-// flight: the tail it started from, its event total, whether it fits (k_depth_offsets writes them for the
-// emit pass), and the count of emit workgroups that have finished.
-enum : uint32_t { DC_TAIL = 0, DC_JOBS = 1, DC_DEFERRED = 2, DC_PENDING = 3, DC_JOB_TAIL = 4, DC_JOB_TOTAL = 5,
-                  DC_JOB_FIT = 6, DC_DONE = 7, DC_N = 8 };
+// Words of ring.ctl behind the ring's own, belonging to the job in flight: the tail it started from, its
+// event total, whether it fits (k_depth_offsets writes them for the emit pass), and the count of emit
+// workgroups that have finished.
+enum : uint32_t { DJ_TAIL = FR_N, DJ_TOTAL, DJ_FIT, DJ_DONE, DJ_N };
 struct DepthDev {
+  FeedRing<me_depth_event> ring;
   DepthLvl* pub;             // [2S][D] published views, best first
   uint32_t* npub;            // [2S] their lengths
   DepthLvl* cand;            // [2S][D] this job's views of the sides that differ
@@ -531,12 +539,6 @@ struct DepthDev {
   DepthLvl* cev;             // [2S][2D] this job's events per side in priority order (qty 0 = DELETE)
   uint32_t* nev;             // [2S] events per side (0: the side did not change)
   uint32_t* off;             // [2S] events before each side
-  unsigned long long* ctl;   // [DC_N]
-  unsigned long long* hctl;  // [4] host-mapped copy of the first four
-  me_depth_event* log;       // [cap] host-mapped ring: event i sits at i % cap
-  unsigned long long cap;
-  unsigned long long consumed;  // events the host had read when the job was enqueued (<= the tail)
-  unsigned long long batches;   // the job's stamp
   uint32_t D;
   uint32_t pad;
 };

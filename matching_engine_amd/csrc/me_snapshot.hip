@@ -210,6 +210,35 @@ __global__ __launch_bounds__(SNAP_T) void k_book_snapshot(BookDev bk, SnapReq rq
   }
 }
 
+// ---- the feeds' event ring (FeedRing, me_layout.hpp): the two steps both emit passes share -----------
+// Does a job of `total` events fit the free part of the log, given the tail it starts from?
+template <class Ev>
+__device__ __forceinline__ bool feed_fits(const FeedRing<Ev>& r, unsigned long long tail, unsigned long long total) {
+  const unsigned long long used = tail - r.consumed;  // (consumed <= tail: the host reads only logged events)
+  return used <= r.cap && total <= r.cap - used;
+}
+
+// The end of a job, run by exactly one thread once every event of the job is behind a system-scope fence
+// (the caller's business). The mirror is pinned host memory written with plain vector stores; the tail goes
+// last, behind a fence, so a host that reads the tail first never sees an unwritten event.
+template <class Ev>
+__device__ __forceinline__ void feed_publish(const FeedRing<Ev>& r, unsigned long long tail, unsigned long long total,
+                                             bool fit) {
+  const unsigned long long jobs = r.ctl[FR_JOBS] + 1ull;
+  const unsigned long long deferred = r.ctl[FR_DEFERRED] + (fit ? 0ull : 1ull);
+  const unsigned long long ntail = fit ? tail + total : tail;
+  r.ctl[FR_TAIL] = ntail;
+  r.ctl[FR_JOBS] = jobs;
+  r.ctl[FR_DEFERRED] = deferred;
+  r.ctl[FR_PENDING] = fit ? 0ull : 1ull;
+  volatile unsigned long long* h = r.hctl;
+  h[FR_JOBS] = jobs;
+  h[FR_DEFERRED] = deferred;
+  h[FR_PENDING] = fit ? 0ull : 1ull;
+  __threadfence_system();
+  h[FR_TAIL] = ntail;
+}
+
 // ---- top-of-book change feed (me_quotes_*, include/me_engine.h; StreamMarketData, proto:32,62-69) ----
 // Two launches behind every match launch of an engine with the feed on.
 //
@@ -223,10 +252,8 @@ __global__ __launch_bounds__(SNAP_T) void k_book_snapshot(BookDev bk, SnapReq rq
 // k_quote_emit: one workgroup. It prefixes the words' popcounts (S / 64 words: 1,563 at 100,000
 // symbols, two block scans), checks the total against the free part of the log, and — only if it fits —
 // writes the events in symbol order (a wave per word, a lane per set bit: position = the word's offset
-// + the bits below the lane) and updates the published quotes. A job that does not fit changes nothing
-// but the deferral counters. The log and the control words' host copy are pinned host memory written
-// through the device mapping with plain vector stores; the tail is stored after a system-scope fence
-// behind the events, so a host that reads the tail first never sees an unwritten event.
+// + the bits below the lane) and updates the published quotes. Every writing thread fences (system scope)
+// behind its events; after the block's barrier thread 0 runs feed_publish.
 __device__ __forceinline__ bool quote_far_best(const BookDev& bk, uint32_t s, uint32_t side, uint32_t nfar,
                                                long long& px, long long& qty) {
   if (!nfar) return false;
@@ -297,9 +324,9 @@ __global__ __launch_bounds__(SNAP_T) void k_quote_emit(BookDev bk, QuoteDev q) {
     if (w < q.nw) q.woff[w] = run + ex;
     run += tot;
   }
-  const unsigned long long tail = q.ctl[QC_TAIL];
-  const unsigned long long used = tail - q.consumed;  // (consumed <= tail: the host reads only logged events)
-  const bool fit = used <= q.cap && run <= q.cap - used;
+  const FeedRing<me_quote>& r = q.ring;
+  const unsigned long long tail = r.ctl[FR_TAIL];
+  const bool fit = feed_fits(r, tail, run);
   __syncthreads();  // the offsets are written, the tail is read
   if (fit && run) {
     for (uint32_t w = wv; w < q.nw; w += SNAP_T / 64) {
@@ -313,30 +340,16 @@ __global__ __launch_bounds__(SNAP_T) void k_quote_emit(BookDev bk, QuoteDev q) {
       ev.ask_price_q4 = c.ask_px;
       ev.bid_qty = c.bid_qty;
       ev.ask_qty = c.ask_qty;
-      ev.batches = q.batches;
+      ev.batches = r.batches;
       ev.symbol = bk.gsym ? bk.gsym[s] : s;
       ev.flags = c.flags;
-      q.log[(tail + pos) % q.cap] = ev;
+      r.log[(tail + pos) % r.cap] = ev;
       q.pub[s] = c;
     }
     __threadfence_system();
   }
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned long long groups = q.ctl[QC_GROUPS] + 1ull;
-    const unsigned long long deferred = q.ctl[QC_DEFERRED] + (fit ? 0ull : 1ull);
-    const unsigned long long ntail = fit ? tail + run : tail;
-    q.ctl[QC_TAIL] = ntail;
-    q.ctl[QC_GROUPS] = groups;
-    q.ctl[QC_DEFERRED] = deferred;
-    q.ctl[QC_PENDING] = fit ? 0ull : 1ull;
-    volatile unsigned long long* h = q.hctl;
-    h[QC_GROUPS] = groups;
-    h[QC_DEFERRED] = deferred;
-    h[QC_PENDING] = fit ? 0ull : 1ull;
-    __threadfence_system();
-    h[QC_TAIL] = ntail;
-  }
+  __syncthreads();  // every writer has fenced
+  if (tid == 0) feed_publish(r, tail, run, fit);
 }
 
 // The feed's job: scan + emit on st (behind the match launch whose quotes it takes).
@@ -367,14 +380,14 @@ hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q) {
 // two popcounts, nothing is sorted.
 //
 // k_depth_offsets: one workgroup. Block scans, 1,024 counts a round with the running total carried from
-// round to round, turn the 2S counts into offsets and the job's total; the fit test is the quote feed's; it
+// round to round, turn the 2S counts into offsets and the job's total; the fit test is feed_fits; it
 // leaves {tail, total, fit} for the emit pass.
 //
 // k_depth_emit: spread over the grid, at most 2,048 waves, each over a run of consecutive sides. Only when
 // the job fits, a wave copies the events of its changed sides to log[(tail + offset + rank) % cap] and their
 // candidate views over the published ones. A wave that wrote events fences once (system scope) behind all of
-// them, not once per side, and every workgroup counts itself done on a device-scope counter; the last one updates the control words, mirrors them to pinned memory, fences and
-// stores the host-visible tail: a host that reads the tail first never sees an unwritten event.
+// them, not once per side, and every workgroup counts itself done on a device-scope counter; the last one
+// runs feed_publish.
 constexpr int DEPTH_WAVES = 4;
 constexpr uint32_t DEPTH_EMIT_WAVES = 2048;  // waves of the emit pass at most (8 per CU)
 
@@ -556,21 +569,22 @@ __global__ __launch_bounds__(SNAP_T) void k_depth_offsets(BookDev bk, DepthDev d
     run += tot;
   }
   if (tid == 0) {
-    const unsigned long long tail = d.ctl[DC_TAIL];
-    const unsigned long long used = tail - d.consumed;  // (consumed <= tail: the host reads only logged events)
-    d.ctl[DC_JOB_TAIL] = tail;
-    d.ctl[DC_JOB_TOTAL] = run;
-    d.ctl[DC_JOB_FIT] = used <= d.cap && run <= d.cap - used ? 1ull : 0ull;
+    unsigned long long* ctl = d.ring.ctl;
+    const unsigned long long tail = ctl[FR_TAIL];
+    ctl[DJ_TAIL] = tail;
+    ctl[DJ_TOTAL] = run;
+    ctl[DJ_FIT] = feed_fits(d.ring, tail, run) ? 1ull : 0ull;
   }
 }
 
 __global__ __launch_bounds__(DEPTH_WAVES * 64) void k_depth_emit(BookDev bk, DepthDev d, uint32_t spw) {
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   const uint32_t ns = 2u * bk.S, D = d.D;
-  const bool fit = d.ctl[DC_JOB_FIT] != 0ull;
-  const unsigned long long total = d.ctl[DC_JOB_TOTAL];
+  const FeedRing<me_depth_event>& r = d.ring;
+  const bool fit = r.ctl[DJ_FIT] != 0ull;
+  const unsigned long long total = r.ctl[DJ_TOTAL];
   if (fit && total) {
-    const unsigned long long tail = d.ctl[DC_JOB_TAIL];
+    const unsigned long long tail = r.ctl[DJ_TAIL];
     // this wave's sides [lo, hi): 64 counts per load, then the changed sides one after the other
     const uint32_t lo = min(ns, (blockIdx.x * DEPTH_WAVES + wv) * spw), hi = min(ns, lo + spw);
     bool wrote = false;
@@ -589,11 +603,11 @@ __global__ __launch_bounds__(DEPTH_WAVES * 64) void k_depth_emit(BookDev bk, Dep
           me_depth_event ev;
           ev.price_q4 = x.price;
           ev.qty = x.qty;
-          ev.batches = d.batches;
+          ev.batches = r.batches;
           ev.symbol = bk.gsym ? bk.gsym[s] : s;
           ev.side = (sidx & 1u) ? ME_SIDE_SELL : ME_SIDE_BUY;
           ev.pad[0] = ev.pad[1] = ev.pad[2] = 0;
-          d.log[(tail + d.off[sidx] + lane) % d.cap] = ev;
+          r.log[(tail + d.off[sidx] + lane) % r.cap] = ev;
         }
         // (the published view is read by the next job's scan only, a later launch: no fence for it)
         const uint32_t nc = min(d.ncand[sidx], D);
@@ -605,24 +619,11 @@ __global__ __launch_bounds__(DEPTH_WAVES * 64) void k_depth_emit(BookDev bk, Dep
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const unsigned long long before = atomicAdd(&d.ctl[DC_DONE], 1ull);
+    const unsigned long long before = atomicAdd(&r.ctl[DJ_DONE], 1ull);
     if (before + 1ull == gridDim.x) {  // the last workgroup: every event of the job is behind a fence
       __threadfence_system();
-      const unsigned long long tail = d.ctl[DC_JOB_TAIL];
-      const unsigned long long jobs = d.ctl[DC_JOBS] + 1ull;
-      const unsigned long long deferred = d.ctl[DC_DEFERRED] + (fit ? 0ull : 1ull);
-      const unsigned long long ntail = fit ? tail + total : tail;
-      d.ctl[DC_TAIL] = ntail;
-      d.ctl[DC_JOBS] = jobs;
-      d.ctl[DC_DEFERRED] = deferred;
-      d.ctl[DC_PENDING] = fit ? 0ull : 1ull;
-      d.ctl[DC_DONE] = 0ull;
-      volatile unsigned long long* h = d.hctl;
-      h[DC_JOBS] = jobs;
-      h[DC_DEFERRED] = deferred;
-      h[DC_PENDING] = fit ? 0ull : 1ull;
-      __threadfence_system();
-      h[DC_TAIL] = ntail;
+      r.ctl[DJ_DONE] = 0ull;
+      feed_publish(r, r.ctl[DJ_TAIL], total, fit);
     }
   }
 }

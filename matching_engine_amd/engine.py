@@ -144,6 +144,7 @@ class Engine:
             host_tape_cap,
         )
         self.max_batch = int(max_batch)
+        self._depth = 0  # levels per side of the depth feed (depth_enable), 0 while it is off
         h = self.lib.me_create(C.byref(cfg))
         if not h:
             buf = C.create_string_buffer(1024)
@@ -379,6 +380,26 @@ class Engine:
         _check(self.lib, self.h, self.lib.me_admission_read(self.h, C.byref(r), C.byref(b), C.byref(x)))
         return {"resting": r.value, "bound": b.value, "exact_counts": x.value}
 
+    # -- the feeds' shared read side (me_quotes_* / me_depth_*: one event-ring protocol, two event types)
+    def _feed_read(self, fn, dtype, cap: int):
+        out = np.zeros(cap, dtype=dtype)
+        n, left = C.c_size_t(0), C.c_size_t(0)
+        _check(self.lib, self.h, fn(self.h, ptr(out), cap, C.byref(n), C.byref(left)))
+        return out[: n.value], left.value
+
+    def _feed_drain(self, read) -> np.ndarray:
+        parts = []
+        while True:
+            ev, left = read()
+            parts.append(ev)
+            if not left:
+                return np.concatenate(parts)
+
+    def _feed_stats(self, fn) -> dict:
+        g, ev, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib, self.h, fn(self.h, C.byref(g), C.byref(ev), C.byref(d)))
+        return {"groups": g.value, "events": ev.value, "deferred": d.value}
+
     # -- top-of-book change feed (me_quotes_*)
     def quotes_enable(self, cap_events: int):
         """Turn the quote feed on with a log of cap_events events (raised to num_symbols), or off with 0.
@@ -388,25 +409,14 @@ class Engine:
     def quotes_read(self, cap: int = 0):
         """(events QUOTE_DTYPE, left): up to `cap` logged events in order (0 = a buffer of num_symbols) and
         how many stay unread. Launches no partial group; see me_quotes_read for what is there when."""
-        cap = int(cap) or self.num_symbols
-        out = np.zeros(cap, dtype=_abi.QUOTE_DTYPE)
-        n, left = C.c_size_t(0), C.c_size_t(0)
-        _check(self.lib, self.h, self.lib.me_quotes_read(self.h, ptr(out), cap, C.byref(n), C.byref(left)))
-        return out[: n.value], left.value
+        return self._feed_read(self.lib.me_quotes_read, _abi.QUOTE_DTYPE, int(cap) or self.num_symbols)
 
     def quotes_drain(self) -> np.ndarray:
         """Every logged event: reads until none is left (a deferred job's catch-up included)."""
-        parts = []
-        while True:
-            ev, left = self.quotes_read()
-            parts.append(ev)
-            if not left:
-                return np.concatenate(parts)
+        return self._feed_drain(self.quotes_read)
 
     def quotes_stats(self) -> dict:
-        g, ev, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _check(self.lib, self.h, self.lib.me_quotes_stats(self.h, C.byref(g), C.byref(ev), C.byref(d)))
-        return {"groups": g.value, "events": ev.value, "deferred": d.value}
+        return self._feed_stats(self.lib.me_quotes_stats)
 
     # -- depth feed (me_depth_*)
     def depth_enable(self, depth: int, cap_events: int):
@@ -419,25 +429,15 @@ class Engine:
     def depth_read(self, cap: int = 0):
         """(events DEPTH_DTYPE, left): up to `cap` logged events in order (0 = a buffer of one job's most) and
         how many stay unread. Launches no partial group; see me_depth_read for what is there when."""
-        cap = int(cap) or max(1, 4 * getattr(self, "_depth", 1) * self.num_symbols)
-        out = np.zeros(cap, dtype=_abi.DEPTH_DTYPE)
-        n, left = C.c_size_t(0), C.c_size_t(0)
-        _check(self.lib, self.h, self.lib.me_depth_read(self.h, ptr(out), cap, C.byref(n), C.byref(left)))
-        return out[: n.value], left.value
+        cap = int(cap) or max(1, 4 * self._depth * self.num_symbols)
+        return self._feed_read(self.lib.me_depth_read, _abi.DEPTH_DTYPE, cap)
 
     def depth_drain(self) -> np.ndarray:
         """Every logged event: reads until none is left (a deferred job's catch-up included)."""
-        parts = []
-        while True:
-            ev, left = self.depth_read()
-            parts.append(ev)
-            if not left:
-                return np.concatenate(parts)
+        return self._feed_drain(self.depth_read)
 
     def depth_stats(self) -> dict:
-        g, ev, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _check(self.lib, self.h, self.lib.me_depth_stats(self.h, C.byref(g), C.byref(ev), C.byref(d)))
-        return {"groups": g.value, "events": ev.value, "deferred": d.value}
+        return self._feed_stats(self.lib.me_depth_stats)
 
     # -- timing
     def timing_enable(self, period: int = 1):

@@ -4,45 +4,14 @@
 Every test but the log-full one sizes the log so that no job defers, and asserts it: a deferral must not
 be able to hide a missing event.
 """
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 from tests import depth_model as dm
 from tests import quote_model as qm
+from tests.feed_common import BIG, BUY, PATHS, SELL, SMALL, Rows, _c5_stream, _engine, _env, _same
 
 pytestmark = pytest.mark.gpu
-
-BUY, SELL = 1, 2
-BIG = 2_147_483_647
-
-# name -> (levels, environment, expected eng.paths(), grouped): the table of tests/test_quotes_gpu.py
-PATHS = {
-    "reg": (128, {"ME_REG_AGG": "0"}, {"grouped_agg": False}, True),
-    "gwalk": (128, {"ME_REG_AGG": "1", "ME_GW_CANCEL": "0"}, {"grouped_agg": True, "grouped_cancels": False}, True),
-    "gwalk_cx": (128, {"ME_REG_AGG": "1", "ME_GW_CANCEL": "1"}, {"grouped_agg": True, "grouped_cancels": True}, True),
-    "deep": (1024, {"ME_HOT_MIN": "0"}, {"hot_agg": False}, False),
-    "hot_agg": (1024, {"ME_HOT_MIN": "200", "ME_HOT_AGG": "1"}, {"hot_agg": True}, False),
-    "hot": (2048, {"ME_HOT_MIN": "200", "ME_HOT_AGG": "0"}, {"hot_agg": False}, False),
-}
-SMALL = ("reg", "gwalk", "gwalk_cx")
-
-
-@contextlib.contextmanager
-def _env(env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
 
 @pytest.fixture(scope="module")
 def me(built):
@@ -56,45 +25,6 @@ def orc(built):
     from oracle import oracle
 
     return oracle
-
-
-def _engine(me, path, S, base, max_batch, max_resting, **kw):
-    L, env, expect, _ = PATHS[path]
-    with _env(env):
-        eng = me.Engine(S, L, base, max_batch=max_batch, max_resting=max_resting, seq_ring=1 << 22, **kw)
-    p = eng.paths()
-    for k, v in expect.items():
-        assert p[k] == v, f"{path}: paths() {p}"
-    return eng
-
-
-class Rows:
-    """Scripted records in stream order: (symbol, side, price, qty) LIMITs, MARKETs and cancels."""
-
-    def __init__(self, me, seq0=1):
-        self.me, self.seq, self.r = me, seq0, []
-
-    def limit(self, s, side, px, q):
-        self.r.append((self.seq, px, q, s, self.me.kind(side)))
-        self.seq += 1
-        return self.seq - 1
-
-    def market(self, s, side, q):
-        self.r.append((self.seq, 0, q, s, self.me.kind(side, 1)))
-        self.seq += 1
-
-    def cancel(self, s, target):
-        self.r.append((self.seq - 1, target, 0, s, self.me.kind(BUY, 0, 1)))
-
-    def batch(self):
-        b = self.me.Batch(*[[x[i] for x in self.r] for i in range(5)])
-        self.r = []
-        return b
-
-
-def _same(got, exp, ctx):
-    assert got.dtype == exp.dtype
-    assert np.array_equal(got, exp), f"{ctx}: events differ\n got {got}\n exp {exp}"
 
 
 def _no_deferral(eng, groups=None):
@@ -120,13 +50,6 @@ def _replays_to(eng, S, D, got, ids=None):
 
 
 # ---- every path ------------------------------------------------------------------------------------
-def _c5_stream(me, S, L, nb, batch):
-    sc = me.preset(5, num_symbols=S, levels=L, batch=batch, cancel_pct=30, market_pct=15, market_qty_mult=4,
-                   far_pct=3, zipf_s=1.1, seed=11)
-    st = me.Stream(sc)
-    return st.base_prices(), [st.next(batch) for _ in range(nb)]
-
-
 @pytest.mark.parametrize("path,group", [(p, g) for p in SMALL for g in (1, 8, 32)] +
                          [(p, 1) for p in PATHS if p not in SMALL])
 def test_events_of_every_group_on_every_path(me, orc, path, group):

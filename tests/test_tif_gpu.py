@@ -6,14 +6,12 @@ walk (ME_GW_CANCEL=1), the deep generic kernel (L = 1,024, ME_HOT_MIN=0), the ag
 a symbol above ME_HOT_MIN) and k_match_hot (L = 2,048, ME_HOT_AGG=0). An IOC priced inside the window runs
 natively on the fast walks; FOK and POST_ONLY hand their symbol to the generic loops.
 """
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 from tests import tif_model as tm
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
+from tests.feed_common import PATHS, SMALL, _env  # (other test files import them from here)
 from tests.tif_model import TIF_FOK, TIF_GTC, TIF_IOC, TIF_POST_ONLY, TifBook, kind
 
 pytestmark = pytest.mark.gpu
@@ -21,37 +19,11 @@ pytestmark = pytest.mark.gpu
 BUY, SELL = 1, 2
 ST_NEW, ST_FILLED, ST_CANCELED, ST_REJECTED = 0, 2, 3, 4
 
-# name -> (levels, environment, expected eng.paths(), grouped)
-PATHS = {
-    "reg": (128, {"ME_REG_AGG": "0"}, {"grouped_agg": False}, True),
-    "gwalk": (128, {"ME_REG_AGG": "1", "ME_GW_CANCEL": "0"}, {"grouped_agg": True, "grouped_cancels": False}, True),
-    "gwalk_cx": (128, {"ME_REG_AGG": "1", "ME_GW_CANCEL": "1"}, {"grouped_agg": True, "grouped_cancels": True}, True),
-    "deep": (1024, {"ME_HOT_MIN": "0"}, {"hot_agg": False}, False),
-    "hot_agg": (1024, {"ME_HOT_MIN": "200", "ME_HOT_AGG": "1"}, {"hot_agg": True}, False),
-    "hot": (2048, {"ME_HOT_MIN": "200", "ME_HOT_AGG": "0"}, {"hot_agg": False}, False),
-}
-SMALL = ("reg", "gwalk", "gwalk_cx")
-
-
 @pytest.fixture(scope="module")
 def me(built):
     import matching_engine_amd
 
     return matching_engine_amd
-
-
-@contextlib.contextmanager
-def _env(env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
 
 
 def _engine(me, path, S, base, batches, env_over=None, **kw):
