@@ -32,6 +32,7 @@
 // exist on the side it crosses) hands the symbol's remaining records to k_match_hot_cont, the generic
 // record loop, exactly as k_match_hot does; the HBM book is complete before it runs.
 // Same semantics and HBM layout as k_match (me_kernels.hip); parity: tests/test_hot_path.py.
+#include "me_launch.hpp"
 #include "me_wave.hpp"
 #include "me_far.hpp"  // old_lookup (k_agg_gwalk_cx)
 

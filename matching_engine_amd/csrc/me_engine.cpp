@@ -19,6 +19,7 @@
 
 #include "me_engine.h"
 #include "me_feed.hpp"
+#include "me_launch.hpp"
 #include "me_layout.hpp"
 
 static_assert(me::ME_C == ME_CHUNK_SLOTS, "chunk width mismatch");
@@ -26,34 +27,6 @@ static_assert(sizeof(me_fill) == 32, "me_fill must be 32 B");
 static_assert(sizeof(me_order_result) == 20, "me_order_result must be 20 B");
 static_assert(sizeof(me_quote) == 48, "me_quote must be 48 B");
 static_assert(sizeof(me_depth_event) == 32, "me_depth_event must be 32 B");
-
-namespace me {
-hipError_t launch_sort_pass(hipStream_t st, const uint32_t* keys_in, const uint32_t* idx_in, uint32_t n,
-                            uint32_t clamp_key, int shift, int dbits, uint32_t* hist, uint32_t* tot,
-                            uint32_t* keys_out, uint32_t* idx_out, uint32_t* zero_buf,
-                            uint32_t zero_words, unsigned long long* scratch_top, uint32_t* bin_start,
-                            const uint64_t* seq, const uint8_t* kind, uint32_t* err);
-hipError_t launch_seq_sweep(hipStream_t st, const BookDev& bk, const uint64_t* const* seq, const uint8_t* const* kind,
-                            const uint32_t* n, uint32_t ng, uint32_t in_idx, uint32_t grid, uint32_t launch);
-hipError_t launch_match(hipStream_t st, const BookDev& bk, const BatchDev& bt, hipEvent_t ev0, hipEvent_t ev1,
-                        const HotLaunch& hot);
-hipError_t launch_match_reg(hipStream_t st, const BookDev& bk, const BatchDev* bt, uint32_t ng, const AuxDev& ax, hipEvent_t ev0,
-                            hipEvent_t ev1, const HotLaunch* hot);
-namespace rc64 {
-hipError_t launch_fill_early(hipStream_t st, const BookDev& bk, const AuxDev& ax, bool& done);
-}
-uint32_t sort_tile(uint32_t n);
-hipError_t launch_tape(hipStream_t st, const BatchDev& bt, me_fill* tape, unsigned long long tape_cap,
-                       unsigned long long* tape_count, unsigned long long* fills_acc, uint32_t* err,
-                       me_order_result* hres, uint32_t* err_out);
-hipError_t launch_tape_spill(hipStream_t st, const me_order_result* res, const uint32_t* fstart, uint32_t n,
-                             const me_fill* scratch, unsigned long long cap, me_fill* spill);
-hipError_t launch_init_levels(hipStream_t st, Level* levels, size_t count);
-hipError_t launch_book_snapshot(hipStream_t st, const BookDev& bk, const SnapReq& rq);
-hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q);
-hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d);
-hipError_t launch_init_chunks(hipStream_t st, Chunk* chunks, size_t count);
-}  // namespace me
 
 using namespace me;
 
@@ -276,7 +249,11 @@ struct me_engine {
   // ME_EARLY_FILL). Config 2's driver shape, same box: 8 -> +1.6 % over off (-0.6 to +2.4 % for earlier
   // forms), 4 and 16 no better (profiles/r6/early_fill).
   uint32_t early_fill = 8;
-  uint32_t group = 1;     // batches per launch (me_config.batches_per_launch)
+  // A launch with no match job (the pipeline's fill and drain): k_side's bucket units per XCD in turn, one
+  // batch's buckets per L2 at a time (AuxDev::xseq; driver shape +1 %, profiles/r5/fx); ME_FILL_XSEQ=0: all
+  // at once
+  uint32_t fill_xseq = 1;
+  uint32_t group = 1;    // batches per launch (me_config.batches_per_launch)
   uint64_t ngroup = 0;    // groups launched
   int last_tape = 0;      // tape buffer (position in its group) of the most recent batch
   uint32_t ncu = 0;  // compute units: workgroups of one dispatch round host the side jobs
@@ -686,6 +663,7 @@ extern "C" me_engine* me_create(const me_config* cfg) {
     const int gw = vw ? atoi(vw) : 0;
     e->hot.ag.gres_waves = gw == 4 || gw == 8 ? (uint32_t)gw : 0u;
     if (const char* ve = getenv("ME_EARLY_FILL")) e->early_fill = (uint32_t)atoi(ve);  // (0: off)
+    if (const char* vx = getenv("ME_FILL_XSEQ")) e->fill_xseq = atoi(vx) != 0 ? 1u : 0u;
     // the grouped aggregate path's side jobs on a stream of their own (ME_SIDE_STREAM=0: in line)
     const char* vs = getenv("ME_SIDE_STREAM");
     if (e->hot.agg_reg && !(vs && atoi(vs) == 0)) {
@@ -1092,6 +1070,7 @@ static int pipe_launch(me_engine* e, const me_engine::Group* nb) {
   }
   ax.S = e->bk.S;
   ax.nwg = e->ncu;
+  if (!gm.n) ax.xseq = e->fill_xseq;  // side jobs only (beside a match the dispatcher decides)
   if (nb) {
     ax.nb = nb->n - nb->filled;
     for (uint32_t j = 0; j < ax.nb; ++j) bucket_job(e, nb->b[nb->filled + j], ax.b[j]);
@@ -1191,9 +1170,10 @@ static int early_fill(me_engine* e) {
   ax.nb = gf.n - gf.filled;
   for (uint32_t j = 0; j < ax.nb; ++j) bucket_job(e, gf.b[gf.filled + j], ax.b[j]);
   ax.fills_acc = e->d_fills_acc;
+  ax.xseq = e->fill_xseq;
   bool done = false;
-  hipError_t he = rc64::launch_fill_early(e->stream, e->bk, ax, done);
-  if (he == hipSuccess && !done) he = launch_match_reg(e->stream, e->bk, nullptr, 0, ax, nullptr, nullptr, &e->hot);
+  hipError_t he = launch_side_fill(e->stream, e->bk.err, ax, done);
+  if (he == hipSuccess && !done) he = launch_side(e->stream, e->bk.err, ax, nullptr, nullptr);
   if (he != hipSuccess) return e->hip_fail(he, "early fill launch");
   gf.filled = gf.n;
   return ME_OK;

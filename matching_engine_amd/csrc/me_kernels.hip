@@ -18,9 +18,9 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
+#define ME_LAUNCH_REG_VARIANTS
 #include "me_far.hpp"
+#include "me_launch.hpp"
 #include "me_layout.hpp"
 #include "me_wave.hpp"
 
@@ -2744,31 +2744,22 @@ hipError_t launch_sort_pass(hipStream_t st, const uint32_t* keys_in, const uint3
   return hipGetLastError();
 }
 
-namespace rc64 {
-hipError_t launch_match_reg(hipStream_t st, const BookDev& bk, const BatchDev* bt, uint32_t ng, const AuxDev& ax,
-                            hipEvent_t ev0, hipEvent_t ev1);
-hipError_t launch_match_reg_cont(hipStream_t st, const BookDev& bk, const BatchDev* bt, uint32_t ng, hipEvent_t ev1);
-}
-namespace rc128 {
-hipError_t launch_match_reg(hipStream_t st, const BookDev& bk, const BatchDev* bt, uint32_t ng, const AuxDev& ax,
-                            hipEvent_t ev0, hipEvent_t ev1);
-hipError_t launch_match_reg_cont(hipStream_t st, const BookDev& bk, const BatchDev* bt, uint32_t ng, hipEvent_t ev1);
-}
-hipError_t launch_agg_group(hipStream_t st, const BookDev& bk, const BatchDev* bt, uint32_t ng, const AggDev& ag);  // me_agg.hip
 // The register-ladder launch (me_match_reg.hip, two builds): one head-cache entry per level while one
 // workgroup per CU covers the symbols (rc128), 64 shared entries and two workgroups per CU beyond
-// that (rc64). ax.nwg is the CU count (0: assume 256).
+// that (rc64). ax.nwg is the CU count (0: assume 256). Side jobs with no match job beside them in their
+// launch go to launch_side (me_side.hip): ax.xseq as the caller set it, but for the forked launch.
 #ifndef ME_SIDE_XSEQ
 #define ME_SIDE_XSEQ 1
 #endif
 hipError_t launch_match_reg(hipStream_t st, const BookDev& bk, const BatchDev* bt, uint32_t ng, const AuxDev& ax,
                             hipEvent_t ev0, hipEvent_t ev1, const HotLaunch* hot) {
+  if (ng == 0) return launch_side(st, bk.err, ax, ev0, ev1);  // the pipeline's fill and drain
   constexpr uint32_t kWaves = 4;  // matching waves per workgroup (me_match_reg.hip REG_WAVES)
-  const uint32_t waves = ng && bt[0].bcnt ? bk.S : bk.S + 1;
+  const uint32_t waves = bt[0].bcnt ? bk.S : bk.S + 1;
   const uint32_t wgs = (waves + kWaves - 1) / kWaves;
   const uint32_t ncu = ax.nwg ? ax.nwg : 256u;
   const bool big = wgs > ncu;
-  if (hot && hot->agg_reg && ng && bt[0].bcnt) {
+  if (hot && hot->agg_reg && bt[0].bcnt) {
     // the group through the aggregate path: side jobs (k_side), walk + per-level kernels, continuation
     hipError_t e;
     const bool side = ax.nb || ax.nt, fork = side && hot->sst;
@@ -2780,13 +2771,11 @@ hipError_t launch_match_reg(hipStream_t st, const BookDev& bk, const BatchDev* b
         return e;
       AuxDev sx = ax;
       sx.xseq = ME_SIDE_XSEQ;  // off the critical path: bucket the batches per XCD in turn (fewer partial lines)
-      e = big ? rc64::launch_match_reg(hot->sst, bk, bt, 0, sx, nullptr, nullptr)
-              : rc128::launch_match_reg(hot->sst, bk, bt, 0, sx, nullptr, nullptr);
+      e = launch_side(hot->sst, bk.err, sx, nullptr, nullptr);
       if (e != hipSuccess || (e = hipEventRecord(hot->sjoin, hot->sst)) != hipSuccess) return e;
       e = ev0 ? hipEventRecord(ev0, st) : hipSuccess;
     } else if (side) {
-      e = big ? rc64::launch_match_reg(st, bk, bt, 0, ax, ev0, nullptr)
-              : rc128::launch_match_reg(st, bk, bt, 0, ax, ev0, nullptr);
+      e = launch_side(st, bk.err, ax, ev0, nullptr);
     } else {
       e = ev0 ? hipEventRecord(ev0, st) : hipSuccess;
     }
@@ -2798,24 +2787,14 @@ hipError_t launch_match_reg(hipStream_t st, const BookDev& bk, const BatchDev* b
     // after this (host batches' tapes) wait for the side jobs
     return fork ? hipStreamWaitEvent(st, hot->sjoin, 0) : hipSuccess;
   }
-  // a launch with no match job (the pipeline's fill and drain): its bucket units too per XCD in turn (one
-  // batch's buckets per L2 at a time; driver shape +1 %, profiles/r5/fx); ME_FILL_XSEQ=0: all at once
-  static const bool fill_xseq = [] {
-    const char* e = getenv("ME_FILL_XSEQ");
-    return !e || atoi(e) != 0;
-  }();
-  AuxDev axx = ax;
-  if (ng == 0 && fill_xseq) axx.xseq = 1u;
-  return big ? rc64::launch_match_reg(st, bk, bt, ng, axx, ev0, ev1)
-             : rc128::launch_match_reg(st, bk, bt, ng, axx, ev0, ev1);
+  return big ? rc64::launch_match_reg(st, bk, bt, ng, ax, ev0, ev1)
+             : rc128::launch_match_reg(st, bk, bt, ng, ax, ev0, ev1);
 }
 
 // ev0 / ev1 (optional, timing): the launch records the kernel's own start and end
 // (hipExtLaunchKernelGGL), so timing adds no marker packet — and no gap — to the stream.
 // hot (deep windows with bk.hot_min): the stream and fork / join events k_match_hot runs with, beside
 // k_match (same symbols never meet: k_match skips what k_hot_pick listed).
-hipError_t launch_agg(hipStream_t hs, const BookDev& bk, const BatchDev& bt, const AggDev& ag);  // me_agg.hip
-
 hipError_t launch_match(hipStream_t st, const BookDev& bk, const BatchDev& bt, hipEvent_t ev0, hipEvent_t ev1,
                         const HotLaunch& hot) {
   const uint32_t waves = bk.S + 1;

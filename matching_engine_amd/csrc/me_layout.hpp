@@ -1,6 +1,6 @@
 // me_layout.hpp — HBM layout of the resident books and of one in-flight batch.
 //
-// Shared by the gfx950 kernels (me_kernels.hip, me_match_reg.hip) and the host engine
+// Shared by the gfx950 kernels (me_kernels.hip, me_match_reg.hip, me_side.hip) and the host engine
 // (me_engine.cpp). Everything is plain-old-data; the host allocates, the kernels own the contents.
 //
 // Book of one shard. Prices are unbounded int64 Q4 (include/domain/price.hpp:6):
@@ -423,9 +423,10 @@ struct BatchDev {
   uint32_t bcap;
 };
 
-// Side jobs of one pipelined register-ladder launch (me_match_reg.hip), run by each workgroup's
-// extra waves while its matching waves work on group J-1: group the batches of group J into their
-// buckets (and clear the output counters they will use), compact the tapes of group J-2.
+// Side jobs of one pipelined launch (device code: me_side.hpp), beside the match of group J-1: group the
+// batches of group J into their buckets (and clear the output counters they will use), compact the tapes
+// of group J-2. Run by the extra waves of k_match_reg's workgroups (me_match_reg.hip aux_jobs) or by the
+// side kernels k_side / k_side_fill (me_side.hip).
 struct AuxBucket {  // bucket + clear job of one batch
   const uint32_t* sym;
   const uint64_t* seq;
@@ -463,7 +464,7 @@ struct AuxDev {
   uint32_t nwg;  // workgroups that run side jobs (those of the first dispatch round)
   uint32_t nb;   // bucket jobs (batches of group J)
   uint32_t nt;   // tape jobs (batches of group J-2)
-  uint32_t xseq; // k_side beside a walk: each XCD buckets its batches one after another (me_match_reg.hip)
+  uint32_t xseq; // k_side only (me_side.hip): each XCD buckets its batches one after another, not all at once
   uint32_t rsv;
   unsigned long long* fills_acc;
   AuxBucket b[ME_GMAX];

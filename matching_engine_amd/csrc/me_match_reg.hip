@@ -33,8 +33,11 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#define ME_LAUNCH_REG_VARIANTS
 #include "me_far.hpp"
+#include "me_launch.hpp"
 #include "me_layout.hpp"
+#include "me_side.hpp"
 #include "me_wave.hpp"
 
 // Compiled twice (Makefile): rc128 (a head-chunk cache entry per level, one workgroup per CU) and
@@ -164,38 +167,6 @@ struct ColdArgs {
   uint32_t ng;
   uint32_t pad;
 };
-
-// A wave-uniform value read from LDS at the point of use. A relaxed atomic load is never hoisted out
-// of a loop (a plain load would be, pinning the value in SGPRs for the whole loop) and, unlike a
-// volatile one, keeps its LDS address space (ds_read, not flat); readfirstlane makes it scalar.
-template <class T>
-__device__ __forceinline__ T ldsu(const T& f) {
-  static_assert(sizeof(T) == 8 || sizeof(T) == 4, "ldsu: 4- or 8-byte values");
-  if constexpr (sizeof(T) == 8) {
-    const unsigned long long v = __hip_atomic_load((const unsigned long long*)&f, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
-    // readfirstlane (first ACTIVE lane): readlane 0 may read an inactive lane in a divergent branch
-    const unsigned long long r =
-        ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    return __builtin_bit_cast(T, r);
-  } else {
-    const uint32_t v = __hip_atomic_load((const uint32_t*)&f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return __builtin_bit_cast(T, (uint32_t)__builtin_amdgcn_readfirstlane((int)v));
-  }
-}
-
-// A pointer launch argument read from LDS, as a global-address-space pointer (global_* ops).
-template <class T>
-__device__ __forceinline__ gptr<T> ldsg(T* const& f) {
-  return (gptr<T>)ldsu(reinterpret_cast<const unsigned long long&>(f));
-}
-
-// Store a wave-uniform 32-bit value into the wave's LDS (lane 0; read back with ldsu).
-__device__ __forceinline__ void ldsw(uint32_t& f, uint32_t v) {
-  if (lane_id() == 0) __hip_atomic_store(&f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
 
 struct RegCtx {
   gptr<Chunk> chunks;    // VGPR
@@ -934,19 +905,6 @@ __device__ __forceinline__ bool rescan_window(RegLds* M, const ColdArgs& G, uint
   return false;
 }
 
-// (pipelined path: no fill start of its own — the tape job reads a record's scratch start from its
-// result's tape_offset, see aux_tape_tile)
-__device__ __forceinline__ void reject_bad_at(gptr<me_order_result> res, uint32_t i) {
-  me_order_result r;
-  r.filled_qty = 0;
-  r.remaining_qty = 0;
-  r.fill_count = 0;
-  r.tape_offset = 0;
-  r.status = ME_ST_REJECTED;
-  r.reason = ME_RJ_BAD_SYMBOL;
-  r.pad[0] = r.pad[1] = 0;
-  res[i] = r;
-}
 __device__ __forceinline__ void reject_bad(const ColdArgs& G, uint32_t g, uint32_t i, bool v) {
   if (!v) return;
   me_order_result r;
@@ -969,133 +927,8 @@ __device__ __forceinline__ void reject_bad_run(const ColdArgs& G, uint32_t lo, u
 
 // ---- side jobs of a pipelined launch (the workgroup's waves REG_WAVES .. 2*REG_WAVES-1) -------
 // Memory-latency work with few instructions, so sharing the SIMDs with the matching waves costs
-// them little; what it saves is two launches per batch.
-
-// Bucket job: records [r0, r1) of bucket job j, one returning atomic per record on its bin's counter.
-template <class GA>
-__device__ __forceinline__ void aux_bucket(const GA& G, uint32_t j, uint32_t r0, uint32_t r1) {
-  const int lane = lane_id();
-  const AuxBucket& J = G.ax.b[j];
-  const gptr<const uint32_t> sym = ldsg(J.sym);
-  const gptr<const uint64_t> seq = ldsg(J.seq);
-  const gptr<const int64_t> px = ldsg(J.px);
-  const gptr<const int32_t> qty = ldsg(J.qty);
-  const gptr<const uint8_t> kind = ldsg(J.kind);
-  const gptr<uint32_t> bcnt = ldsg(J.bcnt);
-  const gptr<BkRec> brec = ldsg(J.b_rec);
-  const uint32_t S = ldsu(G.ax.S);
-  const gptr<me_order_result> bres = ldsg(J.bres);
-  bool order_ok = true;
-  for (uint32_t i0 = r0; i0 < r1; i0 += 64) {
-    const uint32_t i = i0 + (uint32_t)lane;
-    if (i < r1) {
-      const uint32_t k = kind[i];
-      // API precondition (the seq ring relies on it): seqs ascending through the batch (seq_follows)
-      if (i > 0) order_ok &= seq_follows(seq[i - 1], seq[i], k);
-      const uint32_t b = min(sym[i], S);
-      if (b == S) {  // unknown symbol: rejected here, never bucketed (the batch's result set is free)
-        reject_bad_at(bres, i);
-        continue;
-      }
-      const uint64_t sq = seq[i];  // the payload loads are in flight while the atomic returns
-      const int64_t p = px[i];
-      const int32_t q = qty[i];
-      const uint32_t r = atomicAdd(&bcnt[(size_t)b * BK_CNT_STRIDE], 1u);
-      if (r < (uint32_t)BK_CAP) {
-        const size_t d = (size_t)b * BK_CAP + r;
-        brec[d].seq = sq;
-        brec[d].px = p;
-        brec[d].qty = q;
-        brec[d].ok = i | ((k & BK_KIND_BITS) << BK_KIND_SHIFT);
-      }
-    }
-  }
-  if (__ballot(!order_ok) && lane == 0) atomicOr(ldsg(G.bk.err), ERR_SEQ_ORDER);
-}
-
-// Tape job j, one TILE_TAPE-record tile per wave: tape offsets of its records and the copy of their
-// fills from scratch into the batch's tape (ordered by taker seq).
-template <class GA>
-__device__ __forceinline__ void aux_tape_tile(const GA& G, uint32_t jb, uint32_t t, uint32_t ntiles,
-                                              uint32_t tn) {
-  const int lane = lane_id();
-  const AuxTape& J = G.ax.t[jb];
-  const gptr<const uint32_t> tile_sum = ldsg(J.tile_sum);
-  const gptr<me_order_result> res = ldsg(J.res);
-  const gptr<const me_fill> scratch = ldsg(J.scratch);
-  const gptr<me_fill> tape = ldsg(J.tape);
-  const gptr<me_order_result> hres = ldsg(J.hres);
-  const bool host = hres != nullptr;  // a host batch: soft tape cap, results and scratch starts kept
-  const unsigned long long cap = ldsu(J.cap);
-  long long acc = 0;  // fills of the earlier tiles
-  for (uint32_t u = (uint32_t)lane; u < t; u += 64) acc += tile_sum[u];
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-  const unsigned long long base = (unsigned long long)rli64(acc, 0);
-  const uint32_t r0 = t * TILE_TAPE;
-  const uint32_t cnt = min((uint32_t)TILE_TAPE, tn - r0);
-  uint32_t c[TILE_TAPE / 64], src[TILE_TAPE / 64];
-  long long loc = 0;
-#pragma unroll
-  for (int k = 0; k < TILE_TAPE / 64; ++k) {  // lane holds records 4*lane .. 4*lane+3 of the tile
-    const uint32_t j = (uint32_t)(lane * (TILE_TAPE / 64) + k);
-    // the match job left the record's scratch start in tape_offset (same line as fill_count)
-    c[k] = j < cnt ? res[r0 + j].fill_count : 0u;
-    src[k] = j < cnt ? res[r0 + j].tape_offset : 0u;
-    loc += c[k];
-  }
-  const long long incl = wave_incl_scan(loc);
-  const uint32_t total = (uint32_t)rli64(incl, 63);
-  uint32_t o = (uint32_t)(incl - loc);
-#pragma unroll
-  for (int k = 0; k < TILE_TAPE / 64; ++k) {
-    const uint32_t j = (uint32_t)(lane * (TILE_TAPE / 64) + k);
-    if (j < cnt) res[r0 + j].tape_offset = (uint32_t)(base + o);
-    o += c[k];
-  }
-  if (host) {  // the slot's copy of the final results; the scratch starts stay for me_collect's spill
-    const gptr<uint32_t> fst = ldsg(J.fstart);
-    uint32_t o3 = (uint32_t)(incl - loc);
-#pragma unroll
-    for (int k = 0; k < TILE_TAPE / 64; ++k) {
-      const uint32_t j = (uint32_t)(lane * (TILE_TAPE / 64) + k);
-      if (j < cnt) {
-        me_order_result r = res[r0 + j];  // written by the match job of an earlier launch
-        r.tape_offset = (uint32_t)(base + o3);
-        hres[r0 + j] = r;
-        fst[r0 + j] = src[k];
-      }
-      o3 += c[k];
-    }
-  } else if (base + total > cap) {
-    if (lane == 0) atomicOr(ldsg(G.bk.err), ERR_SCRATCH_OOM);
-    return;
-  }
-  // The tile's fills are one contiguous tape run [base, base + total): lane i copies fill f0 + i, found
-  // by a binary search over the lanes' exclusive offsets (one record per lane), so every store
-  // instruction writes 64 consecutive 32-B records — whole lines in HBM, full-size PCIe writes when
-  // the tape is a host slot's pinned buffer.
-  static_assert(TILE_TAPE == 64, "one record per lane");
-  {
-    const uint32_t ex = (uint32_t)(incl - loc);
-    for (uint32_t f0 = 0; f0 < total; f0 += 64) {
-      const uint32_t f = f0 + (uint32_t)lane;
-      int lo = 0;  // last lane whose exclusive offset is <= f: the record that owns fill f
-#pragma unroll
-      for (int step = 32; step >= 1; step >>= 1) {
-        const uint32_t e = (uint32_t)__shfl((int)ex, min(lo + step, 63), 64);
-        if (lo + step < 64 && e <= f) lo += step;
-      }
-      const uint32_t s0 = (uint32_t)__shfl((int)src[0], lo, 64);
-      const uint32_t e0 = (uint32_t)__shfl((int)ex, lo, 64);
-      if (f < total && base + f < cap) tape[base + f] = scratch[s0 + (f - e0)];
-    }
-  }
-  if (t == ntiles - 1 && lane == 0) {
-    *ldsg(J.tape_count) = base + total;
-    atomicAdd(ldsg(G.ax.fills_acc), base + total);
-    if (host) *ldsg(J.err_out) = __hip_atomic_load(ldsg(G.bk.err), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
+// them little; what it saves is two launches per batch. The jobs themselves (aux_bucket,
+// aux_tape_tile) are me_side.hpp's, shared with the side kernels of me_side.hip.
 
 // Side-job wave k of side workgroup b (of nwg): its share of every bucket / clear job of group J and
 // every tape job of J-2. A batch's bucket job runs on the side waves of the
@@ -1125,232 +958,6 @@ __device__ __forceinline__ void aux_jobs(const ColdArgs& G, uint32_t b, uint32_t
     const uint32_t tn = ldsu(G.ax.t[j].tn);
     const uint32_t ntiles = (tn + TILE_TAPE - 1) / TILE_TAPE;
     for (uint32_t t = a; t < ntiles; t += A) aux_tape_tile(G, j, t, ntiles, tn);
-  }
-}
-
-// ---- launches with no match job: the side jobs alone ------------------------------------------
-// The pipeline's first launch of a run (bucket only) and its last (tape only) have no matching waves to
-// hide behind: in k_match_reg they ran on its 4 side waves per CU (one 145-KB workgroup per CU), 74 and
-// 87 us for a 20-batch group at config 2. k_side carries only the side jobs' arguments in LDS.
-//  * bucket: one workgroup per SB_REC records of a batch counts its records per symbol in LDS, then
-//    reserves each symbol's run with ONE returning global atomic (device-scope atomics execute at the
-//    memory side, one request each: one per record capped the fill launch at ~20 G records/s), then
-//    writes the records at run + rank. A bucket's order is free (the match wave sorts by batch index).
-//    Needs (S + 1) counters in LDS; above SB_SMAX symbols the waves bucket 64-record blocks with one
-//    atomic per record as the pipelined launch does.
-//  * tape: tiles dealt round-robin to the tape waves over a list flattened across the group's batches.
-struct SideArgs {
-  struct {
-    uint32_t* err;
-  } bk;
-  AuxDev ax;
-};
-#ifndef ME_SIDE_THREADS
-#define ME_SIDE_THREADS 512
-#endif
-#ifndef ME_SB_REC
-#define ME_SB_REC 2048  // records per bucket workgroup: same box, config 2's driver shape 1,818-1,836M at 4,096,
-                        // 1,911-1,918M at 2,048, 1,804-1,820M at 1,024; 640 steps 2,561 / 2,604 / 2,572M; config
-                        // 3 1,301 / 1,317M (profiles/r4/sb) — the group's walk + resolve 549 -> 514 us
-#endif
-constexpr int SIDE_THREADS = ME_SIDE_THREADS;
-constexpr int SIDE_WAVES = SIDE_THREADS / 64;
-#ifndef ME_TAPE_XCD
-#define ME_TAPE_XCD 1  // tape tiles: each half of a batch's tape on one XCD (1) or dealt over all (0); profiles/r5/tx
-#endif
-constexpr uint32_t SB_REC = ME_SB_REC;             // records per bucket workgroup
-constexpr uint32_t SB_PER = SB_REC / SIDE_THREADS;  // records per thread
-constexpr uint32_t SB_SMAX = 16383;                // symbols bucketed through an LDS histogram (64 KB)
-
-// Units [off, off + cnt) of a list flattened over batches, dealt round-robin to waves: wave a's first.
-__device__ __forceinline__ uint32_t flat_first(uint32_t off, uint32_t a, uint32_t A) {
-  return off + (a + A - off % A) % A;
-}
-
-// The early fill's launch (me_engine.cpp early_fill): bucket jobs only, at most FILL_NB of them — a
-// ~0.8-KB argument block instead of SideArgs' ~5.7 KB (the host's launch call is the early fill's cost:
-// ~13 us per launch with SideArgs).
-constexpr uint32_t FILL_NB = 8;
-struct FillArgs {
-  struct {
-    uint32_t* err;
-  } bk;
-  struct {
-    uint32_t S, nb;
-    AuxBucket b[FILL_NB];
-  } ax;
-};
-
-// Bucket records [r0, r1) of bucket job j with a workgroup histogram (cnt: S + 1 LDS counters).
-template <class GA>
-__device__ __forceinline__ void side_bucket_wg(const GA& G, uint32_t j, uint32_t r0, uint32_t r1, uint32_t* cnt) {
-  const uint32_t tid = threadIdx.x;
-  const AuxBucket& J = G.ax.b[j];
-  const uint32_t S = ldsu(G.ax.S);
-  const gptr<const uint32_t> sym = ldsg(J.sym);
-  const gptr<const uint64_t> seq = ldsg(J.seq);
-  const gptr<const int64_t> px = ldsg(J.px);
-  const gptr<const int32_t> qty = ldsg(J.qty);
-  const gptr<const uint8_t> kind = ldsg(J.kind);
-  const gptr<uint32_t> bcnt = ldsg(J.bcnt);
-  const gptr<BkRec> brec = ldsg(J.b_rec);
-  const gptr<me_order_result> bres = ldsg(J.bres);
-  for (uint32_t b = tid; b <= S; b += SIDE_THREADS) cnt[b] = 0u;
-  {  // the tile sums of this record range, and the batch's scratch top, start at zero
-    const gptr<uint32_t> z = ldsg(J.zero_tile_sum);
-    const uint32_t t1 = min((r1 + TILE_TAPE - 1) / TILE_TAPE, ldsu(J.zero_tiles));
-    for (uint32_t t = r0 / TILE_TAPE + tid; t < t1; t += SIDE_THREADS) z[t] = 0u;
-    if (r0 == 0 && tid == 0) *ldsg(J.zero_top) = 0ull;
-  }
-  __syncthreads();
-  uint32_t bin[SB_PER], rank[SB_PER];
-  uint64_t sq[SB_PER];
-  int64_t p[SB_PER];
-  int32_t q[SB_PER];
-  uint32_t k8[SB_PER];
-  bool order_ok = true;
-#pragma unroll
-  for (uint32_t k = 0; k < SB_PER; ++k) {
-    const uint32_t i = r0 + k * SIDE_THREADS + tid;
-    bin[k] = S;
-    if (i < r1) {
-      bin[k] = min(sym[i], S);
-      sq[k] = seq[i];
-      p[k] = px[i];
-      q[k] = qty[i];
-      k8[k] = kind[i];
-      // API precondition (the seq ring relies on it): seqs ascending through the batch (seq_follows)
-      if (i > 0) order_ok &= seq_follows(seq[i - 1], sq[k], k8[k]);
-    }
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < SB_PER; ++k) {
-    const uint32_t i = r0 + k * SIDE_THREADS + tid;
-    if (i < r1 && bin[k] == S) reject_bad_at(bres, i);  // unknown symbol: rejected here, never bucketed
-    if (bin[k] < S) rank[k] = atomicAdd(&cnt[bin[k]], 1u);
-  }
-  if (__ballot(!order_ok) && lane_id() == 0) atomicOr(ldsg(G.bk.err), ERR_SEQ_ORDER);
-  __syncthreads();
-  for (uint32_t b = tid; b < S; b += SIDE_THREADS) {
-    const uint32_t c = cnt[b];
-    if (c) cnt[b] = atomicAdd(&bcnt[(size_t)b * BK_CNT_STRIDE], c);
-  }
-  __syncthreads();
-#pragma unroll
-  for (uint32_t k = 0; k < SB_PER; ++k) {
-    if (bin[k] >= S) continue;
-    const uint32_t r = cnt[bin[k]] + rank[k];
-    if (r < (uint32_t)BK_CAP) {
-      const uint32_t i = r0 + k * SIDE_THREADS + tid;
-      const size_t d = (size_t)bin[k] * BK_CAP + r;
-      brec[d].seq = sq[k];
-      brec[d].px = p[k];
-      brec[d].qty = q[k];
-      brec[d].ok = i | ((k8[k] & BK_KIND_BITS) << BK_KIND_SHIFT);
-    }
-  }
-}
-
-// Grid: 8 x the most units a batch has; batch j on the blocks b = j (mod 8), its units in turn (k_side's
-// xseq form, one batch per XCD).
-__global__ __launch_bounds__(SIDE_THREADS) void k_side_fill(FillArgs args) {
-  __shared__ FillArgs G;
-  extern __shared__ uint32_t side_cnt[];
-  static_assert(sizeof(FillArgs) % 8 == 0, "FillArgs copy");
-  for (uint32_t i = threadIdx.x; i < sizeof(FillArgs) / 8; i += SIDE_THREADS)
-    reinterpret_cast<unsigned long long*>(&G)[i] = reinterpret_cast<const unsigned long long*>(&args)[i];
-  __syncthreads();
-  const uint32_t nb = ldsu(G.ax.nb), x = blockIdx.x % 8u, k = blockIdx.x / 8u;
-  for (uint32_t j = x; j < nb; j += 8) {
-    const uint32_t n = ldsu(G.ax.b[j].n), r0 = k * SB_REC;
-    if (r0 >= n) continue;  // (uniform over the workgroup)
-    side_bucket_wg(G, j, r0, min(n, r0 + SB_REC), side_cnt);
-    __syncthreads();  // the LDS counters are zeroed again by the next batch
-  }
-}
-
-// Grid: [0, nbu) bucket workgroups (histogram path; 0 on the per-record path), then tape workgroups.
-__global__ __launch_bounds__(SIDE_THREADS) void k_side(SideArgs args, uint32_t nbu) {
-  __shared__ SideArgs G;
-  extern __shared__ uint32_t side_cnt[];
-  static_assert(sizeof(SideArgs) % 8 == 0, "SideArgs copy");
-  for (uint32_t i = threadIdx.x; i < sizeof(SideArgs) / 8; i += SIDE_THREADS)
-    reinterpret_cast<unsigned long long*>(&G)[i] = reinterpret_cast<const unsigned long long*>(&args)[i];
-  __syncthreads();
-  const int lane = lane_id();
-  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t nb = ldsu(G.ax.nb);
-  if (blockIdx.x < nbu) {  // histogram bucket unit: batch j, records [u * SB_REC, ...)
-    // Blocks b and b + 8 share an XCD (round-robin placement; speed only): every unit of batch j runs
-    // on blocks b = j (mod 8), so the runs its workgroups write side by side into one bucket array
-    // meet in one L2 and leave it as whole lines, not as partial lines from several XCDs.
-    const uint32_t x = blockIdx.x % 8u, k = blockIdx.x / 8u;
-    if (ldsu(G.ax.xseq)) {
-      // beside a walk (off the critical path): unit k of each of the XCD's batches in turn, so one
-      // batch's buckets (1.5 MB at config 2) are being filled per L2 at a time, not four batches' 6 MB
-      // whose partial lines the 4-MB L2 evicts before the later units complete them (profiles/r4/xs)
-      for (uint32_t j = x; j < nb; j += 8) {
-        const uint32_t n = ldsu(G.ax.b[j].n), r0 = k * SB_REC;
-        if (r0 >= n) continue;  // (uniform over the workgroup)
-        side_bucket_wg(G, j, r0, min(n, r0 + SB_REC), side_cnt);
-        __syncthreads();  // the LDS counters are zeroed again by the next batch
-      }
-      return;
-    }
-    uint32_t off = 0;
-    for (uint32_t j = x; j < nb; j += 8) {
-      const uint32_t n = ldsu(G.ax.b[j].n), nu = (n + SB_REC - 1) / SB_REC;
-      if (k < off + nu) {
-        const uint32_t r0 = (k - off) * SB_REC;
-        side_bucket_wg(G, j, r0, min(n, r0 + SB_REC), side_cnt);
-        return;
-      }
-      off += nu;
-    }
-    return;
-  }
-  const uint32_t A = (gridDim.x - nbu) * SIDE_WAVES, a = (blockIdx.x - nbu) * SIDE_WAVES + wv;
-  uint32_t off = 0;
-  if (nbu == 0) {  // per-record bucket path (too many symbols for the LDS histogram)
-    for (uint32_t j = 0; j < nb; ++j) {
-      const AuxBucket& J = G.ax.b[j];
-      const uint32_t zt = ldsu(J.zero_tiles);
-      const gptr<uint32_t> z = ldsg(J.zero_tile_sum);
-      for (uint32_t i = a * 64u + (uint32_t)lane; i < zt; i += A * 64u) z[i] = 0u;
-      if (a == 0 && lane == 0) *ldsg(J.zero_top) = 0ull;
-      const uint32_t n = ldsu(J.n), nblk = (n + 63u) / 64u;
-      for (uint32_t u = flat_first(off, a, A); u < off + nblk; u += A) {
-        const uint32_t r0 = (u - off) * 64u;
-        aux_bucket(G, j, r0, min(n, r0 + 64u));
-      }
-      off += nblk;
-    }
-  }
-  const uint32_t nt = ldsu(G.ax.nt);
-#if ME_TAPE_XCD
-  // Each half of a batch's tape on one XCD (blocks b = x mod 8 under round-robin placement; speed only): a
-  // 128-B line of a symbol's scratch slab holds fills of takers ~16 tiles apart, so the tiles that read it
-  // meet in one L2 instead of fetching the line once per XCD. Halves, not batches, keep the XCDs balanced.
-  if (gridDim.x - nbu >= 8u) {
-    const uint32_t x = blockIdx.x % 8u;
-    const uint32_t b0 = nbu + (x + 8u - nbu % 8u) % 8u;  // the first tape block on XCD x
-    const uint32_t AX = ((gridDim.x - b0 + 7u) / 8u) * SIDE_WAVES, ax = ((blockIdx.x - b0) / 8u) * SIDE_WAVES + wv;
-    for (uint32_t v = x; v < 2u * nt; v += 8u) {
-      const uint32_t j = v >> 1, h = v & 1u;
-      const uint32_t tn = ldsu(G.ax.t[j].tn);
-      const uint32_t ntiles = (tn + TILE_TAPE - 1) / TILE_TAPE, half = (ntiles + 1u) / 2u;
-      const uint32_t t0 = h * half, t1 = min(ntiles, t0 + half);
-      for (uint32_t t = t0 + ax; t < t1; t += AX) aux_tape_tile(G, j, t, ntiles, tn);
-    }
-    return;
-  }
-#endif
-  off = 0;
-  for (uint32_t j = 0; j < nt; ++j) {
-    const uint32_t tn = ldsu(G.ax.t[j].tn);
-    const uint32_t ntiles = (tn + TILE_TAPE - 1) / TILE_TAPE;
-    for (uint32_t u = flat_first(off, a, A); u < off + ntiles; u += A) aux_tape_tile(G, j, u - off, ntiles, tn);
-    off += ntiles;
   }
 }
 
@@ -1971,35 +1578,17 @@ __global__ __launch_bounds__(128 * REG_WAVES) void k_match_reg(ColdArgs args) {
   }
 }
 
-// One launch: the match job of bt[0, ng) (ng == 0: none) on S / REG_WAVES workgroups (S + 1 for the
-// sort path's bad-symbol bin) and the side jobs of ax on the first dispatch round's extra waves; then,
-// when it matched anything, the continuation launch over the symbols it handed off (one wave per
-// symbol, like the common launch; workgroups with nothing to do leave at once). ev0 / ev1 bracket both.
-// The early fill (bucket jobs of at most FILL_NB batches, symbols within the LDS histogram); false: not
-// this launch's shape (the caller uses launch_match_reg's side launch).
-hipError_t launch_fill_early(hipStream_t st, const BookDev& bk, const AuxDev& ax, bool& done) {
-  done = false;
-  if (ax.nb == 0 || ax.nb > FILL_NB || ax.S > SB_SMAX || ax.nt) return hipSuccess;
-  FillArgs FA{};
-  FA.bk.err = bk.err;
-  FA.ax.S = ax.S;
-  FA.ax.nb = ax.nb;
-  uint32_t per = 0;
-  for (uint32_t j = 0; j < ax.nb; ++j) {
-    FA.ax.b[j] = ax.b[j];
-    per = max(per, (ax.b[j].n + SB_REC - 1) / SB_REC);
-  }
-  hipLaunchKernelGGL(k_side_fill, dim3(8u * max(per, 1u)), dim3(SIDE_THREADS), (size_t)(ax.S + 1) * sizeof(uint32_t),
-                     st, FA);
-  done = true;
-  return hipGetLastError();
-}
-
+// One launch: the match job of bt[0, ng), ng >= 1, on S / REG_WAVES workgroups (S + 1 for the sort
+// path's bad-symbol bin) and the side jobs of ax on the first dispatch round's extra waves; then the
+// continuation launch over the symbols it handed off (one wave per symbol, like the common launch;
+// workgroups with nothing to do leave at once). ev0 / ev1 bracket both. Side jobs with no match job are
+// launch_side's (me_side.hip).
 hipError_t launch_match_reg(hipStream_t st, const BookDev& bk, const BatchDev* bt, uint32_t ng, const AuxDev& ax,
                             hipEvent_t ev0, hipEvent_t ev1) {
   if (bk.L > (uint32_t)RL || bk.L < 64u || !bk.fcache || !bk.gsym || !bk.hand || !bk.hcount)
     return hipErrorInvalidValue;
-  if (ng > (uint32_t)ME_GMAX || ax.nb > (uint32_t)ME_GMAX || ax.nt > (uint32_t)ME_GMAX) return hipErrorInvalidValue;
+  if (!ng || ng > (uint32_t)ME_GMAX || ax.nb > (uint32_t)ME_GMAX || ax.nt > (uint32_t)ME_GMAX)
+    return hipErrorInvalidValue;
   ColdArgs A{};
   A.bk = bk;
   A.ax = ax;
@@ -2010,41 +1599,17 @@ hipError_t launch_match_reg(hipStream_t st, const BookDev& bk, const BatchDev* b
     A.bt[g] = bt[g];
   }
   // bucketed batches carry no bad-symbol bin (the bucket job rejects those records)
-  const uint32_t waves = ng && A.bt[0].bcnt ? bk.S : bk.S + 1;
-  const uint32_t match_wgs = ng ? (waves + REG_WAVES - 1) / REG_WAVES : 0u;
+  const uint32_t waves = A.bt[0].bcnt ? bk.S : bk.S + 1;
+  const uint32_t match_wgs = (waves + REG_WAVES - 1) / REG_WAVES;
   uint32_t nbr = 0, ntr = 0;
   for (uint32_t j = 0; j < ax.nb; ++j) nbr += ax.b[j].n;
   for (uint32_t j = 0; j < ax.nt; ++j) ntr += ax.t[j].tn;
-  if (!ng) {  // side jobs only (the pipeline's fill and drain): k_side, all waves on them
-    SideArgs SA{};
-    SA.bk.err = bk.err;
-    SA.ax = ax;
-    const bool hist = ax.S <= SB_SMAX;
-    uint32_t nbu = 0;
-    if (hist) {  // 8 x the most units any XCD's batches have (batch j on blocks = j mod 8)
-      uint32_t per[8] = {};
-      for (uint32_t j = 0; j < ax.nb; ++j) {
-        const uint32_t nu = (ax.b[j].n + SB_REC - 1) / SB_REC;
-        per[j % 8] = ax.xseq ? max(per[j % 8], nu) : per[j % 8] + nu;  // xseq: the batches in turn
-      }
-      for (uint32_t x = 0; x < 8; ++x) nbu = max(nbu, 8u * per[x]);
-    }
-    // the waves after the bucket workgroups: tape tiles (and per-record bucket blocks without hist)
-    const uint32_t units = max(hist ? 0u : (nbr + 63u) / 64u, (ntr + TILE_TAPE - 1) / TILE_TAPE);
-    const uint32_t twg = min((units + SIDE_WAVES - 1) / SIDE_WAVES, max(ax.nwg, 1u) * 4u);
-    const uint32_t sgrid = max(nbu + twg, 1u);
-    const size_t lds = hist ? (size_t)(ax.S + 1) * sizeof(uint32_t) : 0;
-    hipExtLaunchKernelGGL(k_side, dim3(sgrid), dim3(SIDE_THREADS), lds, st, ev0, ev1, 0, SA, nbu);
-    return hipGetLastError();
-  }
   const uint32_t aux_wgs = min((max(nbr, ntr) + 256u * REG_WAVES - 1) / (256u * REG_WAVES), max(ax.nwg, 1u));
-  const uint32_t grid = max(max(match_wgs, aux_wgs), 1u);
-  hipExtLaunchKernelGGL(k_match_reg<false>, dim3(grid), dim3(128 * REG_WAVES), 0, st, ev0, ng ? nullptr : ev1, 0, A);
-  if (ng) {
-    A.ax = AuxDev{};
-    // one wave per possible hand-off: workgroups past the hand-off count leave before the argument copy
-    hipExtLaunchKernelGGL(k_match_reg<true>, dim3(match_wgs), dim3(128 * REG_WAVES), 0, st, nullptr, ev1, 0, A);
-  }
+  const uint32_t grid = max(match_wgs, aux_wgs);  // (match_wgs >= 1: the book has symbols)
+  hipExtLaunchKernelGGL(k_match_reg<false>, dim3(grid), dim3(128 * REG_WAVES), 0, st, ev0, nullptr, 0, A);
+  A.ax = AuxDev{};
+  // one wave per possible hand-off: workgroups past the hand-off count leave before the argument copy
+  hipExtLaunchKernelGGL(k_match_reg<true>, dim3(match_wgs), dim3(128 * REG_WAVES), 0, st, nullptr, ev1, 0, A);
   return hipGetLastError();
 }
 

@@ -16,6 +16,7 @@
 // practice (dependent chunk loads).
 #include <hip/hip_runtime.h>
 
+#include "me_launch.hpp"
 #include "me_layout.hpp"
 
 namespace me {

@@ -1,5 +1,6 @@
 // me_wave.hpp — wavefront (64-lane) helpers shared by the gfx950 kernels: lane reads, DPP
-// scans, the wave-wide lower bound over the grouped symbol keys, and the diagnostic stamps.
+// scans, launch arguments read back from LDS, the wave-wide lower bound over the grouped symbol keys,
+// and the diagnostic stamps.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -117,6 +118,37 @@ __device__ __forceinline__ unsigned long long vreg64(unsigned long long x) {
 template <class T>
 __device__ __forceinline__ gptr<T> vptr(T* p) {
   return (gptr<T>)vreg64((unsigned long long)p);
+}
+
+// A wave-uniform value read from LDS at the point of use. A relaxed atomic load is never hoisted out
+// of a loop (a plain load would be, pinning the value in SGPRs for the whole loop) and, unlike a
+// volatile one, keeps its LDS address space (ds_read, not flat); readfirstlane makes it scalar.
+template <class T>
+__device__ __forceinline__ T ldsu(const T& f) {
+  static_assert(sizeof(T) == 8 || sizeof(T) == 4, "ldsu: 4- or 8-byte values");
+  if constexpr (sizeof(T) == 8) {
+    const unsigned long long v = __hip_atomic_load((const unsigned long long*)&f, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+    // readfirstlane (first ACTIVE lane): readlane 0 may read an inactive lane in a divergent branch
+    const unsigned long long r =
+        ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    return __builtin_bit_cast(T, r);
+  } else {
+    const uint32_t v = __hip_atomic_load((const uint32_t*)&f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return __builtin_bit_cast(T, (uint32_t)__builtin_amdgcn_readfirstlane((int)v));
+  }
+}
+
+// A pointer launch argument read from LDS, as a global-address-space pointer (global_* ops).
+template <class T>
+__device__ __forceinline__ gptr<T> ldsg(T* const& f) {
+  return (gptr<T>)ldsu(reinterpret_cast<const unsigned long long&>(f));
+}
+
+// Store a wave-uniform 32-bit value into the wave's LDS (lane 0; read back with ldsu).
+__device__ __forceinline__ void ldsw(uint32_t& f, uint32_t v) {
+  if (lane_id() == 0) __hip_atomic_store(&f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 // Orders the wave's own global stores before its later loads of the same lines (another lane

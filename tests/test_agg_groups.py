@@ -194,6 +194,22 @@ def test_agg_groups_early_fill_after_flush(me, orc, monkeypatch, early):
             db.free()
 
 
+def test_agg_groups_side_jobs_in_line(me, orc, monkeypatch):
+    """ME_SIDE_STREAM=0: the engine creates no side stream, so a group's side jobs (the next group's buckets,
+    the tapes of the group before) run as a k_side launch on the engine stream ahead of the walk instead of
+    beside it. Config 2's stream on 8 symbols, 8 batches of 512 records in groups of 3 (two full groups and a
+    partial one, host slots): every batch against the oracle."""
+    monkeypatch.setenv("ME_SIDE_STREAM", "0")
+    sc = me.preset(2, num_symbols=8, batch=512)
+    st = me.Stream(sc)
+    base = st.base_prices()
+    batches = [st.next(sc.batch) for _ in range(8)]
+    ob = orc.OracleBook(sc.num_symbols)
+    with _engine(me, sc, base, batches, batches_per_launch=3) as eng:
+        assert eng.paths()["grouped_agg"]
+        assert _check(eng, ob, batches, _pipelined(eng, batches, 7), "side jobs in line") > 0
+
+
 def _peak_resting(orc, sc, batches):
     """The most orders resting at any record of the stream (the oracle fed one record at a time)."""
     ob = orc.OracleBook(sc.num_symbols)
