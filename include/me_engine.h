@@ -313,6 +313,37 @@ int me_book_dump(me_engine* e, uint32_t symbol, me_book_entry* out, size_t cap, 
 /* Resting orders over all symbols (device counter). */
 int me_resting_count(me_engine* e, uint64_t* n);
 
+/* ---- order query: what a resting order still holds and where it stands (no reference counterpart) ----
+ * One answer per seq, from ONE launch of a read-only kernel (k_order_query, one wave per seq; DESIGN.md §2,
+ * §4) over the books at the point me_book_dump brings the pipeline to (me_sync runs first). In terms of
+ * me_book_dump's order (bids best first, then asks best first, FIFO inside a level): AHEAD are the entries
+ * of the order's side and price that come before it, BETTER the entries of its side at strictly better
+ * prices. level_qty >= qty_ahead + qty always. The three quantities are int64, as level totals are.
+ * found = 0 (every field but seq zero) for seq 0, a seq never submitted or beyond the stream's last, the
+ * seq of a record that never rested (MARKET, IOC, FOK, a rejected record, a CANCEL or REDUCE record) and an
+ * order that was filled, cancelled or reduced to nothing; these are not told apart. A partially filled or
+ * partially reduced order is found with its smaller qty and its unchanged place. */
+typedef struct me_order_info { /* 64 B */
+  uint64_t seq;           /* echoed */
+  int64_t price_q4;
+  int64_t qty_ahead;      /* live quantity in front of it in its own level's FIFO */
+  int64_t level_qty;      /* its level's total, its own quantity included */
+  int64_t qty_better;     /* total resting at the strictly better price levels of its side */
+  int32_t qty;            /* what it still holds (> 0 when found) */
+  uint32_t orders_ahead;  /* live orders in front of it in its level's FIFO */
+  uint32_t levels_better; /* occupied price levels of its side strictly better than its own */
+  uint32_t symbol;        /* me_fill.symbol id space (symbol_ids when given) */
+  uint8_t side;           /* ME_SIDE_BUY / ME_SIDE_SELL */
+  uint8_t found;          /* 1: a live resting order has this seq */
+  uint8_t pad[6];         /* zero */
+} me_order_info;
+/* Synchronous: one H2D copy of the seqs, one launch, one D2H copy of the answers (device buffers grown on
+ * demand). Seqs are unique over an engine's stream, so no symbol is named; duplicates in seqs are
+ * independent queries. n == 0: ME_OK, nothing is launched. n > 2^24, or seqs / out NULL with n > 0:
+ * ME_E_INVALID. A failed engine answers what me_sync answers. A FIFO chain that does not lead back to its
+ * level's head: ME_E_STATE "corrupt FIFO chain", as the snapshot calls. */
+int me_order_query(me_engine* e, const uint64_t* seqs, size_t n, me_order_info* out);
+
 /* ---- top-of-book change feed (StreamMarketData, proto/matching_engine.proto:32,62-69) ---------------
  * A symbol's QUOTE is (has_bid, bid_price_q4, bid_qty, has_ask, ask_price_q4, ask_qty): per side the
  * price of the best occupied level and that level's total resting quantity (int64, as level totals

@@ -229,6 +229,31 @@ typedef struct me_reduce_request {
  * by `quantity`; a restart rebuilds the book from it, so the order comes back reduced and in its place. */
 int me_service_reduce_order(me_service* s, const me_reduce_request* req, me_order_response* resp);
 
+/* OrderStatus (build extension): what a client's resting orders still hold and where they stand in their
+ * queues, from one me_order_query (me_engine.h) for all n ids. The cancel RPC's conventions: ids are
+ * "OID-<n>", n >= 1, and only the owner learns anything.
+ *   ME_OS_NOT_RESTING  the id is malformed, the order is unknown, it stopped resting (filled, cancelled,
+ *                      reduced to nothing, a MARKET / IOC / FOK), or it belongs to ANOTHER client: the call
+ *                      does not reveal that such an order exists. Every field but order_id and scale is 0.
+ *   ME_OS_PENDING      the caller's order is known to the service but the engine has no resting order of that
+ *                      id: it sits in a slice not matched yet, or its closing update is on its way. quantity =
+ *                      the remainder the service knows; no position.
+ *   ME_OS_RESTING      side, quantity (what it still holds), price (Q4) and the position fields exactly as
+ *                      me_order_info defines them.
+ * out[i] answers order_ids[i] (order_id echoed, truncated to fit). The call matches what was flushed before
+ * it (me_order_query's me_sync) but flushes no open slice. A service over a me_matcher has no order query:
+ * ME_E_INVALID. n == 0: ME_OK. */
+enum { ME_OS_NOT_RESTING = 0, ME_OS_PENDING = 1, ME_OS_RESTING = 2 };
+typedef struct me_order_status { /* 88 B */
+  char order_id[32];
+  int32_t state; /* ME_OS_* */
+  int32_t side, scale /* 4 */, quantity /* remaining */;
+  int64_t price, qty_ahead, level_qty, qty_better;
+  uint32_t orders_ahead, levels_better;
+} me_order_status;
+int me_service_order_status(me_service* s, const char* client_id, const char* const* order_ids, size_t n,
+                            me_order_status* out);
+
 /* OrderUpdate (proto:71-91). Events per flushed record, in slice order: for each fill the maker's
  * update then the taker's (fill price/qty, remaining after the fill, PARTIALLY_FILLED / FILLED);
  * then a closing taker update when no fill closed it (NEW resting, CANCELED market / IOC remainder or

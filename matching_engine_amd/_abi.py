@@ -126,6 +126,13 @@ DEPTH_DTYPE = np.dtype(
 )
 DEPTH_MAX = 32
 assert DEPTH_DTYPE.itemsize == 32
+# me_order_info: one answer of me_order_query (found 0: every field but seq is 0)
+ORDER_INFO_DTYPE = np.dtype(
+    [("seq", "<u8"), ("price_q4", "<i8"), ("qty_ahead", "<i8"), ("level_qty", "<i8"), ("qty_better", "<i8"),
+     ("qty", "<i4"), ("orders_ahead", "<u4"), ("levels_better", "<u4"), ("symbol", "<u4"), ("side", "u1"),
+     ("found", "u1"), ("pad", "u1", (6,))]
+)
+assert ORDER_INFO_DTYPE.itemsize == 64
 
 
 # ---- raw export of the resident book (me_debug_layout / me_debug_export: diagnostic) -------------------
@@ -209,6 +216,7 @@ PROTOTYPES = {
                                  _P, _P, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "me_book_levels_all": (C.c_int, [_P, C.c_uint32, _P, _P]),
     "me_resting_count": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "me_order_query": (C.c_int, [_P, _P, _SZ, _P]),
     "me_timing_enable": (C.c_int, [_P, C.c_int]),
     "me_timing_read": (
         C.c_int,
@@ -382,6 +390,27 @@ class MeBookOrder(C.Structure):
 
 assert C.sizeof(MeBookOrder) == 120, "me_book_order layout"
 
+OS_NOT_RESTING, OS_PENDING, OS_RESTING = 0, 1, 2
+
+
+class MeOrderStatus(C.Structure):
+    _fields_ = [
+        ("order_id", C.c_char * 32),
+        ("state", C.c_int32),
+        ("side", C.c_int32),
+        ("scale", C.c_int32),
+        ("quantity", C.c_int32),
+        ("price", C.c_int64),
+        ("qty_ahead", C.c_int64),
+        ("level_qty", C.c_int64),
+        ("qty_better", C.c_int64),
+        ("orders_ahead", C.c_uint32),
+        ("levels_better", C.c_uint32),
+    ]
+
+
+assert C.sizeof(MeOrderStatus) == 88, "me_order_status layout"
+
 MATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(MeOrderSoa), C.c_size_t, C.POINTER(C.c_void_p),
                        C.POINTER(C.c_size_t), C.POINTER(C.c_void_p))
 BOOK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
@@ -445,6 +474,7 @@ PROTOTYPES.update({
     "me_service_create_matcher": (_P, [C.POINTER(MeMatcher), C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p]),
     "me_service_order_book": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ),
                                         C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ)]),
+    "me_service_order_status": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_char_p), _SZ, C.POINTER(MeOrderStatus)]),
     "me_service_cancel_order": (C.c_int, [_P, C.POINTER(MeCancelRequest), C.POINTER(MeOrderResponse)]),
     "me_service_reduce_order": (C.c_int, [_P, C.POINTER(MeReduceRequest), C.POINTER(MeOrderResponse)]),
     "me_service_market_data": (C.c_int, [_P, C.c_char_p, C.POINTER(MeMarketData)]),

@@ -288,6 +288,12 @@ struct me_engine {
     uint32_t* err = nullptr;
     size_t sym_cap = 0, lv_cap = 0, n_cap = 0, ord_cap = 0, nord_cap = 0, err_cap = 0;
   } snap;
+  struct QueryBufs {  // device buffers of the order query kernel, grown on demand
+    uint64_t* seqs = nullptr;
+    me_order_info* out = nullptr;
+    uint32_t* err = nullptr;
+    size_t cap = 0;  // queries seqs and out hold
+  } oq;
   // top-of-book change feed (me_quotes_*) and depth feed (me_depth_*): each its event ring and its own
   // device arrays (qd.ring / dd.ring are filled in per job, from the Feed)
   Feed<me_quote> quotes;
@@ -312,7 +318,8 @@ struct me_engine {
   // memory ahead of every match launch; a synchronous exact count replaces it when it is too stale.
   static constexpr uint32_t ADM_RING = 256;
   unsigned long long* pub_host = nullptr;  // hipHostMalloc'd, device-mapped (bk.pub): [0] {launch, resting},
-                                           // [1] {launch, hand-offs}, [2] me_sync's error-word copy
+                                           // [1] {launch, hand-offs}, [2] me_sync's error-word copy,
+                                           // [3] me_order_query's
   // grouped launches through the aggregate path (hot.agg_reg) chosen by shape, not by ME_REG_AGG: turned
   // off for good when symbols hand off to the continuation in more than 1/16 of their launches (cancels,
   // far prices — config 5's stream), which then pays both paths
@@ -465,7 +472,8 @@ static void free_all(me_engine* e) {
   e->hs.clear();
   if (e->d_spill) (void)hipFree(e->d_spill);
   {
-    void* sp[] = {e->snap.sym, e->snap.lv, e->snap.nlv, e->snap.ord, e->snap.nord, e->snap.err};
+    void* sp[] = {e->snap.sym, e->snap.lv,  e->snap.nlv, e->snap.ord, e->snap.nord,
+                  e->snap.err, e->oq.seqs, e->oq.out,   e->oq.err};
     for (void* p : sp)
       if (p) (void)hipFree(p);
   }
@@ -2027,6 +2035,44 @@ extern "C" int me_book_dump(me_engine* e, uint32_t symbol, me_book_entry* out, s
     if (cap > nb) memcpy(out + nb, side[1].data(), std::min(na, cap - nb) * sizeof(me_book_entry));
   }
   if (n) *n = nb + na;
+  return ME_OK;
+}
+
+// ---- order query (me_snapshot.hip k_order_query): one wave per seq, answers in e->oq ------------------
+extern "C" int me_order_query(me_engine* e, const uint64_t* seqs, size_t n, me_order_info* out) {
+  if (!e) return ME_E_INVALID;
+  if (n > ((size_t)1 << 24)) return e->fail(ME_E_INVALID, "order query: more than 2^24 seqs");
+  if (n && (!seqs || !out)) return e->fail(ME_E_INVALID, "order query: null seqs or out");
+  int rc = me_sync(e);
+  if (rc) return rc;
+  if (!n) return ME_OK;
+  auto& qb = e->oq;
+  if (n > qb.cap) {
+    if (qb.seqs) HIP_TRY(hipFree(qb.seqs), "hipFree");
+    qb.seqs = nullptr;
+    if (qb.out) HIP_TRY(hipFree(qb.out), "hipFree");
+    qb.out = nullptr;
+    qb.cap = 0;
+    HIP_TRY(hipMalloc((void**)&qb.seqs, n * sizeof(uint64_t)), "hipMalloc order query");
+    HIP_TRY(hipMalloc((void**)&qb.out, n * sizeof(me_order_info)), "hipMalloc order query");
+    qb.cap = n;
+  }
+  if (!qb.err) HIP_TRY(hipMalloc((void**)&qb.err, 4), "hipMalloc order query");
+  HIP_TRY(hipMemcpyAsync(qb.seqs, seqs, n * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream), "H2D order query seqs");
+  HIP_TRY(hipMemsetAsync(qb.err, 0, 4, e->stream), "hipMemset");
+  OrderQueryReq rq{};
+  rq.seqs = qb.seqs;
+  rq.out = qb.out;
+  rq.err = qb.err;
+  rq.n = (uint32_t)n;
+  hipError_t he = launch_order_query(e->stream, e->bk, rq);
+  if (he != hipSuccess) return e->hip_fail(he, "order query launch");
+  // the error word rides behind the answers: the stream orders the two copies, one synchronisation
+  uint32_t* bad = reinterpret_cast<uint32_t*>(e->pub_host + 3);
+  HIP_TRY(hipMemcpyAsync(out, qb.out, n * sizeof(me_order_info), hipMemcpyDeviceToHost, e->stream), "D2H order query answers");
+  HIP_TRY(hipMemcpyAsync(bad, qb.err, 4, hipMemcpyDeviceToHost, e->stream), "D2H order query error");
+  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+  if (*(volatile uint32_t*)bad) return e->fail(ME_E_STATE, "corrupt FIFO chain");
   return ME_OK;
 }
 

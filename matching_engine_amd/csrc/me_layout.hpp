@@ -484,6 +484,15 @@ struct SnapReq {
   uint32_t* err;             // set on a corrupt chain
 };
 
+// An order query (me_snapshot.hip k_order_query): one wave per seq.
+struct OrderQueryReq {
+  const uint64_t* seqs;      // [n] OIDs asked for (duplicates are independent queries)
+  me_order_info* out;        // [n] answers, in the order of seqs
+  uint32_t* err;             // set on a corrupt chain or an order whose level cannot be found
+  uint32_t n;
+  uint32_t pad;
+};
+
 // ---- the feeds' event ring -----------------------------------------------------------
 // Both feeds log into a bounded ring in pinned, device-mapped memory: event i sits at log[i % cap]. Four
 // control words are kept in HBM (ctl) and mirrored into pinned memory (hctl) by the one thread that ends a

@@ -1651,6 +1651,55 @@ extern "C" int me_service_order_book(me_service* s, const char* symbol, uint32_t
   return ME_OK;
 }
 
+// OrderStatus (build extension): the queue position of a client's resting orders, from one me_order_query.
+// The engine is asked about every id, another client's included; the live table then decides what the caller
+// may see, so an answer never tells whether somebody else's order exists.
+extern "C" int me_service_order_status(me_service* s, const char* client_id, const char* const* order_ids, size_t n,
+                                       me_order_status* out) {
+  if (!s) return ME_E_INVALID;
+  if (n > ((size_t)1 << 24)) return s->fail(ME_E_INVALID, "order status: more than 2^24 ids");
+  if (n && (!order_ids || !out)) return s->fail(ME_E_INVALID, "order status: null order_ids or out");
+  if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
+  if (!s->eng) return s->fail(ME_E_INVALID, "order status: the backend has no order query");
+  if (!n) return ME_OK;
+  const std::string client = client_id ? client_id : "";
+  std::vector<uint64_t> seqs(n);
+  for (size_t i = 0; i < n; ++i) seqs[i] = parse_oid(order_ids[i]);
+  std::vector<me_order_info> info(n);
+  {
+    std::lock_guard<std::mutex> le(s->eng_mu);
+    const int rc = me_order_query(s->eng, seqs.data(), n, info.data());
+    if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
+  }
+  std::lock_guard<std::mutex> lv(s->live_mu);
+  for (size_t i = 0; i < n; ++i) {
+    me_order_status& o = out[i];
+    memset(&o, 0, sizeof o);
+    put(o.order_id, sizeof o.order_id, order_ids[i] ? order_ids[i] : "");
+    o.state = ME_OS_NOT_RESTING;
+    o.scale = 4;
+    if (!seqs[i]) continue;
+    auto it = s->live.find(seqs[i]);
+    if (it == s->live.end() || it->second.client != client) continue;
+    const me_order_info& q = info[i];
+    if (!q.found) {  // in a slice not matched yet, or its closing update is on its way
+      o.state = ME_OS_PENDING;
+      o.quantity = it->second.remaining;
+      continue;
+    }
+    o.state = ME_OS_RESTING;
+    o.side = q.side;
+    o.quantity = q.qty;
+    o.price = q.price_q4;
+    o.qty_ahead = q.qty_ahead;
+    o.level_qty = q.level_qty;
+    o.qty_better = q.qty_better;
+    o.orders_ahead = q.orders_ahead;
+    o.levels_better = q.levels_better;
+  }
+  return ME_OK;
+}
+
 extern "C" int me_service_market_data(me_service* s, const char* symbol, me_market_data* out) {
   memset(out, 0, sizeof(*out));
   out->scale = 4;

@@ -16,8 +16,10 @@
 // practice (dependent chunk loads).
 #include <hip/hip_runtime.h>
 
+#include "me_far.hpp"
 #include "me_launch.hpp"
 #include "me_layout.hpp"
+#include "me_wave.hpp"
 
 namespace me {
 
@@ -641,6 +643,206 @@ hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d) {
   hipLaunchKernelGGL(k_depth_offsets, dim3(1), dim3(SNAP_T), 0, st, bk, d);
   hipLaunchKernelGGL(k_depth_emit, dim3((ewaves + DEPTH_WAVES - 1u) / DEPTH_WAVES), dim3(DEPTH_WAVES * 64), 0, st, bk, d,
                      spw);
+  return hipGetLastError();
+}
+
+// ---- order query (me_order_query, include/me_engine.h) -----------------------------------------------
+// k_order_query: one wave per queried seq, four per workgroup, read-only. The wave
+//   1. finds the order's slot as cancel_order does (me_kernels.hip): the seq ring's entry, verified (chunk id
+//      in range, the slot holds the seq, quantity > 0); on someone else's entry and a seq below the horizon,
+//      the old-order table of the current epoch, verified the same way. Between launches HBM is the book:
+//      no on-chip copy exists;
+//   2. walks hdr.prev from the order's chunk to the level's head: lanes 0..15 hold a chunk's quantities and
+//      add the live ones (in the order's own chunk only the slots below its own). One dependent HBM round
+//      trip per chunk; every id is checked against nchunks before it is dereferenced and the walk ends
+//      after nchunks steps at the latest;
+//   3. finds the level: price - base inside [0, L) is a window level, a bid at or below best_bid, an ask at
+//      or above best_ask; any other price is a far level of side price < base ? bid : ask (Invariant I),
+//      located by far_rank. The walk must have ended at that level's head;
+//   4. adds up the better levels of the side: the occupied window levels between the side's best hint and
+//      the order's level (all of the side's window levels for a far order: a window level always beats a far
+//      level) and, for a far order, the occupied far entries behind its own (the best is last).
+// Whatever does not fit (an id out of range, the step bound, a level that is not there, a head that is not
+// the walk's end) sets the request's error word and answers found = 0; nothing is read out of bounds.
+constexpr int OQ_WAVES = 4;
+
+__device__ __forceinline__ long long oq_wave_sum(long long x) { return rli64(wave_incl_scan(x), 63); }
+
+// Occupied levels of window levels [lo, hi) and their totals, as per-lane partial sums. L <= 128: every
+// total of the range, 64 per load. Deeper windows: the occ words, 64 per load, and only the totals under set
+// bits; the total decides (k_depth_scan's rule).
+__device__ __forceinline__ void oq_window(const BookDev& bk, uint32_t s, int lo, int hi, long long& qty, long long& cnt) {
+  const int lane = lane_id();
+  const Level* lv = bk.levels + (size_t)s * bk.L;
+  if (lo >= hi) return;
+  if (bk.L <= 128u) {
+    for (int l0 = lo; l0 < hi; l0 += 64) {
+      const int l = l0 + lane;
+      const long long t = l < hi ? lv[l].total : 0;
+      if (t > 0) {
+        qty += t;
+        cnt += 1;
+      }
+    }
+    return;
+  }
+  const unsigned long long* oc = bk.occ + (size_t)s * bk.Lwords;
+  const int wlo = lo >> 6, whi = (hi - 1) >> 6;  // words [wlo, whi]
+  for (int w0 = wlo; w0 <= whi; w0 += 64) {
+    const int wi = w0 + lane;
+    unsigned long long word = wi <= whi ? oc[wi] : 0ull;
+    if (wi == wlo) word &= ~0ull << (lo & 63);
+    if (wi == whi && (hi & 63)) word &= (1ull << (hi & 63)) - 1ull;
+    unsigned long long nz = __ballot(word != 0ull);
+    while (nz) {
+      const int j = __builtin_ctzll(nz);
+      nz &= nz - 1ull;
+      const unsigned long long g = rl64(word, j);
+      const long long t = (g >> lane) & 1ull ? lv[(w0 + j) * 64 + lane].total : 0;
+      if (t > 0) {
+        qty += t;
+        cnt += 1;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(OQ_WAVES * 64) void k_order_query(BookDev bk, OrderQueryReq rq) {
+  const int lane = lane_id();
+  const uint32_t qi = blockIdx.x * OQ_WAVES + (threadIdx.x >> 6);
+  if (qi >= rq.n) return;  // (whole waves leave: the kernel has no block barrier)
+  const unsigned long long tgt = rl64(rq.seqs[qi], 0);
+  const uint32_t NC = bk.nchunks;
+  me_order_info o{};
+  o.seq = tgt;
+  // ---- 1. the slot
+  uint32_t g = NIL;
+  int q = 0;
+  if (tgt != 0ull) {
+    const SeqState sqs = bk.sq[bk.sq_idx];
+    const unsigned long long horizon = rl64(sqs.horizon, 0);
+    const uint32_t epoch = rl32(sqs.epoch, 0);
+    uint32_t cand = rl32(bk.loc[tgt & bk.ring_mask], 0);
+    for (int pass = 0;; ++pass) {
+      if (cand != NIL && cand / ME_C < NC) {
+        const unsigned long long sq = rl64(cs_at(bk.chunks, cand), 0);
+        if (sq == tgt) {  // the order's slot: live or dead, it never moves
+          q = rli32(cq_at(bk.chunks, cand), 0);
+          if (q > 0) g = cand;
+          break;
+        }
+      }
+      // the ring entry is someone else's: only an order older than the horizon can still be live
+      if (pass != 0 || tgt >= horizon) break;
+      cand = old_lookup((gptr<const OldEnt>)bk.old, bk.old_mask, epoch, tgt);
+      if (cand == NIL) break;
+    }
+  }
+  bool bad = false;
+  if (g != NIL) {
+    const uint32_t ch0 = g / ME_C, slot = g % ME_C;
+    const long long price = rli64(bk.chunks[ch0].hdr.price, 0);
+    const uint32_t s = rl32(bk.chunks[ch0].owner, 0);
+    // ---- 2. the place in the level: back to the head
+    long long a_qty = 0, a_cnt = 0;  // per-lane partial sums
+    uint32_t cur = ch0, steps = 0;
+    for (;;) {
+      const uint32_t prv = rl32(bk.chunks[cur].hdr.prev, 0);
+      const int qv = lane < ME_C ? bk.chunks[cur].qty[lane] : 0;
+      if (qv > 0 && (cur != ch0 || (uint32_t)lane < slot)) {
+        a_qty += qv;
+        a_cnt += 1;
+      }
+      if (prv == NIL) break;
+      if (prv >= NC || ++steps >= NC) {
+        bad = true;
+        break;
+      }
+      cur = prv;
+    }
+    bad = bad || s >= bk.S;
+    if (!bad) {
+      // ---- 3. the level
+      const SymState st = bk.sym[s];
+      const long long base = rli64(st.base, 0);
+      const int L = (int)bk.L;
+      const int bb = min(rli32(st.best_bid, 0), L - 1), ba = max(rli32(st.best_ask, 0), 0);
+      const unsigned long long off = (unsigned long long)price - (unsigned long long)base;
+      long long b_qty = 0, b_cnt = 0;
+      long long level_qty = 0;
+      uint32_t head = NIL;
+      bool bid = false;
+      if (off < (unsigned long long)L) {
+        const int lvl = (int)off;
+        const Level x = bk.levels[(size_t)s * L + lvl];
+        level_qty = rli64(x.total, 0);
+        head = rl32(x.head, 0);
+        bid = lvl <= bb;
+        if (bid == (lvl >= ba)) bad = true;  // between the hints (or both): no level of either side
+        // ---- 4. better: strictly between the side's best hint and the order's level
+        if (!bad) {
+          if (bid)
+            oq_window(bk, s, lvl + 1, bb + 1, b_qty, b_cnt);
+          else
+            oq_window(bk, s, ba, lvl, b_qty, b_cnt);
+        }
+      } else {
+        bid = price < base;
+        const uint32_t k = bid ? 0u : 1u;
+        const FarDir fd = bk.fdir[(size_t)s * 2u + k];
+        const uint32_t nfar = min(rl32(bid ? st.nfar[0] : st.nfar[1], 0), rl32(fd.cap, 0));
+        const unsigned long long foff = rl64(fd.off, 0);
+        const unsigned long long fend = 2ull * bk.S * bk.fcap + 2ull * bk.far_half;  // entries of the arena
+        const gptr<FarLevel> far = (gptr<FarLevel>)(bk.far + foff);
+        const bool region = nfar != 0u && foff <= fend && nfar <= fend - foff;
+        const uint32_t pos = region ? far_rank(far, nfar, price, k) : nfar;
+        if (pos >= nfar) {
+          bad = true;
+        } else {
+          const FarLevel e = far_get(far, pos);
+          level_qty = e.total;
+          head = e.head;
+          bad = e.price != price;
+        }
+        if (!bad) {
+          if (bid)
+            oq_window(bk, s, 0, bb + 1, b_qty, b_cnt);
+          else
+            oq_window(bk, s, ba, L, b_qty, b_cnt);
+          for (uint32_t i0 = pos + 1u; i0 < nfar; i0 += 64u) {
+            const uint32_t i = i0 + (uint32_t)lane;
+            const long long t = i < nfar ? far[i].total : 0;
+            if (t > 0) {
+              b_qty += t;
+              b_cnt += 1;
+            }
+          }
+        }
+      }
+      bad = bad || head != cur;  // the walk ended at another chunk than the level's first
+      if (!bad) {
+        o.price_q4 = price;
+        o.qty_ahead = oq_wave_sum(a_qty);
+        o.level_qty = level_qty;
+        o.qty_better = oq_wave_sum(b_qty);
+        o.qty = q;
+        o.orders_ahead = (uint32_t)oq_wave_sum(a_cnt);
+        o.levels_better = (uint32_t)oq_wave_sum(b_cnt);
+        o.symbol = bk.gsym ? bk.gsym[s] : s;
+        o.side = bid ? ME_SIDE_BUY : ME_SIDE_SELL;
+        o.found = 1;
+      }
+    }
+  }
+  if (lane == 0) {
+    if (bad) atomicOr(rq.err, 1u);
+    rq.out[qi] = o;
+  }
+}
+
+hipError_t launch_order_query(hipStream_t st, const BookDev& bk, const OrderQueryReq& rq) {
+  if (!rq.n) return hipSuccess;
+  hipLaunchKernelGGL(k_order_query, dim3((rq.n + OQ_WAVES - 1u) / OQ_WAVES), dim3(OQ_WAVES * 64), 0, st, bk, rq);
   return hipGetLastError();
 }
 

@@ -307,6 +307,14 @@ class Engine:
         _check(self.lib, self.h, self.lib.me_book_dump(self.h, symbol, ptr(out), n.value, C.byref(n)))
         return out
 
+    def order_query(self, seqs) -> np.ndarray:
+        """me_order_query: one ORDER_INFO_DTYPE answer per seq (what the order still holds, its place in its
+        level's FIFO, what rests at better prices of its side), from one launch on the current books."""
+        q = np.ascontiguousarray(seqs, dtype=np.uint64).reshape(-1)
+        out = np.zeros(len(q), dtype=_abi.ORDER_INFO_DTYPE)
+        _check(self.lib, self.h, self.lib.me_order_query(self.h, ptr(q), len(q), ptr(out)))
+        return out
+
     def resting_count(self) -> int:
         v = C.c_uint64(0)
         _check(self.lib, self.h, self.lib.me_resting_count(self.h, C.byref(v)))

@@ -101,6 +101,25 @@ class MatchingEngineService:
         return {"order_id": resp.order_id.decode(), "success": bool(resp.success),
                 "error_message": resp.error_message.decode(), "grpc_status": resp.grpc_status}
 
+    def order_status(self, client_id, order_ids) -> list:
+        """OrderStatus (build extension, me_service_order_status): one dict per id with state (OS_NOT_RESTING /
+        OS_PENDING / OS_RESTING), side, quantity, price, scale and the queue position (qty_ahead, orders_ahead,
+        level_qty, qty_better, levels_better), from one device query for all ids. Only the owner's resting
+        orders answer RESTING. ServiceError (code ME_E_INVALID) on a matcher."""
+        ids = [o.encode() for o in order_ids]
+        n = len(ids)
+        arr = (C.c_char_p * max(n, 1))(*ids)
+        out = (_abi.MeOrderStatus * max(n, 1))()
+        rc = self.lib.me_service_order_status(self.h, client_id.encode(), arr, n, out)
+        if rc != 0:
+            e = ServiceError(f"order_status failed ({rc}): {self.last_error()}")
+            e.code = rc
+            raise e
+        return [{"order_id": o.order_id.decode(), "state": o.state, "side": o.side, "scale": o.scale,
+                 "quantity": o.quantity, "price": o.price, "qty_ahead": o.qty_ahead, "level_qty": o.level_qty,
+                 "qty_better": o.qty_better, "orders_ahead": o.orders_ahead, "levels_better": o.levels_better}
+                for o in out[:n]]
+
     def order_updates(self, client_id=None, cap=1 << 16) -> list:
         """StreamOrderUpdates (proto:34,71-91): drain the queued OrderUpdate events (one client, or all)."""
         out = []
