@@ -911,7 +911,7 @@ __device__ __forceinline__ void lad_shift(WaveCtx& c, int d) {
   wave_mem_order();
 }
 
-// Move the window so that it is centred on `target` as far as invariant I allows (me_far.hpp):
+// Move the window so that it is centred on `target` as far as invariant I allows (recentre_base, me_layout.hpp):
 // cached heads go back to HBM and the cache is cleared (it is indexed by level), levels leaving the
 // window become far levels at the best end of their side, the window arrays shift, and far levels
 // now inside it are installed. Chunks name their level by price, so none of them changes.

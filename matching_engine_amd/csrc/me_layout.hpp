@@ -392,6 +392,24 @@ __host__ __device__ __forceinline__ unsigned long long old_hash(unsigned long lo
   return q;
 }
 
+// New window base for a re-centre around `target`: target - L/2, kept inside the range where
+// invariant I holds afterwards (every bid below base + L, every ask at or above base) and where
+// base + L cannot overflow. best_bid / best_ask are the symbol's overall best prices (with_bid /
+// with_ask: whether any exists). Host code only reads it in tests/host/recentre_test.cpp.
+__host__ __device__ __forceinline__ long long recentre_base(long long target, uint32_t L, bool with_bid,
+                                                            long long best_bid, bool with_ask, long long best_ask) {
+  const long long half = (long long)(L / 2);
+  const long long lo_lim = INT64_MIN, hi_lim = INT64_MAX - (long long)L + 1;
+  long long nb = target < lo_lim + half ? lo_lim : target - half;
+  if (nb > hi_lim) nb = hi_lim;
+  if (with_bid) {
+    const long long need = best_bid < lo_lim + (long long)L ? lo_lim : best_bid - (long long)L + 1;
+    if (nb < need) nb = need;
+  }
+  if (with_ask && nb > best_ask) nb = best_ask;
+  return nb;
+}
+
 struct BatchDev {
   const uint64_t* seq;
   const int64_t* px;

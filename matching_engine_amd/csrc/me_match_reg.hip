@@ -665,7 +665,7 @@ __device__ __forceinline__ void reg_install(RegCtx& c, int j, const FarLevel& e)
   if (lane_id() == 0) c.M->tot[j] = e.total;
 }
 
-// Move the window so that it is centred on `target` as far as invariant I allows (me_far.hpp
+// Move the window so that it is centred on `target` as far as invariant I allows (me_layout.hpp
 // recentre_base): cached heads go back to HBM (the cache is indexed by window level), levels leaving
 // the window become far levels at the best end of their side, the ladder rows and totals shift, and
 // far levels now inside the window are popped into it. Chunks name their level by price, so none
