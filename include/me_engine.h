@@ -449,6 +449,62 @@ int me_depth_read(me_engine* e, me_depth_event* out, size_t cap, size_t* n, size
  * may be NULL. ME_E_INVALID while the feed is off. */
 int me_depth_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred);
 
+/* ---- trade feed: per-symbol trade summaries (what traded) --------------------------------------------
+ * A TRADE is one me_fill. TAPE ORDER is the order of the stream: batches in submit order, inside a batch
+ * its records in batch order, inside a record its fills in fill order — the order me_collect and
+ * me_fetch_outputs hand out.
+ *
+ * The feed is conflated per launch group exactly like the quote feed above: after every match launch a
+ * device job folds that launch's fills into a per-symbol PENDING summary and then logs one me_trade for
+ * every symbol whose pending summary is non-empty, ascending by local symbol id; jobs appear in launch
+ * order. An event covers every fill of its symbol since the symbol's previous event (or since enable):
+ * open is the price of the earliest of them in tape order, the five last-fill fields (taker_seq, maker_seq,
+ * last_price_q4, last_qty, symbol) are the latest me_fill whole, high / low run over all of them, volume
+ * and trades are their sums. cum_volume / cum_trades count the symbol's fills since me_trades_enable, this
+ * event included. A symbol that did not trade gets no event. Fills matched before me_trades_enable are not
+ * counted; there is no initial state, and enabling runs one job that logs nothing (stats: 1 job, 0 events).
+ *
+ * Carried over from the quote feed unchanged: `batches` has me_quote.batches' meaning; events are readable
+ * after me_collect(t) (those stamped <= t's ordinal) and after me_sync (all); a job whose events do not fit
+ * the free part of the log writes nothing and counts as deferred: its fills stay in the pending summaries
+ * and come out, merged into one event per symbol, with a later job or with the catch-up job of a read that
+ * leaves the log empty. After me_sync and reads until *left == 0, for every symbol: the sums of volume and
+ * of trades over its events equal its last event's cum_volume / cum_trades and the fold of every fill of
+ * that symbol on the tapes since enable, and its last event's last-fill fields are its last fill on the tapes.
+ *
+ * The three feeds are independent: any subset may be on. With several on the order is quote job, depth
+ * job, trade job; the other feeds' events, and every result, tape and book, are what they are without it.
+ * There is no notional / VWAP field: price x qty does not fit int64 for arbitrary int64 prices. */
+typedef struct me_trade { /* 96 B */
+  uint64_t taker_seq, maker_seq; /* the LAST fill the event covers: with last_price_q4 / last_qty / symbol, that me_fill */
+  int64_t last_price_q4;
+  int64_t open_price_q4;         /* price of the FIRST fill the event covers */
+  int64_t high_price_q4, low_price_q4;
+  int64_t volume;                /* sum of qty over the event's fills */
+  uint64_t trades;               /* fills the event covers (>= 1) */
+  int64_t cum_volume;            /* this symbol since me_trades_enable, this event included */
+  uint64_t cum_trades;
+  uint64_t batches;              /* me_quote.batches' meaning */
+  int32_t last_qty;
+  uint32_t symbol;               /* me_fill.symbol id space (symbol_ids when given) */
+} me_trade;
+/* me_quotes_enable's rules: cap_events = 0 turns the feed off (an engine that never enables it launches
+ * exactly what it launched without it); else the log's capacity in events, raised to at least num_symbols
+ * so that one job always fits an empty log; more than max(64 * num_symbols, 2^24) events (pinned host
+ * memory, 96 B each) is refused with ME_E_INVALID. Enabling waits for the work in flight and for its own
+ * first job and launches no partial group; enabling an enabled feed starts it afresh (pending summaries
+ * and cumulative counts zero, unread events dropped). A failing call leaves the feed off. */
+int me_trades_enable(me_engine* e, uint64_t cap_events);
+/* me_quotes_read's contract, for me_trade: at most `cap` events in order (out may be NULL when cap is 0);
+ * *n = events copied, *left = events logged and still unread; launches no partial group and waits for no
+ * job in flight, except that a read that leaves the log empty while a deferral is outstanding waits for
+ * the work in flight and, if that still holds, runs one catch-up job whose events follow in the same call
+ * as far as `cap` allows. *n and *left are written on every return. ME_E_INVALID while the feed is off. */
+int me_trades_read(me_engine* e, me_trade* out, size_t cap, size_t* n, size_t* left);
+/* Jobs run, events logged and jobs deferred since the feed was enabled (exact after me_sync). Any pointer
+ * may be NULL. ME_E_INVALID while the feed is off. */
+int me_trades_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred);
+
 /* Kernel timing. period >= 1: every period-th match-kernel launch records its own start and end
  * (hipExtLaunchKernelGGL events: no marker packets, though each timed launch still costs the
  * stream a few microseconds, hence the sampling); period <= 0: off. Resets the counters below. */

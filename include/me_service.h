@@ -349,6 +349,37 @@ int me_service_depth_subscribe(me_service* s, uint32_t depth);
  * me_service_market_stream's are. *n = books written; ME_E_INVALID when not subscribed. */
 int me_service_depth_stream(me_service* s, const char* symbol, me_depth_book* out, size_t cap, size_t* n);
 
+/* The trade stream: one summary per symbol that traded in a matched slice, from the engine's trade feed
+ * (me_trades_*, me_engine.h): last trade price and size, open / high / low and the traded volume and count of
+ * the fills the update covers, and the symbol's totals since the subscription. Prices are Q4 (scale 4).
+ * volume and the cumulative fields are int64 / uint64 and never saturate; there is no notional or VWAP field
+ * (price x quantity does not fit int64 for arbitrary int64 prices). */
+typedef struct me_trade_update {
+  char symbol[32];
+  int32_t scale;     /* 4 */
+  int32_t last_size; /* quantity of the last fill */
+  int64_t last_price;
+  int64_t open_price, high_price, low_price;
+  int64_t volume;    /* over the fills this update covers */
+  uint64_t trades;
+  int64_t cum_volume; /* this symbol NAME since me_service_trades_subscribe, this update included */
+  uint64_t cum_trades;
+} me_trade_update;
+/* on != 0: me_trades_enable on the service's own engine (which must have been fresh when the service was
+ * created, as for me_service_market_subscribe); fills matched before are not counted and nothing is queued. It
+ * waits for a running flush. A service backed by a me_matcher has no trade feed: ME_E_INVALID. on == 0: the
+ * stream stops, queued updates and the totals are dropped. Independent of the market and depth streams. */
+int me_service_trades_subscribe(me_service* s, int on);
+/* Drain up to cap queued updates (symbol NULL or "": every symbol; else only that symbol's, the others stay
+ * queued). After each matched slice the flush path reads the engine's events and queues them. The queue
+ * conflates: a symbol has at most one pending update; a newer event merges into it — last price and size are
+ * the newer event's, open is kept, high / low widen, volume and trades add — and keeps its place. An event is
+ * named by the symbol that owned its book at the slice the event belongs to (its `batches` stamp), and the
+ * cumulative fields are summed per symbol name from the events' own volume and trades: a book handed from an
+ * idle symbol to a new one reports each name's own totals, not the book's. *n = updates written;
+ * ME_E_INVALID when not subscribed. */
+int me_service_trades_stream(me_service* s, const char* symbol, me_trade_update* out, size_t cap, size_t* n);
+
 int me_service_last_error(const me_service* s, char* buf, size_t cap);
 
 #ifdef __cplusplus

@@ -10,7 +10,7 @@ from ._abi import (  # noqa: F401
     RJ_NONE, RJ_BAD_QTY, RJ_BAD_SIDE, RJ_OUT_OF_WINDOW, RJ_BAD_SYMBOL, RJ_UNKNOWN_ORDER, RJ_BAD_SEQ,
     RJ_CAPACITY, RJ_WOULD_CROSS, RJ_BAD_TIF, TIF_GTC, TIF_IOC, TIF_FOK, TIF_POST_ONLY,
     ME_OK, ME_E_INVALID, ME_E_HIP, ME_E_CAPACITY, ME_E_STATE, ME_E_SQLITE,
-    QUOTE_DTYPE, QUOTE_HAS_BID, QUOTE_HAS_ASK, DEPTH_DTYPE, DEPTH_MAX,
+    QUOTE_DTYPE, QUOTE_HAS_BID, QUOTE_HAS_ASK, DEPTH_DTYPE, DEPTH_MAX, TRADE_DTYPE,
     ORDER_INFO_DTYPE, OS_NOT_RESTING, OS_PENDING, OS_RESTING,
 )
 from .engine import (  # noqa: F401

@@ -126,6 +126,13 @@ DEPTH_DTYPE = np.dtype(
 )
 DEPTH_MAX = 32
 assert DEPTH_DTYPE.itemsize == 32
+# me_trade: one symbol's trade summary (the fills since its previous event; the five last-fill fields are a me_fill)
+TRADE_DTYPE = np.dtype(
+    [("taker_seq", "<u8"), ("maker_seq", "<u8"), ("last_price_q4", "<i8"), ("open_price_q4", "<i8"),
+     ("high_price_q4", "<i8"), ("low_price_q4", "<i8"), ("volume", "<i8"), ("trades", "<u8"), ("cum_volume", "<i8"),
+     ("cum_trades", "<u8"), ("batches", "<u8"), ("last_qty", "<i4"), ("symbol", "<u4")]
+)
+assert TRADE_DTYPE.itemsize == 96
 # me_order_info: one answer of me_order_query (found 0: every field but seq is 0)
 ORDER_INFO_DTYPE = np.dtype(
     [("seq", "<u8"), ("price_q4", "<i8"), ("qty_ahead", "<i8"), ("level_qty", "<i8"), ("qty_better", "<i8"),
@@ -239,6 +246,9 @@ PROTOTYPES = {
     "me_depth_enable": (C.c_int, [_P, C.c_uint32, C.c_uint64]),
     "me_depth_read": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "me_depth_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "me_trades_enable": (C.c_int, [_P, C.c_uint64]),
+    "me_trades_read": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "me_trades_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_gen_create": (_P, [C.POINTER(MeGenParams)]),
     "me_gen_destroy": (None, [_P]),
     "me_gen_base_prices": (C.c_int, [_P, _P]),
@@ -376,6 +386,25 @@ class MeDepthBook(C.Structure):
 assert C.sizeof(MeDepthLevel) == 16 and C.sizeof(MeDepthBook) == 48 + 2 * 16 * DEPTH_MAX, "me_depth_book layout"
 
 
+class MeTradeUpdate(C.Structure):
+    _fields_ = [
+        ("symbol", C.c_char * 32),
+        ("scale", C.c_int32),
+        ("last_size", C.c_int32),
+        ("last_price", C.c_int64),
+        ("open_price", C.c_int64),
+        ("high_price", C.c_int64),
+        ("low_price", C.c_int64),
+        ("volume", C.c_int64),
+        ("trades", C.c_uint64),
+        ("cum_volume", C.c_int64),
+        ("cum_trades", C.c_uint64),
+    ]
+
+
+assert C.sizeof(MeTradeUpdate) == 104, "me_trade_update layout"
+
+
 class MeBookOrder(C.Structure):
     _fields_ = [
         ("order_id", C.c_char * 32),
@@ -482,6 +511,8 @@ PROTOTYPES.update({
     "me_service_market_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeMarketUpdate), _SZ, C.POINTER(_SZ)]),
     "me_service_depth_subscribe": (C.c_int, [_P, C.c_uint32]),
     "me_service_depth_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeDepthBook), _SZ, C.POINTER(_SZ)]),
+    "me_service_trades_subscribe": (C.c_int, [_P, C.c_int]),
+    "me_service_trades_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeTradeUpdate), _SZ, C.POINTER(_SZ)]),
     "me_cluster_quotes_enable": (C.c_int, [_P, C.c_uint64]),
     "me_cluster_quotes": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "me_service_updates": (C.c_int, [_P, C.c_char_p, C.POINTER(MeOrderUpdate), _SZ, C.POINTER(_SZ)]),

@@ -27,6 +27,7 @@ static_assert(sizeof(me_fill) == 32, "me_fill must be 32 B");
 static_assert(sizeof(me_order_result) == 20, "me_order_result must be 20 B");
 static_assert(sizeof(me_quote) == 48, "me_quote must be 48 B");
 static_assert(sizeof(me_depth_event) == 32, "me_depth_event must be 32 B");
+static_assert(sizeof(me_trade) == 96, "me_trade must be 96 B");
 
 using namespace me;
 
@@ -300,6 +301,9 @@ struct me_engine {
   QuoteDev qd{};
   Feed<me_depth_event> depth;
   DepthDev dd{};
+  // trade feed (me_trades_*): the same, allocated by me_trades_enable
+  Feed<me_trade> trades;
+  TradeDev td{};
   uint64_t nmatched = 0;    // batches matched (enqueued match launches), host and device: the events' stamp
   uint32_t last_n = 0;
   uint32_t sq_idx = 0;  // seq-ring state the next k_seq_sweep reads (it writes the other one)
@@ -383,6 +387,14 @@ static void depth_free(me_engine* e) {
   e->depth.free();
 }
 
+static void trades_free(me_engine* e) {
+  void* dp[] = {e->td.pend, e->td.cum, e->td.jw, e->td.mask, e->td.woff};
+  for (void* p : dp)
+    if (p) (void)hipFree(p);
+  e->td = TradeDev{};
+  e->trades.free();
+}
+
 // Up to `cap` logged events in order to `out`; *n and *left (either may be null) are kept current before
 // anything that can fail, so an error still tells the caller what it holds.
 template <class Ev>
@@ -430,6 +442,7 @@ static int feed_start(me_engine* e, Feed<Ev>& f, int (*run_job)(me_engine*), voi
 static void free_all(me_engine* e) {
   quotes_free(e);
   depth_free(e);
+  trades_free(e);
   void* ptrs[] = {e->bk.levels,   e->bk.occ,      e->bk.sym,      e->bk.chunks,     e->bk.tend,
                   e->bk.loc,      e->bk.chunk_top, e->bk.err,       (void*)e->bk.gsym,
                   e->d_tape,      e->d_tape_count, e->d_fills_acc, e->bk.dbg,      e->bk.fcache,
@@ -1056,6 +1069,29 @@ static int depth_job(me_engine* e) {
   return ME_OK;
 }
 
+// The trade feed's job, wherever depth_job runs and directly behind it: the fold of the fills of the match
+// launch just enqueued (its nb batches bt, in launch order; bucketed: a pipelined launch, whose run starts
+// are still in the results), then every symbol's pending summary against the log (me_snapshot.hip k_trade_fold / k_trade_scan / k_trade_emit). nb = 0 (enable, catch-up): no fold.
+static int trades_job(me_engine* e, const BatchDev* bt, uint32_t nb, bool bucketed) {
+  TradeDev t = e->td;
+  t.ring = e->trades.ring;
+  t.ring.batches = e->nmatched;
+  TradeLaunch tl{};
+  tl.nb = nb;
+  tl.scratch_cap = e->scratch_cap;
+  for (uint32_t g = 0; g < nb; ++g) {
+    tl.b[g].sym = bt[g].sym;
+    tl.b[g].res = bt[g].res;
+    tl.b[g].fstart = bucketed ? nullptr : bt[g].fstart;
+    tl.b[g].scratch = bt[g].scratch;
+    tl.b[g].n = bt[g].n;
+    tl.nmax = std::max(tl.nmax, bt[g].n);
+  }
+  HIP_TRY(launch_trades(e->stream, e->bk, t, tl), "trade feed launch");
+  return ME_OK;
+}
+static int trades_job_idle(me_engine* e) { return trades_job(e, nullptr, 0, false); }
+
 // One launch of the pipelined register-ladder path: match group g_match (if any), bucket group nb
 // (if any) and clear the counters its batches will use, compact g_tape's tapes (if any) — then the
 // pipeline shifts by one group.
@@ -1152,6 +1188,10 @@ static int pipe_launch(me_engine* e, const me_engine::Group* nb) {
     }
     if (e->depth.on) {
       int rc = depth_job(e);
+      if (rc) return rc;
+    }
+    if (e->trades.on) {  // the group's fills: in scratch until its tape job, one launch on
+      int rc = trades_job(e, bt, gm.n, true);
       if (rc) return rc;
     }
   }
@@ -1300,6 +1340,10 @@ static int enqueue_batch(me_engine* e, const uint64_t* seq, const int64_t* px, c
   }
   if (e->depth.on) {
     rc = depth_job(e);
+    if (rc) return rc;
+  }
+  if (e->trades.on) {
+    rc = trades_job(e, &bt, 1u, false);
     if (rc) return rc;
   }
   if (slot >= 0) {
@@ -1847,6 +1891,59 @@ extern "C" int me_quotes_stats(me_engine* e, uint64_t* groups, uint64_t* events,
   if (!e) return ME_E_INVALID;
   if (!e->quotes.on) return e->fail(ME_E_INVALID, "the quote feed is off (me_quotes_enable)");
   e->quotes.stats(groups, events, deferred);
+  return ME_OK;
+}
+
+// ---- trade feed (me_snapshot.hip k_trade_fold / k_trade_scan / k_trade_emit) ---------------------
+extern "C" int me_trades_enable(me_engine* e, uint64_t cap_events) {
+  if (!e) return ME_E_INVALID;
+  if (e->failed) return ME_E_STATE;
+  HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
+  if (e->trades.on) {  // jobs in flight write the log: wait for them before it goes
+    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    trades_free(e);
+  }
+  if (!cap_events) return ME_OK;
+  const uint64_t S = e->bk.S;
+  const uint64_t cap = std::max<uint64_t>(cap_events, S);
+  // me_quotes_enable's bound (pinned host memory, 96 B per event)
+  if (cap > std::max<uint64_t>(64 * S, 1ull << 24))
+    return e->fail(ME_E_INVALID, "me_trades_enable: cap_events above max(64 * num_symbols, 2^24)");
+  TradeDev& t = e->td;
+  t.nw = (uint32_t)((S + 63) / 64);
+  // the fold's form (profiles/trades): bit 0 a one-symbol wave reduces first, bit 1 the
+  // workgroup's LDS table; ME_TRADE_FOLD=0 every lane issues its own atomics to HBM
+  const char* tf = getenv("ME_TRADE_FOLD");
+  t.wave_reduce = tf && *tf ? (uint32_t)atoi(tf) & 3u : 3u;
+  // the job words at their identities: {~0, 0, 0, ~0, 0, 0, -, -} per symbol
+  std::vector<unsigned long long> jw0(S * TJ_N, 0ull);
+  for (uint64_t s = 0; s < S; ++s) jw0[s * TJ_N + TJ_FIRST] = jw0[s * TJ_N + TJ_LOW] = ~0ull;
+  hipError_t he;
+  if ((he = dalloc(&t.pend, S)) != hipSuccess || (he = dalloc(&t.cum, S)) != hipSuccess ||
+      (he = dalloc(&t.jw, S * TJ_N)) != hipSuccess || (he = dalloc(&t.mask, t.nw)) != hipSuccess ||
+      (he = dalloc(&t.woff, t.nw)) != hipSuccess || (he = e->trades.alloc(e->stream, cap)) != hipSuccess ||
+      (he = hipMemsetAsync(t.pend, 0, S * sizeof(TradePend), e->stream)) != hipSuccess ||
+      (he = hipMemsetAsync(t.cum, 0, S * sizeof(TradeCum), e->stream)) != hipSuccess ||
+      (he = hipMemcpyAsync(t.jw, jw0.data(), jw0.size() * sizeof jw0[0], hipMemcpyHostToDevice, e->stream)) != hipSuccess ||
+      (he = hipStreamSynchronize(e->stream)) != hipSuccess) {  // (jw0 is pageable and goes out of scope)
+    trades_free(e);
+    return e->hip_fail(he, "me_trades_enable");
+  }
+  return feed_start(e, e->trades, trades_job_idle, trades_free);
+}
+
+extern "C" int me_trades_read(me_engine* e, me_trade* out, size_t cap, size_t* n, size_t* left) {
+  if (n) *n = 0;
+  if (left) *left = 0;
+  if (!e) return ME_E_INVALID;
+  if (!e->trades.on) return e->fail(ME_E_INVALID, "the trade feed is off (me_trades_enable)");
+  return e->trades.read(e, out, cap, n, left, trades_job_idle);
+}
+
+extern "C" int me_trades_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred) {
+  if (!e) return ME_E_INVALID;
+  if (!e->trades.on) return e->fail(ME_E_INVALID, "the trade feed is off (me_trades_enable)");
+  e->trades.stats(groups, events, deferred);
   return ME_OK;
 }
 

@@ -42,6 +42,7 @@ hipError_t launch_agg_group(hipStream_t st, const BookDev& bk, const BatchDev* b
 hipError_t launch_book_snapshot(hipStream_t st, const BookDev& bk, const SnapReq& rq);
 hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q);
 hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d);
+hipError_t launch_trades(hipStream_t st, const BookDev& bk, const TradeDev& t, const TradeLaunch& tl);
 hipError_t launch_order_query(hipStream_t st, const BookDev& bk, const OrderQueryReq& rq);
 
 // ---- me_match_reg.hip, one namespace per build (ng >= 1; launch_match_reg above picks one). Visible

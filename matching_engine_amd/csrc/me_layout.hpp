@@ -571,6 +571,70 @@ struct DepthDev {
   uint32_t pad;
 };
 
+// ---- trade feed (me_snapshot.hip k_trade_fold / k_trade_scan / k_trade_emit) ---------
+// Everything below is allocated by me_trades_enable and nothing before it. A symbol's PENDING summary holds,
+// resolved, the fills folded since its last event (trades == 0: empty); its cumulative pair runs since
+// enable. The fold of one job works on raw words, one 64-B line per symbol, updated with 64-bit integer
+// atomics only (sums, and min / max of keys and of biased prices: no result depends on the order of arrival).
+struct alignas(8) TradePend {
+  unsigned long long taker_seq, maker_seq;  // the last fill
+  long long last_px, open_px, high_px, low_px;
+  long long volume;
+  unsigned long long trades;  // 0: nothing pending
+  int32_t last_qty;
+  uint32_t pad;
+};
+static_assert(sizeof(TradePend) == 72, "TradePend is 72 B");
+struct alignas(16) TradeCum {
+  long long volume;
+  unsigned long long trades;
+};
+// The job's raw words of one symbol. Identities: TJ_FIRST ~0 (min), TJ_LAST 0 (max), TJ_HIGH 0 (max of biased
+// prices), TJ_LOW ~0 (min of biased prices), TJ_VOLUME 0, TJ_COUNT 0 (the count decides whether any is valid).
+enum : uint32_t { TJ_FIRST = 0, TJ_LAST = 1, TJ_HIGH = 2, TJ_LOW = 3, TJ_VOLUME = 4, TJ_COUNT = 5, TJ_N = 8 };
+// An int64 price as a u64 of the same order (unsigned min / max then order prices).
+__host__ __device__ constexpr unsigned long long trade_bias(long long px) {
+  return (unsigned long long)px ^ (1ull << 63);
+}
+__host__ __device__ constexpr long long trade_unbias(unsigned long long w) { return (long long)(w ^ (1ull << 63)); }
+// A fill's key: its place in the tape order of one launch — (batch position in the launch, record index,
+// fill index within the record's run). Grouped launches: 5 + 25 + 32 bits. A launch of one batch (deep
+// windows, a group of one): position 0, so the record index may use all 32 bits above the fill index.
+constexpr uint32_t TK_REC_BITS = 25, TK_FILL_BITS = 32;
+static_assert(ME_GMAX <= 32 && 5 + TK_REC_BITS + TK_FILL_BITS <= 64,
+              "a fill's key (batch position, record, fill) must fit 64 bits");  // (and BK_MAX_BATCH, below)
+__host__ __device__ constexpr unsigned long long trade_key(uint32_t pos, uint32_t rec, uint32_t fill) {
+  return ((((unsigned long long)pos << TK_REC_BITS) + rec) << TK_FILL_BITS) | fill;
+}
+// One batch of the launch the fold reads, and the launch: record i of batch b owns
+// scratch[start .. start + res[i].fill_count) in fill order, start = fstart[i], or res[i].tape_offset when
+// fstart is null (a bucketed launch keeps it there until the tape job).
+struct TradeBatch {
+  const uint32_t* sym;
+  const me_order_result* res;
+  const uint32_t* fstart;  // null: the run starts are in res[].tape_offset
+  const me_fill* scratch;
+  uint32_t n;
+  uint32_t pad;
+};
+struct TradeLaunch {
+  TradeBatch b[ME_GMAX];
+  unsigned long long scratch_cap;  // fills every scratch holds
+  uint32_t nb;                     // batches (0: a job without a fold — enable, catch-up)
+  uint32_t nmax;                   // the largest n of them
+};
+struct TradeDev {
+  FeedRing<me_trade> ring;
+  TradePend* pend;           // [S]
+  TradeCum* cum;             // [S]
+  unsigned long long* jw;    // [S][TJ_N] the job's raw words
+  unsigned long long* mask;  // [nw] one ballot word per 64 symbols: bit set <=> the pending summary is non-empty
+  uint32_t* woff;            // [nw] such symbols before each word
+  uint32_t nw;               // ceil(S / 64)
+  uint32_t wave_reduce;      // the fold's form (ME_TRADE_FOLD): bit 0 a wave whose active lanes all hold one symbol
+                             // reduces first, bit 1 updates go through the workgroup's LDS table
+};
+
 constexpr int BK_CAP = 128;          // records per bucket (two 64-record blocks)
 constexpr int BK_KIND_SHIFT = 26;    // BkRec::ok: six kind bits (side, type, op, time in force) above the batch index
 constexpr uint32_t BK_KIND_BITS = 63u;
@@ -578,5 +642,6 @@ constexpr uint32_t BK_IDX_MASK = (1u << BK_KIND_SHIFT) - 1u;
 constexpr uint32_t BK_MAX_BATCH = 1u << 25;  // sort key (index << 7 | bucket slot) fits 32 bits
 constexpr int BK_CNT_STRIDE = 32;    // bcnt[b * stride]: one 128-B line per counter (atomics on one
                                      // line serialise: packed counters made k_bucket 6x slower)
+static_assert(BK_MAX_BATCH <= (1u << TK_REC_BITS), "a grouped batch's record index fits a trade key's record bits");
 
 }  // namespace me

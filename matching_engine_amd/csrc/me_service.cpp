@@ -270,6 +270,13 @@ struct me_service {
   std::list<std::string> dp_q;
   std::unordered_map<std::string, std::list<std::string>::iterator> dp_at;
   std::vector<std::deque<std::pair<uint64_t, std::string>>> dp_owner;
+  // The trade stream (me_service_trades_subscribe / _stream), also under md_mu: one pending update per symbol
+  // name in first-trade order, the names' totals since the subscription, and the feed's own ownership history.
+  std::atomic<bool> tr_on{false};
+  std::list<me_trade_update> tr_q;
+  std::unordered_map<std::string, std::list<me_trade_update>::iterator> tr_at;
+  std::unordered_map<std::string, std::pair<int64_t, uint64_t>> tr_cum;
+  std::vector<std::deque<std::pair<uint64_t, std::string>>> tr_owner;
   uint64_t nsub = 0;  // slices the backend accepted since create (eng_mu): slice k's events are stamped k
   // --- background flusher
   std::thread flusher;
@@ -659,6 +666,11 @@ static void md_note_owners(me_service* s, const Slice& sl, uint64_t k) {
       auto& h = s->dp_owner[sid];
       if (h.empty() || h.back().second != sl.meta[i].symbol) h.emplace_back(k, sl.meta[i].symbol);
     }
+    if (s->tr_on) {  // and the trade feed's
+      if (sid >= s->tr_owner.size()) s->tr_owner.resize((size_t)sid + 1);
+      auto& h = s->tr_owner[sid];
+      if (h.empty() || h.back().second != sl.meta[i].symbol) h.emplace_back(k, sl.meta[i].symbol);
+    }
   }
 }
 
@@ -743,6 +755,56 @@ static int md_pull(me_service* s) {
       } else {
         s->md_q.push_back(u);
         s->md_at.emplace(key, std::prev(s->md_q.end()));
+      }
+    }
+    if (!left) return ME_OK;
+  }
+}
+
+// Read the engine's trade events and queue them, merged per symbol name (eng_mu held). Naming as in md_pull,
+// by the trade feed's own history; the names' totals are summed from the events' own volume and trades (a
+// reused book's device counters span two names).
+static int tr_pull(me_service* s) {
+  std::vector<me_trade> buf(1024);
+  for (;;) {
+    size_t n = 0, left = 0;
+    const int rc = me_trades_read(s->eng, buf.data(), buf.size(), &n, &left);
+    if (rc != ME_OK) return s->fail(rc, "trade stream: reading the engine's trade feed failed: " + backend_err(s));
+    std::lock_guard<std::mutex> lm(s->md_mu);
+    for (size_t i = 0; i < n; ++i) {
+      const me_trade& ev = buf[i];
+      if (ev.symbol >= s->tr_owner.size() || s->tr_owner[ev.symbol].empty()) continue;  // (a book no slice ever named)
+      auto& h = s->tr_owner[ev.symbol];
+      while (h.size() > 1 && h[1].first <= ev.batches) h.pop_front();
+      me_trade_update u;
+      memset(&u, 0, sizeof u);
+      put(u.symbol, sizeof u.symbol, h.front().second);
+      const std::string key = u.symbol;  // (the name as the update carries it)
+      auto& cum = s->tr_cum[key];
+      cum.first += ev.volume;
+      cum.second += ev.trades;
+      u.scale = 4;
+      u.last_size = ev.last_qty;
+      u.last_price = ev.last_price_q4;
+      u.open_price = ev.open_price_q4;
+      u.high_price = ev.high_price_q4;
+      u.low_price = ev.low_price_q4;
+      u.volume = ev.volume;
+      u.trades = ev.trades;
+      u.cum_volume = cum.first;
+      u.cum_trades = cum.second;
+      auto it = s->tr_at.find(key);
+      if (it != s->tr_at.end()) {  // merge into the pending update, which keeps its place
+        const me_trade_update& p = *it->second;
+        u.open_price = p.open_price;
+        u.high_price = std::max(u.high_price, p.high_price);
+        u.low_price = std::min(u.low_price, p.low_price);
+        u.volume += p.volume;
+        u.trades += p.trades;
+        *it->second = u;
+      } else {
+        s->tr_q.push_back(u);
+        s->tr_at.emplace(key, std::prev(s->tr_q.end()));
       }
     }
     if (!left) return ME_OK;
@@ -1408,6 +1470,7 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
       r = backend_collect(s, fl.front());
       if (r == ME_OK && s->md_on) (void)md_pull(s);  // (a failed read is in last_error; the slice is matched)
       if (r == ME_OK && s->dp_on) (void)dp_pull(s);
+      if (r == ME_OK && s->tr_on) (void)tr_pull(s);
     }
     if (r != ME_OK) return lost(r, "engine lost an accepted slice: ");
     Inflight& f = fl.front();
@@ -1438,7 +1501,7 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
       r = backend_submit(s, f, accepted);
       if (accepted) {
         ++s->nsub;
-        if (s->md_on || s->dp_on) md_note_owners(s, f.sl, s->nsub);
+        if (s->md_on || s->dp_on || s->tr_on) md_note_owners(s, f.sl, s->nsub);
       }
     }
     if (r != ME_OK && !accepted) {  // refused: the slices before it go first, then it is split
@@ -1852,6 +1915,63 @@ extern "C" int me_service_depth_stream(me_service* s, const char* symbol, me_dep
       fill(s->dp_q.front(), out[k++]);
       s->dp_at.erase(s->dp_q.front());
       s->dp_q.pop_front();
+    }
+  }
+  if (n) *n = k;
+  return ME_OK;
+}
+
+extern "C" int me_service_trades_subscribe(me_service* s, int on) {
+  if (!s) return ME_E_INVALID;
+  std::lock_guard<std::mutex> lf(s->flush_mu);  // no slice is in flight while it is held
+  std::lock_guard<std::mutex> le(s->eng_mu);
+  auto reset = [&](bool v) {
+    s->tr_on = v;
+    s->tr_q.clear();
+    s->tr_at.clear();
+    s->tr_cum.clear();
+    s->tr_owner.clear();
+  };
+  if (!on) {
+    if (s->tr_on && s->eng) me_trades_enable(s->eng, 0);
+    std::lock_guard<std::mutex> lm(s->md_mu);
+    reset(false);
+    return ME_OK;
+  }
+  if (!s->eng) return s->fail(ME_E_INVALID, "trade stream: the matcher has no trade feed");
+  // room for four jobs in which every symbol trades
+  const int rc = me_trades_enable(s->eng, std::max<uint64_t>(4ull * s->sym_cap, 1024));
+  if (rc != ME_OK) return s->fail(rc, "trade stream: me_trades_enable failed: " + backend_err(s));
+  std::vector<std::string> names;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    names = s->names;
+  }
+  std::lock_guard<std::mutex> lm(s->md_mu);
+  reset(true);
+  s->tr_owner.assign(names.size(), {});
+  for (size_t i = 0; i < names.size(); ++i) s->tr_owner[i].emplace_back(0, names[i]);
+  return ME_OK;  // (no initial state: nothing to read yet)
+}
+
+extern "C" int me_service_trades_stream(me_service* s, const char* symbol, me_trade_update* out, size_t cap, size_t* n) {
+  if (n) *n = 0;
+  if (!s || (cap && !out)) return ME_E_INVALID;
+  std::lock_guard<std::mutex> lm(s->md_mu);
+  if (!s->tr_on) return s->fail(ME_E_INVALID, "trade stream: not subscribed (me_service_trades_subscribe)");
+  size_t k = 0;
+  if (symbol && *symbol) {
+    auto it = s->tr_at.find(std::string(symbol).substr(0, sizeof(out->symbol) - 1));
+    if (it != s->tr_at.end() && cap) {
+      out[k++] = *it->second;
+      s->tr_q.erase(it->second);
+      s->tr_at.erase(it);
+    }
+  } else {
+    while (k < cap && !s->tr_q.empty()) {
+      out[k++] = s->tr_q.front();
+      s->tr_at.erase(s->tr_q.front().symbol);
+      s->tr_q.pop_front();
     }
   }
   if (n) *n = k;

@@ -646,6 +646,304 @@ hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d) {
   return hipGetLastError();
 }
 
+// ---- trade feed: per-symbol trade summaries (me_trades_*, include/me_engine.h) -----------------------
+// Three launches behind every match launch of an engine with the trade feed on (two at enable and catch-up
+// time: no fold). Right behind a match launch, record i of a batch owns scratch[start .. start + fill_count)
+// in fill order on every matching path, so one fold covers them all. The start is fstart[i] behind a launch
+// of the sort path (deep windows: what k_tape_compact reads) and res[i].tape_offset behind a bucketed launch
+// (L <= 128: the match job leaves it there until the group's tape job, one launch on, replaces it with the
+// tape offset — me_side.hpp aux_tape_tile reads the same word).
+//
+// k_trade_fold: one lane per record, a workgroup over TF_T * TF_ITERS consecutive records of one batch
+// (grid.y = the batch's position in the group). A record without fills costs its 8-B count and start.
+// Otherwise the lane reads its symbol and its run and forms the run's volume, high, low and count and the
+// keys of its first and last fill (trade_key, me_layout.hpp); a run longer than 64 fills is read by the
+// whole wave, 64 fills a step. The symbol's raw words take six 64-bit integer updates (add, min, max). They
+// go to the workgroup's LDS table first (TF_TABLE): slot symbol % TF_SLOTS, claimed by a CAS on its tag, so
+// that a workgroup sends every symbol it met to HBM once, six atomics on the symbol's own 64-B line, when
+// it is done; a symbol that finds its slot held by another goes to HBM at once. When every active lane of a
+// wave holds the same symbol (TF_WAVE) the wave reduces first and one lane goes on. Sums and min / max do
+// not depend on arrival order: the words are deterministic. A record whose run does not lie inside the
+// scratch, or whose symbol is >= S, is skipped.
+//
+// k_trade_scan: one lane per symbol. A symbol whose job count is non-zero fetches the two fills its keys
+// name from their batches' scratch, merges the job into its pending summary (open only when that is empty),
+// adds to its cumulative pair and puts the job words back to their identities. Every wave then ballots
+// "pending non-empty" into its mask word.
+//
+// k_trade_emit: k_quote_emit's shape — prefix the popcounts, feed_fits, and only if the job fits write the
+// events in symbol order and empty the pending summaries (never the cumulative pair); every writer fences
+// at system scope, and after the barrier thread 0 runs feed_publish.
+__device__ __forceinline__ unsigned long long trade_wave_add(unsigned long long x) {
+  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
+  return x;
+}
+__device__ __forceinline__ unsigned long long trade_wave_min(unsigned long long x) {
+  for (int d = 32; d >= 1; d >>= 1) x = min(x, (unsigned long long)__shfl_xor(x, d, 64));
+  return x;
+}
+__device__ __forceinline__ unsigned long long trade_wave_max(unsigned long long x) {
+  for (int d = 32; d >= 1; d >>= 1) x = max(x, (unsigned long long)__shfl_xor(x, d, 64));
+  return x;
+}
+
+constexpr uint32_t TF_T = 1024;     // threads of a fold workgroup
+constexpr uint32_t TF_ITERS = 16;   // records per thread: a workgroup folds TF_T * TF_ITERS records of one batch
+constexpr uint32_t TF_SLOTS = 1024; // slots of the workgroup's LDS table (48 KB of words + 4 KB of tags)
+enum : uint32_t { TF_WAVE = 1u, TF_TABLE = 2u };  // TradeDev::wave_reduce bits (ME_TRADE_FOLD)
+
+__device__ __forceinline__ void trade_words_global(unsigned long long* w, unsigned long long kf, unsigned long long kl,
+                                                   unsigned long long hi, unsigned long long lo, unsigned long long vol,
+                                                   unsigned long long cnt) {
+  atomicMin(&w[TJ_FIRST], kf);
+  atomicMax(&w[TJ_LAST], kl);
+  atomicMax(&w[TJ_HIGH], hi);
+  atomicMin(&w[TJ_LOW], lo);
+  atomicAdd(&w[TJ_VOLUME], vol);
+  atomicAdd(&w[TJ_COUNT], cnt);
+}
+
+__global__ __launch_bounds__(TF_T) void k_trade_fold(TradeDev t, TradeLaunch tl, uint32_t S) {
+  __shared__ unsigned long long tab[TF_SLOTS][6];  // TJ_FIRST .. TJ_COUNT of the symbol in tag[slot]
+  __shared__ uint32_t tag[TF_SLOTS];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t pos = blockIdx.y;
+  const TradeBatch& b = tl.b[pos];
+  const bool table = (t.wave_reduce & TF_TABLE) != 0u;
+  if (table) {
+    for (uint32_t k = threadIdx.x; k < TF_SLOTS; k += TF_T) {
+      tag[k] = NIL;
+      tab[k][TJ_FIRST] = ~0ull;
+      tab[k][TJ_LAST] = 0ull;
+      tab[k][TJ_HIGH] = 0ull;
+      tab[k][TJ_LOW] = ~0ull;
+      tab[k][TJ_VOLUME] = 0ull;
+      tab[k][TJ_COUNT] = 0ull;
+    }
+    __syncthreads();
+  }
+  const uint32_t r0 = blockIdx.x * (TF_T * TF_ITERS);
+  for (uint32_t it = 0; it < TF_ITERS; ++it) {
+    const uint32_t w0 = r0 + it * TF_T;
+    if (w0 >= b.n) break;  // (the same for the whole workgroup)
+    const uint32_t i = w0 + threadIdx.x;
+    uint32_t fc = 0, s = 0, f0 = 0;
+    if (i < b.n) {
+      fc = b.res[i].fill_count;
+      f0 = b.res[i].tape_offset;  // (the same 8 B: a bucketed launch leaves the run's start here)
+    }
+    bool active = fc != 0u;
+    if (active) {
+      s = b.sym[i];
+      if (b.fstart) f0 = b.fstart[i];
+      active = s < S && (unsigned long long)f0 <= tl.scratch_cap && (unsigned long long)fc <= tl.scratch_cap - f0;
+    }
+    const unsigned long long am = __ballot(active);
+    if (!am) continue;  // (the whole wave: there is no barrier inside the loop)
+    unsigned long long vol = 0, hi = 0, lo = ~0ull;
+    if (active && fc <= 64u) {
+      for (uint32_t k = 0; k < fc; ++k) {
+        const me_fill& f = b.scratch[(size_t)f0 + k];
+        const unsigned long long p = trade_bias(f.price_q4);
+        vol += (unsigned long long)(long long)f.qty;
+        hi = max(hi, p);
+        lo = min(lo, p);
+      }
+    }
+    // runs longer than 64 fills, one after the other: the whole wave reads them, 64 fills a step
+    for (unsigned long long m = __ballot(active && fc > 64u); m; m &= m - 1ull) {
+      const int j = __builtin_ctzll(m);
+      const uint32_t jf0 = (uint32_t)__shfl((int)f0, j, 64), jfc = (uint32_t)__shfl((int)fc, j, 64);
+      unsigned long long v = 0, h = 0, l = ~0ull;
+      for (uint32_t k = lane; k < jfc; k += 64u) {
+        const me_fill& f = b.scratch[(size_t)jf0 + k];
+        const unsigned long long p = trade_bias(f.price_q4);
+        v += (unsigned long long)(long long)f.qty;
+        h = max(h, p);
+        l = min(l, p);
+      }
+      v = trade_wave_add(v);
+      h = trade_wave_max(h);
+      l = trade_wave_min(l);
+      if ((int)lane == j) {
+        vol = v;
+        hi = h;
+        lo = l;
+      }
+    }
+    unsigned long long kf = ~0ull, kl = 0ull, cnt = 0ull;
+    if (active) {
+      kf = trade_key(pos, i, 0u);
+      kl = trade_key(pos, i, fc - 1u);
+      cnt = fc;
+    }
+    // one symbol in the whole wave: reduce, and the first active lane goes on alone
+    const int lead = __builtin_ctzll(am);
+    bool issue = active;
+    if ((t.wave_reduce & TF_WAVE) && (am & (am - 1ull))) {
+      const uint32_t s0 = (uint32_t)__shfl((int)s, lead, 64);
+      if (!__ballot(active && s != s0)) {
+        vol = trade_wave_add(vol);  // (inactive lanes hold the identities)
+        cnt = trade_wave_add(cnt);
+        hi = trade_wave_max(hi);
+        lo = trade_wave_min(lo);
+        kf = trade_wave_min(kf);
+        kl = trade_wave_max(kl);
+        issue = (int)lane == lead;
+      }
+    }
+    if (issue) {
+      bool mine = false;
+      const uint32_t slot = s & (TF_SLOTS - 1u);
+      if (table) {  // the slot is this symbol's if it is free or already holds it; else straight to HBM
+        const uint32_t was = atomicCAS(&tag[slot], NIL, s);
+        mine = was == NIL || was == s;
+      }
+      if (mine) {
+        atomicMin(&tab[slot][TJ_FIRST], kf);
+        atomicMax(&tab[slot][TJ_LAST], kl);
+        atomicMax(&tab[slot][TJ_HIGH], hi);
+        atomicMin(&tab[slot][TJ_LOW], lo);
+        atomicAdd(&tab[slot][TJ_VOLUME], vol);
+        atomicAdd(&tab[slot][TJ_COUNT], cnt);
+      } else {
+        trade_words_global(t.jw + (size_t)s * TJ_N, kf, kl, hi, lo, vol, cnt);
+      }
+    }
+  }
+  if (!table) return;
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < TF_SLOTS; k += TF_T) {
+    const uint32_t s = tag[k];
+    if (s == NIL || s >= S || !tab[k][TJ_COUNT]) continue;
+    trade_words_global(t.jw + (size_t)s * TJ_N, tab[k][TJ_FIRST], tab[k][TJ_LAST], tab[k][TJ_HIGH], tab[k][TJ_LOW],
+                       tab[k][TJ_VOLUME], tab[k][TJ_COUNT]);
+  }
+}
+
+// The fill a key names, or false when the key does not name one of this launch (never the case for a key
+// the fold wrote: it took them from records it had checked).
+__device__ __forceinline__ bool trade_fill_at(const TradeLaunch& tl, unsigned long long key, me_fill& out) {
+  const uint32_t fill = (uint32_t)key;
+  const unsigned long long up = key >> TK_FILL_BITS;
+  const uint32_t pos = tl.nb == 1u ? 0u : (uint32_t)(up >> TK_REC_BITS);
+  const uint32_t rec = tl.nb == 1u ? (uint32_t)up : (uint32_t)(up & ((1u << TK_REC_BITS) - 1u));
+  if (pos >= tl.nb) return false;
+  const TradeBatch& b = tl.b[pos];
+  if (rec >= b.n) return false;
+  const unsigned long long at = (unsigned long long)(b.fstart ? b.fstart[rec] : b.res[rec].tape_offset) + fill;
+  if (at >= tl.scratch_cap) return false;
+  out = b.scratch[at];
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_trade_scan(TradeDev t, TradeLaunch tl, uint32_t S) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  bool pending = false;
+  if (s < S) {
+    unsigned long long* w = t.jw + (size_t)s * TJ_N;
+    const unsigned long long cnt = w[TJ_COUNT];
+    unsigned long long have = t.pend[s].trades;
+    if (cnt) {
+      me_fill first, last;
+      if (trade_fill_at(tl, w[TJ_FIRST], first) && trade_fill_at(tl, w[TJ_LAST], last)) {
+        TradePend p = t.pend[s];
+        const long long hi = trade_unbias(w[TJ_HIGH]), lo = trade_unbias(w[TJ_LOW]);
+        if (!p.trades) {
+          p.open_px = first.price_q4;
+          p.high_px = hi;
+          p.low_px = lo;
+          p.volume = 0;
+        } else {
+          p.high_px = max(p.high_px, hi);
+          p.low_px = min(p.low_px, lo);
+        }
+        p.taker_seq = last.taker_seq;
+        p.maker_seq = last.maker_seq;
+        p.last_px = last.price_q4;
+        p.last_qty = last.qty;
+        p.pad = 0;
+        p.volume += (long long)w[TJ_VOLUME];
+        p.trades += cnt;
+        t.pend[s] = p;
+        TradeCum c = t.cum[s];
+        c.volume += (long long)w[TJ_VOLUME];
+        c.trades += cnt;
+        t.cum[s] = c;
+        have = p.trades;
+      }
+      w[TJ_FIRST] = ~0ull;
+      w[TJ_LAST] = 0ull;
+      w[TJ_HIGH] = 0ull;
+      w[TJ_LOW] = ~0ull;
+      w[TJ_VOLUME] = 0ull;
+      w[TJ_COUNT] = 0ull;
+    }
+    pending = have != 0ull;
+  }
+  const unsigned long long m = __ballot(pending);
+  const uint32_t wd = s >> 6;
+  if ((threadIdx.x & 63u) == 0u && wd < t.nw) t.mask[wd] = m;
+}
+
+__global__ __launch_bounds__(SNAP_T) void k_trade_emit(BookDev bk, TradeDev t) {
+  __shared__ uint32_t wsum[SNAP_T / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  uint32_t run = 0;
+  for (uint32_t base = 0; base < t.nw; base += SNAP_T) {
+    const uint32_t w = base + tid;
+    const uint32_t pc = w < t.nw ? (uint32_t)__popcll(t.mask[w]) : 0u;
+    uint32_t tot = 0;
+    const uint32_t ex = snap_block_excl_scan(pc, wsum, tot);
+    if (w < t.nw) t.woff[w] = run + ex;
+    run += tot;
+  }
+  const FeedRing<me_trade>& r = t.ring;
+  const unsigned long long tail = r.ctl[FR_TAIL];
+  const bool fit = feed_fits(r, tail, run);
+  __syncthreads();  // the offsets are written, the tail is read
+  if (fit && run) {
+    for (uint32_t w = wv; w < t.nw; w += SNAP_T / 64) {
+      const unsigned long long m = t.mask[w];
+      if (!((m >> lane) & 1ull)) continue;
+      const uint32_t s = w * 64u + lane;
+      const uint32_t pos = t.woff[w] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      const TradePend p = t.pend[s];
+      const TradeCum c = t.cum[s];
+      me_trade ev;
+      ev.taker_seq = p.taker_seq;
+      ev.maker_seq = p.maker_seq;
+      ev.last_price_q4 = p.last_px;
+      ev.open_price_q4 = p.open_px;
+      ev.high_price_q4 = p.high_px;
+      ev.low_price_q4 = p.low_px;
+      ev.volume = p.volume;
+      ev.trades = p.trades;
+      ev.cum_volume = c.volume;
+      ev.cum_trades = c.trades;
+      ev.batches = r.batches;
+      ev.last_qty = p.last_qty;
+      ev.symbol = bk.gsym ? bk.gsym[s] : s;
+      r.log[(tail + pos) % r.cap] = ev;
+      t.pend[s].trades = 0ull;  // empty (the next job's scan reads it: a later launch)
+    }
+    __threadfence_system();
+  }
+  __syncthreads();  // every writer has fenced
+  if (tid == 0) feed_publish(r, tail, run, fit);
+}
+
+// The trade feed's job on st: the fold of the launch's fills (tl.nb batches, behind their match launch; none
+// at enable / catch-up time), then scan + emit.
+hipError_t launch_trades(hipStream_t st, const BookDev& bk, const TradeDev& t, const TradeLaunch& tl) {
+  if (tl.nb && tl.nmax)
+    hipLaunchKernelGGL(k_trade_fold, dim3((tl.nmax + TF_T * TF_ITERS - 1u) / (TF_T * TF_ITERS), tl.nb), dim3(TF_T), 0,
+                       st, t, tl, bk.S);
+  hipLaunchKernelGGL(k_trade_scan, dim3((bk.S + 255u) / 256u), dim3(256), 0, st, t, tl, bk.S);
+  hipLaunchKernelGGL(k_trade_emit, dim3(1), dim3(SNAP_T), 0, st, bk, t);
+  return hipGetLastError();
+}
+
 // ---- order query (me_order_query, include/me_engine.h) -----------------------------------------------
 // k_order_query: one wave per queried seq, four per workgroup, read-only. The wave
 //   1. finds the order's slot as cancel_order does (me_kernels.hip): the seq ring's entry, verified (chunk id

@@ -388,7 +388,7 @@ class Engine:
         _check(self.lib, self.h, self.lib.me_admission_read(self.h, C.byref(r), C.byref(b), C.byref(x)))
         return {"resting": r.value, "bound": b.value, "exact_counts": x.value}
 
-    # -- the feeds' shared read side (me_quotes_* / me_depth_*: one event-ring protocol, two event types)
+    # -- the feeds' shared read side (me_quotes_* / me_depth_* / me_trades_*: one event-ring protocol, three event types)
     def _feed_read(self, fn, dtype, cap: int):
         out = np.zeros(cap, dtype=dtype)
         n, left = C.c_size_t(0), C.c_size_t(0)
@@ -446,6 +446,24 @@ class Engine:
 
     def depth_stats(self) -> dict:
         return self._feed_stats(self.lib.me_depth_stats)
+
+    # -- trade feed (me_trades_*)
+    def trades_enable(self, cap_events: int):
+        """Turn the trade feed on with a log of cap_events events (raised to num_symbols), or off with 0. Fills
+        matched before this point of the stream are not counted."""
+        _check(self.lib, self.h, self.lib.me_trades_enable(self.h, int(cap_events)))
+
+    def trades_read(self, cap: int = 0):
+        """(events TRADE_DTYPE, left): up to `cap` logged events in order (0 = a buffer of num_symbols) and
+        how many stay unread. Launches no partial group; see me_trades_read for what is there when."""
+        return self._feed_read(self.lib.me_trades_read, _abi.TRADE_DTYPE, int(cap) or self.num_symbols)
+
+    def trades_drain(self) -> np.ndarray:
+        """Every logged event: reads until none is left (a deferred job's catch-up included)."""
+        return self._feed_drain(self.trades_read)
+
+    def trades_stats(self) -> dict:
+        return self._feed_stats(self.lib.me_trades_stats)
 
     # -- timing
     def timing_enable(self, period: int = 1):

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (FILL_DTYPE, LEVEL_DTYPE, RESULT_DTYPE, MeBookOrder, MeCancelRequest, MeOrderRequest, MeReduceRequest,
-                   MeOrderResponse, MeMarketData, MeMarketUpdate, MeDepthBook, MeOrderUpdate, ptr)
+                   MeOrderResponse, MeMarketData, MeMarketUpdate, MeDepthBook, MeTradeUpdate, MeOrderUpdate, ptr)
 
 
 class ServiceError(RuntimeError):
@@ -211,6 +211,33 @@ class MatchingEngineService:
                 out.append({"symbol": b.symbol.decode(), "scale": b.scale,
                             "bids": [(b.bids[i].price, b.bids[i].size) for i in range(b.n_bids)],
                             "asks": [(b.asks[i].price, b.asks[i].size) for i in range(b.n_asks)]})
+            if n.value < cap:
+                return out
+
+    def trades_subscribe(self, on: bool = True):
+        """The trade stream (me_service_trades_subscribe): enable the engine's trade feed; fills matched before
+        are not counted. ServiceError (code ME_E_INVALID) on a matcher."""
+        rc = self.lib.me_service_trades_subscribe(self.h, 1 if on else 0)
+        if rc != 0:
+            e = ServiceError(f"trades_subscribe failed ({rc}): {self.last_error()}")
+            e.code = rc
+            raise e
+
+    def trades_stream(self, symbol=None, cap=4096) -> list:
+        """Drain the queued trade summaries (one symbol's, or all in first-trade order): dicts with symbol,
+        scale, last_price, last_size, open / high / low_price, volume, trades, cum_volume, cum_trades."""
+        out = []
+        buf = (MeTradeUpdate * cap)()
+        names = [f for f, _ in MeTradeUpdate._fields_ if f != "symbol"]
+        while True:
+            n = C.c_size_t(0)
+            rc = self.lib.me_service_trades_stream(self.h, symbol.encode() if symbol else None, buf, cap, C.byref(n))
+            if rc != 0:
+                e = ServiceError(f"trades_stream failed ({rc}): {self.last_error()}")
+                e.code = rc
+                raise e
+            for u in buf[: n.value]:
+                out.append({"symbol": u.symbol.decode(), **{f: getattr(u, f) for f in names}})
             if n.value < cap:
                 return out
 
