@@ -344,6 +344,36 @@ typedef struct me_order_info { /* 64 B */
  * level's head: ME_E_STATE "corrupt FIFO chain", as the snapshot calls. */
 int me_order_query(me_engine* e, const uint64_t* seqs, size_t n, me_order_info* out);
 
+/* ---- mass cancel: empty the named sides of the named symbols' books (no reference counterpart) -------
+ * A halt, a delisting, the end-of-session purge, a kill switch: every resting order of sides[i]
+ * (ME_SIDE_BUY = 1, ME_SIDE_SELL = 2, 3 = both) of symbols[i] is removed, window levels and far levels
+ * alike, by a stand-alone kernel beside the matching kernels (k_purge): a read-only count
+ * launch, one D2H copy of the counts, and — only if anything rests there and fits — one remove launch.
+ * When: on the books at the point me_book_dump brings the pipeline to (me_sync runs first, so a partial
+ * group is launched and matched); tickets of me_submit_host submitted before stay collectable afterwards
+ * with the outputs they would have had. Stream position: the call consumes no seq, does not touch the seq
+ * state and is no batch (the feeds' `batches` stamps do not advance).
+ * out receives the removed orders request by request; inside a request in me_book_dump's order restricted to
+ * the sides asked for (bids best first, then asks best first, FIFO inside a level), qty = what the order
+ * still held. counts (or NULL) is [n][2]: counts[2 i] bids, counts[2 i + 1] asks removed for request i.
+ * *n_out receives the total. All or nothing: when cap (0 for out == NULL) cannot take every order, nothing
+ * is changed, *n_out still holds the exact number needed and the call returns ME_E_CAPACITY — not sticky,
+ * the engine stays usable, as after a refused batch. n == 0: ME_OK, nothing is launched.
+ * ME_E_INVALID with nothing changed: symbols or sides NULL with n > 0, a symbol >= num_symbols, a sides
+ * value outside 1..3, the same symbol named twice, n > num_symbols. A failed engine answers what me_sync
+ * answers; a chain that does not lead to its level's tail: ME_E_STATE "corrupt FIFO chain", nothing removed.
+ * Afterwards: a CANCEL or REDUCE naming a removed seq is REJECTED / ME_RJ_UNKNOWN_ORDER, me_order_query
+ * answers found = 0 for it, me_book_dump of a fully purged symbol is empty, a one-sided purge leaves the
+ * other side's dump as it was, the window base does not move, and every later record behaves as if the same
+ * orders had been removed by individual CANCEL records. The removed orders leave the resting count of
+ * admission control at once (max_resting): a batch refused before the call can be admitted after it.
+ * Feeds: with the quote and / or depth feed on, their jobs run once behind the remove launch (quote, then
+ * depth), exactly as behind a match launch; a purged side comes out as a quote with its flag clear and as
+ * DELETEs of its published view. The trade feed logs nothing: there are no fills.
+ * Like the order query, the call exists on an engine only: not on a cluster, not behind a me_matcher. */
+int me_mass_cancel(me_engine* e, const uint32_t* symbols, const uint8_t* sides, size_t n, me_book_entry* out,
+                   size_t cap, size_t* n_out, uint64_t* counts /* [n][2] or NULL */);
+
 /* ---- top-of-book change feed (StreamMarketData, proto/matching_engine.proto:32,62-69) ---------------
  * A symbol's QUOTE is (has_bid, bid_price_q4, bid_qty, has_ask, ask_price_q4, ask_qty): per side the
  * price of the best occupied level and that level's total resting quantity (int64, as level totals

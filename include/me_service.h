@@ -254,6 +254,19 @@ typedef struct me_order_status { /* 88 B */
 int me_service_order_status(me_service* s, const char* client_id, const char* const* order_ids, size_t n,
                             me_order_status* out);
 
+/* Mass cancel (build extension): an operator's action — a halt, a delisting, the end-of-session purge — so
+ * there is no owner check. Every resting order of `sides` (ME_SIDE_BUY = 1, ME_SIDE_SELL = 2, 3 = both) of the
+ * n named symbols is removed by ONE me_mass_cancel; symbols == NULL means every symbol that has a book. The open
+ * slice is closed and everything pending flushed first, so the purge takes what was submitted before the call.
+ * Every removed order's owner gets one OrderUpdate, CANCELED with remaining_quantity = the quantity removed —
+ * a cancel's update exactly; the rows' status is persisted in one transaction through the path matched slices
+ * take (a failed transaction: ME_E_SQLITE, kept and retried at the next flush), so a restart does not bring
+ * the orders back; me_service_order_status then answers ME_OS_NOT_RESTING for them, and a book left empty
+ * counts as idle: a new symbol may take it (me_service_stats: reclaimed_books). *n_cancelled (or NULL)
+ * receives the number of orders removed. ME_E_INVALID with nothing changed: a name that has no book, a name
+ * given twice, a NULL name, sides outside 1..3, and a service over a me_matcher (it has no mass cancel). */
+int me_service_mass_cancel(me_service* s, const char* const* symbols, size_t n, int32_t sides, uint64_t* n_cancelled);
+
 /* OrderUpdate (proto:71-91). Events per flushed record, in slice order: for each fill the maker's
  * update then the taker's (fill price/qty, remaining after the fill, PARTIALLY_FILLED / FILLED);
  * then a closing taker update when no fill closed it (NEW resting, CANCELED market / IOC remainder or

@@ -224,6 +224,7 @@ PROTOTYPES = {
     "me_book_levels_all": (C.c_int, [_P, C.c_uint32, _P, _P]),
     "me_resting_count": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "me_order_query": (C.c_int, [_P, _P, _SZ, _P]),
+    "me_mass_cancel": (C.c_int, [_P, _P, _P, _SZ, _P, _SZ, C.POINTER(_SZ), _P]),
     "me_timing_enable": (C.c_int, [_P, C.c_int]),
     "me_timing_read": (
         C.c_int,
@@ -504,6 +505,7 @@ PROTOTYPES.update({
     "me_service_order_book": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ),
                                         C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ)]),
     "me_service_order_status": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_char_p), _SZ, C.POINTER(MeOrderStatus)]),
+    "me_service_mass_cancel": (C.c_int, [_P, C.POINTER(C.c_char_p), _SZ, C.c_int32, C.POINTER(C.c_uint64)]),
     "me_service_cancel_order": (C.c_int, [_P, C.POINTER(MeCancelRequest), C.POINTER(MeOrderResponse)]),
     "me_service_reduce_order": (C.c_int, [_P, C.POINTER(MeReduceRequest), C.POINTER(MeOrderResponse)]),
     "me_service_market_data": (C.c_int, [_P, C.c_char_p, C.POINTER(MeMarketData)]),

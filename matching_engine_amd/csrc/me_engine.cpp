@@ -295,6 +295,16 @@ struct me_engine {
     uint32_t* err = nullptr;
     size_t cap = 0;  // queries seqs and out hold
   } oq;
+  struct PurgeBufs {  // device buffers of the mass cancel kernel, grown on demand
+    uint32_t* sym = nullptr;
+    uint8_t* sides = nullptr;
+    unsigned long long* cnt = nullptr;
+    unsigned long long* off = nullptr;
+    me_book_entry* out = nullptr;
+    uint32_t* err = nullptr;
+    size_t cap = 0;      // requests sym, sides, cnt and off hold
+    size_t out_cap = 0;  // entries out holds
+  } pg;
   // top-of-book change feed (me_quotes_*) and depth feed (me_depth_*): each its event ring and its own
   // device arrays (qd.ring / dd.ring are filled in per job, from the Feed)
   Feed<me_quote> quotes;
@@ -486,7 +496,8 @@ static void free_all(me_engine* e) {
   if (e->d_spill) (void)hipFree(e->d_spill);
   {
     void* sp[] = {e->snap.sym, e->snap.lv,  e->snap.nlv, e->snap.ord, e->snap.nord,
-                  e->snap.err, e->oq.seqs, e->oq.out,   e->oq.err};
+                  e->snap.err, e->oq.seqs, e->oq.out,   e->oq.err,   e->pg.sym,
+                  e->pg.sides, e->pg.cnt,  e->pg.off,   e->pg.out,   e->pg.err};
     for (void* p : sp)
       if (p) (void)hipFree(p);
   }
@@ -2170,6 +2181,103 @@ extern "C" int me_order_query(me_engine* e, const uint64_t* seqs, size_t n, me_o
   HIP_TRY(hipMemcpyAsync(bad, qb.err, 4, hipMemcpyDeviceToHost, e->stream), "D2H order query error");
   HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
   if (*(volatile uint32_t*)bad) return e->fail(ME_E_STATE, "corrupt FIFO chain");
+  return ME_OK;
+}
+
+// ---- mass cancel (me_snapshot.hip k_purge): count pass, host scan of the counts, remove pass -----------
+extern "C" int me_mass_cancel(me_engine* e, const uint32_t* symbols, const uint8_t* sides, size_t n, me_book_entry* out,
+                              size_t cap, size_t* n_out, uint64_t* counts) {
+  if (n_out) *n_out = 0;
+  if (!e) return ME_E_INVALID;
+  if (n && (!symbols || !sides)) return e->fail(ME_E_INVALID, "mass cancel: null symbols or sides");
+  if (n > e->bk.S) return e->fail(ME_E_INVALID, "mass cancel: more requests than symbols");
+  {
+    std::vector<bool> seen(e->bk.S, false);
+    for (size_t i = 0; i < n; ++i) {
+      if (symbols[i] >= e->bk.S) return e->fail(ME_E_INVALID, "mass cancel: symbol out of range");
+      if (sides[i] < 1 || sides[i] > 3) return e->fail(ME_E_INVALID, "mass cancel: sides must be 1 (buy), 2 (sell) or 3 (both)");
+      if (seen[symbols[i]]) return e->fail(ME_E_INVALID, "mass cancel: a symbol is named twice");
+      seen[symbols[i]] = true;
+    }
+  }
+  int rc = me_sync(e);
+  if (rc) return rc;
+  if (!n) return ME_OK;
+  auto& pb = e->pg;
+  if (n > pb.cap) {
+    void** ps[] = {(void**)&pb.sym, (void**)&pb.sides, (void**)&pb.cnt, (void**)&pb.off};
+    for (void** p : ps) {
+      if (*p) HIP_TRY(hipFree(*p), "hipFree");
+      *p = nullptr;
+    }
+    pb.cap = 0;
+    HIP_TRY(hipMalloc((void**)&pb.sym, n * sizeof(uint32_t)), "hipMalloc mass cancel");
+    HIP_TRY(hipMalloc((void**)&pb.sides, n), "hipMalloc mass cancel");
+    HIP_TRY(hipMalloc((void**)&pb.cnt, 2 * n * sizeof(unsigned long long)), "hipMalloc mass cancel");
+    HIP_TRY(hipMalloc((void**)&pb.off, 2 * n * sizeof(unsigned long long)), "hipMalloc mass cancel");
+    pb.cap = n;
+  }
+  if (!pb.err) HIP_TRY(hipMalloc((void**)&pb.err, 4), "hipMalloc mass cancel");
+  HIP_TRY(hipMemcpyAsync(pb.sym, symbols, n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream), "H2D mass cancel symbols");
+  HIP_TRY(hipMemcpyAsync(pb.sides, sides, n, hipMemcpyHostToDevice, e->stream), "H2D mass cancel sides");
+  HIP_TRY(hipMemsetAsync(pb.err, 0, 4, e->stream), "hipMemset");
+  PurgeReq rq{};
+  rq.sym = pb.sym;
+  rq.sides = pb.sides;
+  rq.cnt = pb.cnt;
+  rq.off = pb.off;
+  rq.err = pb.err;
+  rq.n = (uint32_t)n;
+  hipError_t he = launch_purge(e->stream, e->bk, rq, false);
+  if (he != hipSuccess) return e->hip_fail(he, "mass cancel count launch");
+  std::vector<unsigned long long> cnt(2 * n), off(2 * n);
+  uint32_t bad = 0;
+  HIP_TRY(hipMemcpyAsync(cnt.data(), pb.cnt, cnt.size() * 8, hipMemcpyDeviceToHost, e->stream), "D2H mass cancel counts");
+  HIP_TRY(hipMemcpyAsync(&bad, pb.err, 4, hipMemcpyDeviceToHost, e->stream), "D2H mass cancel error");
+  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+  if (bad) return e->fail(ME_E_STATE, "corrupt FIFO chain");
+  unsigned long long total = 0;
+  for (size_t r = 0; r < 2 * n; ++r) {
+    off[r] = total;
+    total += cnt[r];
+  }
+  if (n_out) *n_out = (size_t)total;
+  if (total > cap || (total && !out)) {  // all or nothing; not sticky (e->fail would make it so)
+    e->err = "mass cancel refused: " + std::to_string(total) + " resting orders to remove, room for " +
+             std::to_string(out ? cap : 0) + "; the books are unchanged";
+    return ME_E_CAPACITY;
+  }
+  if (counts)
+    for (size_t r = 0; r < 2 * n; ++r) counts[r] = cnt[r];
+  if (!total) return ME_OK;  // nothing rests on the named sides: nothing to launch, no quote or level changed
+  if (total > pb.out_cap) {
+    if (pb.out) HIP_TRY(hipFree(pb.out), "hipFree");
+    pb.out = nullptr;
+    pb.out_cap = 0;
+    HIP_TRY(hipMalloc((void**)&pb.out, total * sizeof(me_book_entry)), "hipMalloc mass cancel");
+    pb.out_cap = total;
+  }
+  HIP_TRY(hipMemcpyAsync(pb.off, off.data(), off.size() * 8, hipMemcpyHostToDevice, e->stream), "H2D mass cancel offsets");
+  rq.out = pb.out;
+  rq.cap = total;
+  he = launch_purge(e->stream, e->bk, rq, true);
+  if (he != hipSuccess) return e->hip_fail(he, "mass cancel launch");
+  // the feeds' jobs behind the purge as behind a match launch, stamped with the unchanged batch count; the
+  // trade feed has nothing to log
+  if (e->quotes.on && (rc = quotes_job(e))) return rc;
+  if (e->depth.on && (rc = depth_job(e))) return rc;
+  unsigned long long resting = 0;
+  HIP_TRY(hipMemcpyAsync(out, pb.out, total * sizeof(me_book_entry), hipMemcpyDeviceToHost, e->stream), "D2H mass cancel orders");
+  HIP_TRY(hipMemcpyAsync(&bad, pb.err, 4, hipMemcpyDeviceToHost, e->stream), "D2H mass cancel error");
+  HIP_TRY(hipMemcpyAsync(&resting, e->bk.stats + ST_RESTING, 8, hipMemcpyDeviceToHost, e->stream), "D2H resting count");
+  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+  if (bad) {  // (the count pass walked the same chains on an idle stream: not reachable)
+    e->failed = true;
+    return e->fail(ME_E_STATE, "corrupt FIFO chain");
+  }
+  // admission control: the exact count, as admit()'s exact() takes it (every accepted record is matched)
+  e->ovr_resting = resting;
+  e->ovr_adm = e->adm_matched;
   return ME_OK;
 }
 

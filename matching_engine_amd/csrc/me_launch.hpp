@@ -44,6 +44,8 @@ hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q);
 hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d);
 hipError_t launch_trades(hipStream_t st, const BookDev& bk, const TradeDev& t, const TradeLaunch& tl);
 hipError_t launch_order_query(hipStream_t st, const BookDev& bk, const OrderQueryReq& rq);
+// the mass cancel's passes: remove = false counts (read-only), true removes
+hipError_t launch_purge(hipStream_t st, const BookDev& bk, const PurgeReq& rq, bool remove);
 
 // ---- me_match_reg.hip, one namespace per build (ng >= 1; launch_match_reg above picks one). Visible
 // only under ME_LAUNCH_REG_VARIANTS, which that dispatcher's file and the defining file set: no other

@@ -511,6 +511,21 @@ struct OrderQueryReq {
   uint32_t pad;
 };
 
+// A mass cancel (me_snapshot.hip k_purge): one workgroup per (request, side), index 2 * request + side
+// (0 bids, 1 asks). The count pass fills cnt; the remove pass writes request i's orders of side k to
+// out[off[2 i + k] ..) in dump order and frees the side.
+struct PurgeReq {
+  const uint32_t* sym;            // [n] symbols, each at most once
+  const uint8_t* sides;           // [n] ME_SIDE_BUY, ME_SIDE_SELL or 3 = both
+  unsigned long long* cnt;        // [n][2] live orders of the side (0 for a side not asked for)
+  const unsigned long long* off;  // [n][2] remove pass: where the side's orders go in out
+  me_book_entry* out;             // [cap] remove pass
+  unsigned long long cap;
+  uint32_t* err;                  // set on a corrupt chain or a far region outside the arena
+  uint32_t n;
+  uint32_t pad;
+};
+
 // ---- the feeds' event ring -----------------------------------------------------------
 // Both feeds log into a bounded ring in pinned, device-mapped memory: event i sits at log[i % cap]. Four
 // control words are kept in HBM (ctl) and mirrored into pinned memory (hctl) by the one thread that ends a

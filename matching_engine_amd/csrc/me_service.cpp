@@ -1763,6 +1763,97 @@ extern "C" int me_service_order_status(me_service* s, const char* client_id, con
   return ME_OK;
 }
 
+// Mass cancel (build extension): the purge itself is one me_mass_cancel; its outcome travels to the owners and
+// to the DB as a slice of CANCEL records that the engine never sees — one per removed order, answered CANCELED
+// with the removed quantity — through deliver(), so updates, live table, book counts and rows move exactly as
+// for cancels the clients had sent.
+extern "C" int me_service_mass_cancel(me_service* s, const char* const* symbols, size_t n, int32_t sides,
+                                      uint64_t* n_cancelled) {
+  if (n_cancelled) *n_cancelled = 0;
+  if (!s) return ME_E_INVALID;
+  if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
+  if (!s->eng) return s->fail(ME_E_INVALID, "mass cancel: the backend has no mass cancel");
+  if (sides < 1 || sides > 3) return s->fail(ME_E_INVALID, "mass cancel: sides must be 1 (buy), 2 (sell) or 3 (both)");
+  std::lock_guard<std::mutex> lf(s->flush_mu);
+  std::vector<uint32_t> sids;
+  std::vector<std::string> names;
+  size_t total = 0;
+  uint64_t id = 0;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (symbols) {
+      std::unordered_map<uint32_t, bool> seen;
+      for (size_t i = 0; i < n; ++i) {
+        if (!symbols[i]) return s->fail(ME_E_INVALID, "mass cancel: null symbol name");
+        auto it = s->sym.find(symbols[i]);
+        if (it == s->sym.end()) return s->fail(ME_E_INVALID, std::string("mass cancel: unknown symbol ") + symbols[i]);
+        if (!seen.emplace(it->second, true).second)
+          return s->fail(ME_E_INVALID, std::string("mass cancel: symbol named twice: ") + symbols[i]);
+        sids.push_back(it->second);
+        names.push_back(it->first);
+      }
+    } else {
+      for (uint32_t c = 0; c < s->names.size(); ++c) {
+        sids.push_back(c);
+        names.push_back(s->names[c]);
+      }
+    }
+    close_open(s);
+    total = s->closed_records;  // inflight is 0 here (flush_mu held)
+    id = s->next_id - 1;        // a cancel's stream position: the last OID allocated
+  }
+  int rc = flush_closed(s, false, total, nullptr, true);
+  if (rc != ME_OK) return rc;
+  if (sids.empty()) return ME_OK;
+  std::vector<uint8_t> sd(sids.size(), (uint8_t)sides);
+  std::vector<uint64_t> counts(2 * sids.size());
+  std::vector<me_book_entry> ent;
+  {
+    std::lock_guard<std::mutex> le(s->eng_mu);
+    size_t need = 0;
+    rc = me_mass_cancel(s->eng, sids.data(), sd.data(), sids.size(), nullptr, 0, &need, counts.data());
+    if (rc == ME_E_CAPACITY && need) {  // sized from *n_out (nothing can rest in between: eng_mu is held)
+      ent.resize(need);
+      rc = me_mass_cancel(s->eng, sids.data(), sd.data(), sids.size(), ent.data(), ent.size(), &need, counts.data());
+    }
+    if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
+    ent.resize(need);
+    if (s->md_on) (void)md_pull(s);  // the purge's feed events carry the last slice's stamp
+    if (s->dp_on) (void)dp_pull(s);
+  }
+  if (n_cancelled) *n_cancelled = ent.size();
+  if (ent.empty()) return ME_OK;
+  Slice sl;
+  std::vector<me_order_result> res(ent.size());
+  size_t k = 0;
+  for (size_t i = 0; i < sids.size(); ++i) {
+    const size_t cnt = (size_t)(counts[2 * i] + counts[2 * i + 1]);
+    ref_add(s, sids[i], (int64_t)cnt);  // the records' own counts: emit_updates releases them
+    for (size_t j = 0; j < cnt && k < ent.size(); ++j, ++k) {
+      const me_book_entry& e = ent[k];
+      sl.seq.push_back(id);
+      sl.px.push_back((int64_t)e.seq);
+      sl.qty.push_back(0);
+      sl.sid.push_back(sids[i]);
+      sl.kind.push_back(ME_KIND(ME_SIDE_BUY, ME_TYPE_LIMIT, ME_OP_CANCEL));
+      sl.meta.push_back(Pending{"", names[i], 0, true, e.seq});
+      res[k].remaining_qty = e.qty;
+      res[k].status = ME_ST_CANCELED;
+    }
+  }
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    s->inflight_records += sl.size();  // (deliver takes them off again)
+  }
+  deliver(s, std::move(sl), std::move(res), std::vector<me_fill>{}, nullptr);
+  std::unique_lock<std::mutex> lq(s->pq_mu);
+  s->pq_cv.wait(lq, [&] { return s->pq_emitted == s->pq.size() && (s->pq.empty() || s->pq_stalled); });
+  if (s->pq_stalled)
+    return s->fail(ME_E_SQLITE, "persistence deferred (" + s->pq_err +
+                                    "); the matched slices are kept and retried at the next flush");
+  return ME_OK;
+}
+
 extern "C" int me_service_market_data(me_service* s, const char* symbol, me_market_data* out) {
   memset(out, 0, sizeof(*out));
   out->scale = 4;

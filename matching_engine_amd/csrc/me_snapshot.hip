@@ -1144,6 +1144,254 @@ hipError_t launch_order_query(hipStream_t st, const BookDev& bk, const OrderQuer
   return hipGetLastError();
 }
 
+// ---- mass cancel (me_mass_cancel, include/me_engine.h) -----------------------------------------------
+// k_purge<REMOVE>: k_book_snapshot's shape, one 1024-thread workgroup per (request, side), over ALL of the
+// side's levels, in passes of up to PURGE_P. The window levels of a pass come from the occupancy words, not
+// from the totals (a window has up to 2^20 levels): every thread takes one word of the side's range, going
+// outward from the best level; a block scan of the popcounts places the words' levels in the pass, and the
+// words that still fit it — a prefix, whole words only — are taken; the cursor stops at the first that does
+// not. Windows of L <= 128 form their (at most two) words from the totals, as the scans do. Far levels
+// follow once the window is exhausted, best (last) first. Every thread then walks the chains of two levels
+// of the pass to count their live slots, and a block scan turns the counts into output offsets.
+//   REMOVE = false writes the side's count and nothing else. REMOVE = true walks each chain a second time:
+// it writes the live slots in slot order to out, zeroes all 16 quantities of every chunk (a freed chunk is
+// zero in HBM before it is listed anywhere), pushes the whole chain onto the symbol's free list (an atomic
+// exchange of free_head with the chain's head, then tail.next = the old head: both sides of a symbol may
+// push at once, nothing pops during the launch), writes Level{0, NIL, NIL} and clears the level's occ bit.
+// Thread 0 ends the side: best_bid = -1 / best_ask = L, nfar = 0, and the removed count off the symbol's
+// resting count and ST_RESTING (atomics: the other side's workgroup does the same). FarDir, fcache, nfree,
+// the seq ring and the old-order table are not touched: their entries are verified against the slot, whose
+// quantity is now 0. A chain that leaves [0, nchunks), takes more than nchunks steps or ends before its
+// tail sets the error word and is left alone; the host runs the count pass first and removes nothing then.
+constexpr int PURGE_P = 2048;  // levels per pass (LDS: 20 B each)
+
+__device__ __forceinline__ unsigned long long purge_occ_word(const BookDev& bk, const Level* lv,
+                                                             const unsigned long long* oc, int wi) {
+  if (bk.L > 128u) return oc[wi];
+  unsigned long long w = 0;
+  for (int b = 0; b < 64; ++b) {
+    const int l = wi * 64 + b;
+    if (l < (int)bk.L && lv[l].total > 0) w |= 1ull << b;
+  }
+  return w;
+}
+
+template <bool REMOVE>
+__global__ __launch_bounds__(SNAP_T) void k_purge(BookDev bk, PurgeReq rq) {
+  __shared__ long long p_price[PURGE_P];
+  __shared__ uint32_t p_head[PURGE_P];  // NIL: nothing to walk (an empty or a corrupt level)
+  __shared__ uint32_t p_tail[PURGE_P];
+  __shared__ int p_lvl[PURGE_P];        // window level, -1 for a far level
+  __shared__ uint32_t wsum[SNAP_T / 64];
+  __shared__ int s_cur;                 // window cursor: the next occ word to look at
+  __shared__ uint32_t s_far;            // far levels taken so far
+  __shared__ uint32_t s_np;             // levels in this pass
+  __shared__ uint32_t s_first;          // first thread of a round whose word did not fit the pass
+  const int tid = threadIdx.x;
+  const uint32_t q = blockIdx.x >> 1, side = blockIdx.x & 1u;
+  const size_t reg = blockIdx.x;
+  const bool bid = side == 0u;
+  const uint32_t s = rq.sym[q];
+  if (!((rq.sides[q] >> side) & 1u) || s >= bk.S) {  // (ME_SIDE_BUY = 1, ME_SIDE_SELL = 2: bit `side`)
+    if (!REMOVE && tid == 0) rq.cnt[reg] = 0ull;
+    return;
+  }
+  if (REMOVE && rq.cnt[reg] == 0ull) return;  // the count pass found the side empty: its hints say so already
+  const int L = (int)bk.L;
+  const SymState st = bk.sym[s];
+  Level* lv = bk.levels + (size_t)s * L;
+  unsigned long long* oc = bk.occ + (size_t)s * bk.Lwords;
+  const FarDir fd = bk.fdir[(size_t)s * 2u + side];
+  const uint32_t nfar = min(st.nfar[side], fd.cap);
+  const unsigned long long fend = 2ull * bk.S * bk.fcap + 2ull * bk.far_half;  // entries of the arena
+  if (nfar && (fd.off > fend || nfar > fend - fd.off)) {
+    if (tid == 0) {
+      atomicOr(rq.err, 1u);
+      if (!REMOVE) rq.cnt[reg] = 0ull;
+    }
+    return;
+  }
+  const FarLevel* far = bk.far + fd.off;
+  // the side's window levels [lo, hi] (none: lo > hi), words [wlo, whi]
+  const int lo = bid ? 0 : max(st.best_ask, 0);
+  const int hi = bid ? min(st.best_bid, L - 1) : L - 1;
+  const int wlo = lo >> 6, whi = hi >> 6;
+  if (tid == 0) {
+    s_cur = lo <= hi ? (bid ? whi : wlo) : (bid ? wlo - 1 : whi + 1);
+    s_far = 0;
+  }
+  __syncthreads();
+  const unsigned long long obase = REMOVE ? rq.off[reg] : 0ull;
+  unsigned long long norders = 0;
+  for (;;) {
+    if (tid == 0) s_np = 0;
+    __syncthreads();
+    // ---- this pass's window levels
+    for (;;) {
+      const int cur = s_cur;
+      const uint32_t np = s_np;
+      if (bid ? cur < wlo : cur > whi) break;
+      __syncthreads();  // everyone holds cur and np
+      if (tid == 0) s_first = SNAP_T;
+      const int wi = bid ? cur - tid : cur + tid;
+      unsigned long long word = 0;
+      if (wi >= wlo && wi <= whi) {
+        word = purge_occ_word(bk, lv, oc, wi);
+        if (wi == wlo) word &= ~0ull << (lo & 63);
+        if (wi == whi && (hi & 63) != 63) word &= (2ull << (hi & 63)) - 1ull;
+      }
+      const uint32_t pc = (uint32_t)__popcll(word);
+      uint32_t all = 0;
+      const uint32_t pos = snap_block_excl_scan(pc, wsum, all);
+      // pos + pc ascends with the thread: the words taken are a prefix of the round
+      if (np + pos + pc > (uint32_t)PURGE_P) {
+        atomicMin(&s_first, (uint32_t)tid);
+      } else if (pc) {
+        atomicMax(&s_np, np + pos + pc);
+        uint32_t at = np + pos;
+        for (unsigned long long m = word; m;) {  // in priority order: bids from the top bit down
+          const int b = bid ? 63 - __builtin_clzll(m) : __builtin_ctzll(m);
+          m &= ~(1ull << b);
+          p_lvl[at++] = wi * 64 + b;
+        }
+      }
+      __syncthreads();
+      const uint32_t first = s_first;
+      if (tid == 0) s_cur = bid ? cur - (int)first : cur + (int)first;
+      __syncthreads();
+      if (first < (uint32_t)SNAP_T) break;  // the pass is full
+    }
+    const uint32_t nw = s_np;
+    for (uint32_t i = tid; i < nw; i += SNAP_T) {
+      const int l = p_lvl[i];
+      const Level x = lv[l];
+      p_price[i] = st.base + l;
+      p_head[i] = x.total > 0 ? x.head : NIL;  // (the total decides, as in the scans)
+      p_tail[i] = x.tail;
+    }
+    // ---- far levels, once the window is exhausted
+    const bool win_done = bid ? s_cur < wlo : s_cur > whi;
+    const uint32_t fr = s_far;
+    const uint32_t nf = win_done ? min((uint32_t)PURGE_P - nw, nfar - fr) : 0u;
+    for (uint32_t j = tid; j < nf; j += SNAP_T) {
+      const FarLevel f = far[nfar - 1u - (fr + j)];
+      p_lvl[nw + j] = -1;
+      p_price[nw + j] = f.price;
+      p_head[nw + j] = f.total > 0 ? f.head : NIL;
+      p_tail[nw + j] = f.tail;
+    }
+    __syncthreads();
+    if (tid == 0) s_far = fr + nf;
+    const uint32_t np = nw + nf;
+    if (np == 0) break;
+    // ---- count every level's live orders (two levels per thread), scan
+    uint32_t cnt[PURGE_P / SNAP_T];
+    uint32_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < PURGE_P / SNAP_T; ++k) {
+      const uint32_t i = (uint32_t)tid * (PURGE_P / SNAP_T) + k;
+      uint32_t c = 0;
+      if (i < np && p_head[i] != NIL) {
+        uint32_t ch = p_head[i], guard = 0;
+        for (;;) {
+          if (ch >= bk.nchunks || ++guard > bk.nchunks) {  // (NIL too: the chain ended before its tail)
+            atomicOr(rq.err, 1u);
+            p_head[i] = NIL;  // (this thread's own entry)
+            c = 0;
+            break;
+          }
+          const int4* qv = reinterpret_cast<const int4*>(bk.chunks[ch].qty);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int4 v = qv[u];
+            c += (v.x > 0) + (v.y > 0) + (v.z > 0) + (v.w > 0);
+          }
+          if (ch == p_tail[i]) break;
+          ch = bk.chunks[ch].hdr.next;
+        }
+      }
+      cnt[k] = c;
+      mine += c;
+    }
+    uint32_t pass_total = 0;
+    uint32_t off = snap_block_excl_scan(mine, wsum, pass_total);
+    if (REMOVE) {
+#pragma unroll
+      for (int k = 0; k < PURGE_P / SNAP_T; ++k) {
+        const uint32_t i = (uint32_t)tid * (PURGE_P / SNAP_T) + k;
+        if (i < np && p_head[i] != NIL) {
+          unsigned long long o = obase + norders + off;
+          const uint32_t head = p_head[i], tail = p_tail[i];
+          uint32_t ch = head;
+          for (;;) {  // (the count walk went head -> tail inside [0, nchunks))
+            Chunk& c = bk.chunks[ch];
+            const uint32_t nxt = c.hdr.next;
+            for (int u = 0; u < ME_C; ++u) {
+              const int qq = c.qty[u];
+              if (qq > 0) {
+                if (o < rq.cap) {
+                  me_book_entry e;
+                  e.seq = c.seq[u];
+                  e.price_q4 = p_price[i];
+                  e.qty = qq;
+                  e.side = bid ? ME_SIDE_BUY : ME_SIDE_SELL;
+                  e.pad[0] = e.pad[1] = e.pad[2] = 0;
+                  rq.out[o] = e;
+                }
+                ++o;
+              }
+            }
+            int4* qv = reinterpret_cast<int4*>(c.qty);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) qv[u] = make_int4(0, 0, 0, 0);
+            if (ch == tail) break;
+            ch = nxt;
+          }
+          const uint32_t old = atomicExch(&bk.sym[s].free_head, head);
+          bk.chunks[tail].hdr.next = old;
+          const int l = p_lvl[i];
+          if (l >= 0) {
+            Level z;
+            z.total = 0;
+            z.head = NIL;
+            z.tail = NIL;
+            lv[l] = z;
+            atomicAnd(&oc[l >> 6], ~(1ull << (l & 63)));
+          }
+        }
+        off += cnt[k];
+      }
+    }
+    norders += pass_total;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (!REMOVE) {
+      rq.cnt[reg] = norders;
+    } else {
+      SymState* ss = bk.sym + s;
+      if (bid) {
+        ss->best_bid = -1;
+        ss->nfar[0] = 0;
+      } else {
+        ss->best_ask = L;
+        ss->nfar[1] = 0;
+      }
+      atomicSub(&ss->resting, (uint32_t)norders);
+      atomicAdd(&bk.stats[ST_RESTING], 0ull - norders);
+    }
+  }
+}
+
+hipError_t launch_purge(hipStream_t st, const BookDev& bk, const PurgeReq& rq, bool remove) {
+  if (!rq.n) return hipSuccess;
+  if (remove)
+    hipLaunchKernelGGL(k_purge<true>, dim3(rq.n * 2), dim3(SNAP_T), 0, st, bk, rq);
+  else
+    hipLaunchKernelGGL(k_purge<false>, dim3(rq.n * 2), dim3(SNAP_T), 0, st, bk, rq);
+  return hipGetLastError();
+}
+
 hipError_t launch_book_snapshot(hipStream_t st, const BookDev& bk, const SnapReq& rq) {
   if (!rq.nsym || !rq.depth) return hipSuccess;
   hipLaunchKernelGGL(k_book_snapshot, dim3(rq.nsym * 2), dim3(SNAP_T), 0, st, bk, rq);

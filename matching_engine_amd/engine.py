@@ -307,6 +307,22 @@ class Engine:
         _check(self.lib, self.h, self.lib.me_book_dump(self.h, symbol, ptr(out), n.value, C.byref(n)))
         return out
 
+    def mass_cancel(self, symbols, sides=3):
+        """me_mass_cancel: remove every resting order of `sides` (SIDE_BUY = 1, SIDE_SELL = 2, 3 = both; one value
+        or one per symbol) of `symbols`. Returns (entries, counts): the removed orders in dump()'s dtype, request
+        by request in dump()'s order, and counts[i] = (bids, asks) removed for symbols[i]."""
+        sym = np.ascontiguousarray(symbols, dtype=np.uint32).reshape(-1)
+        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(sides, dtype=np.uint8), sym.shape))
+        counts = np.zeros((len(sym), 2), dtype=np.uint64)
+        n = C.c_size_t(0)
+        out = np.zeros(0, dtype=BOOK_ENTRY_DTYPE)
+        rc = self.lib.me_mass_cancel(self.h, ptr(sym), ptr(sd), len(sym), None, 0, C.byref(n), ptr(counts))
+        if rc == _abi.ME_E_CAPACITY and n.value:  # sized from *n_out, once
+            out = np.zeros(n.value, dtype=BOOK_ENTRY_DTYPE)
+            rc = self.lib.me_mass_cancel(self.h, ptr(sym), ptr(sd), len(sym), ptr(out), len(out), C.byref(n), ptr(counts))
+        _check(self.lib, self.h, rc)
+        return out[:n.value], counts
+
     def order_query(self, seqs) -> np.ndarray:
         """me_order_query: one ORDER_INFO_DTYPE answer per seq (what the order still holds, its place in its
         level's FIFO, what rests at better prices of its side), from one launch on the current books."""

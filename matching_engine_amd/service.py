@@ -101,6 +101,23 @@ class MatchingEngineService:
         return {"order_id": resp.order_id.decode(), "success": bool(resp.success),
                 "error_message": resp.error_message.decode(), "grpc_status": resp.grpc_status}
 
+    def mass_cancel(self, symbols=None, sides=3) -> int:
+        """me_service_mass_cancel: remove every resting order of `sides` (1 buy, 2 sell, 3 both) of the named
+        symbols (None: every symbol that has a book); returns the number of orders removed. Each owner gets a
+        CANCELED OrderUpdate per order, the rows are persisted, the emptied books count as idle."""
+        n = C.c_uint64(0)
+        if symbols is None:
+            rc = self.lib.me_service_mass_cancel(self.h, None, 0, sides, C.byref(n))
+        else:
+            names = [x.encode() for x in symbols]
+            arr = (C.c_char_p * max(len(names), 1))(*names)
+            rc = self.lib.me_service_mass_cancel(self.h, arr, len(names), sides, C.byref(n))
+        if rc != 0:
+            e = ServiceError(f"mass_cancel failed ({rc}): {self.last_error()}")
+            e.code = rc
+            raise e
+        return n.value
+
     def order_status(self, client_id, order_ids) -> list:
         """OrderStatus (build extension, me_service_order_status): one dict per id with state (OS_NOT_RESTING /
         OS_PENDING / OS_RESTING), side, quantity, price, scale and the queue position (qty_ahead, orders_ahead,
