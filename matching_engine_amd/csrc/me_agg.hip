@@ -2411,6 +2411,7 @@ constexpr uint32_t LW_CX = 1u << 30;   // control word: a cancel (lw_cw's reject
 constexpr uint32_t LW_RJ_MASK = 0x1FFFu;
 // record-field flags of the two events of a cancel (log word bits 7 + x; k_agg_gres's sorted entries bits 16 + x)
 constexpr uint32_t AGG_CXF = 1u << 14, AGG_CXU = 1u << 13, AGG_CXP = 1u << 12;
+constexpr uint32_t RSQ_CX = 0xFFFFFFFFu;  // rsq of a CANCEL / REDUCE record (it takes no seq of its own)
 constexpr uint32_t RI_BIG = 0xFFFFFFFFu;  // rest info of a rest too large to pack (>= 2^25): its cancel hands off
 
 struct alignas(16) GwRi {  // a LIMIT's rest: maker position U, qty << 7 | level (0: none), F at the rest
@@ -2435,7 +2436,7 @@ __device__ __forceinline__ uint32_t a_ldg(const uint32_t* p) {  // (past the L1:
 }
 __device__ __forceinline__ uint32_t a_wsum(uint32_t v) { return (uint32_t)rli64(wave_incl_scan((long long)v), 63); }
 
-// An order from before the group (uniform seq T < gmin): live at the group start in this symbol's window?
+// An order from before the group (uniform seq T <= gmin): live at the group start in this symbol's window?
 // Ring entry, else the old-order table (seq below the horizon); then its live quantity ahead in its level's
 // FIFO. d0 / d1: the descriptor; returns 0 live, 1 unknown (not live), 2 hand off.
 __device__ __forceinline__ uint32_t gw_pre_target(const BookDev& bk, uint32_t s, unsigned long long T, long long base,
@@ -2521,7 +2522,8 @@ __device__ __forceinline__ void gw_prepare_cx(GwBuf& B, const GwBuf& Bp, GwCx& X
     }
     const uint32_t j = rbase + (uint32_t)lane;
     if (v) {
-      rsq[j] = (uint32_t)(oseq - gmin);
+      // (a CANCEL or REDUCE repeats a seq: RSQ_CX, so that no tag of another symbol's record is confirmed by it)
+      rsq[j] = cxr ? RSQ_CX : (uint32_t)(oseq - gmin);
       rjs[j] = (g << AGG_GSHIFT) | oi;
       // a LIMIT of this group the walk may rest: its ring entry names its record until k_agg_gres places it
       // (and its rest info reads "none" until the walker writes it)
@@ -2544,7 +2546,11 @@ __device__ __forceinline__ void gw_prepare_cx(GwBuf& B, const GwBuf& Bp, GwCx& X
     if (c && T >= gmin && T - gmin < (1ull << 32)) {  // this group's order: its tagged ring entry, confirmed by its seq
       const uint32_t e = a_ldg(bk.loc + (T & bk.ring_mask));
       const uint32_t jj = e & ~CX_TAG;
-      if ((e & CX_TAG) && jj < jself && a_ldg((const uint32_t*)&rsq[jj]) == (uint32_t)(T - gmin)) {
+      if ((uint32_t)(T - gmin) == RSQ_CX) {
+        // the mark's own value: no ring below 2^32 entries lets a record of the group reach it, but T is the
+        // client's, so a cancel may still name it; the continuation answers that one (correct, slower)
+        cls = 2u;
+      } else if ((e & CX_TAG) && jj < jself && a_ldg((const uint32_t*)&rsq[jj]) == (uint32_t)(T - gmin)) {
         cls = 0u;
         if (jj >= cut) {  // walked in this batch or the one before: the walker reads the ring; its level now
           const uint32_t cwt = jj >= rb0 ? B.cw[jj - rb0] : Bp.cw[jj - cut];
@@ -2558,7 +2564,10 @@ __device__ __forceinline__ void gw_prepare_cx(GwBuf& B, const GwBuf& Bp, GwCx& X
         }
       }
     }
-    unsigned long long pm = __ballot(c && T < gmin);
+    // T == gmin without a confirmed tag: the cancels that open a group repeat the seq of the last record before
+    // it, so seq gmin may be an order from before the group (gw_pre_target confirms owner, seq and quantity in
+    // the chunk; an unplaced record of this group is in no chunk yet)
+    unsigned long long pm = __ballot(c && (T < gmin || (T == gmin && cls == 1u)));
     while (pm) {  // orders from before the group: one at a time (~0.6 per symbol and group at config 5)
       const int i = __builtin_ctzll(pm);
       pm &= pm - 1ull;

@@ -268,7 +268,6 @@ def test_ring_and_old_table(me, path):
     pair_at = len(script) - 1
     sc.cancel(1, P)
     script.append(sc.take())
-    fillers(1)  # (so that the cancel's own seq, the last one given out, is not its target's)
     sc.cancel(1, Q)
     script.append(sc.take())
     for _ in range(6):  # and on: the table is rebuilt again with A, A2 and the fillers in it
