@@ -344,6 +344,49 @@ typedef struct me_order_info { /* 64 B */
  * level's head: ME_E_STATE "corrupt FIFO chain", as the snapshot calls. */
 int me_order_query(me_engine* e, const uint64_t* seqs, size_t n, me_order_info* out);
 
+/* ---- order preview: what a record would execute against the books now (no reference counterpart) -----
+ * The question asked BEFORE sending an order (an impact quote, a pre-trade check): query i is the NEW record
+ * (q->symbol[i], q->kind[i], q->price_q4[i], q->qty[i]); q->seq is ignored and may be NULL. The answer is what
+ * that record would get if it were the only next record of the stream, on the books at the point me_book_dump
+ * brings the pipeline to (me_sync runs first, so a partial group is launched and matched), from ONE launch of
+ * a read-only kernel (k_order_preview, one wave per query). Queries are independent: none
+ * sees another's effect, duplicates are independent queries. The call changes no book, no seq state, no
+ * counter and no feed; it consumes no seq and is no batch (the feeds' `batches` stamps do not advance).
+ * status, reason, filled_qty, remaining_qty and fill_count equal, field for field, the me_order_result the
+ * matcher gives that record (every time in force on LIMIT and MARKET, the MARKET / IOC remainder convention,
+ * a killed FOK, WOULD_CROSS, BAD_TIF, and BAD_SYMBOL / BAD_QTY / BAD_SIDE in the matcher's reject order;
+ * BAD_SEQ cannot occur: there is no seq). first / last price, notional, levels, fill_count and filled_qty
+ * describe the fills the record would produce and are all zero when it produces none (a killed FOK, any
+ * reject, nothing crossing). flags and opp_price_q4 describe the opposite side as it is now on every accepted
+ * answer, a killed FOK and a WOULD_CROSS reject; they are zero on every other reject.
+ * ADMISSION CONTROL IS NOT CONSULTED: ME_PV_RESTS says the remainder would rest if the record were admitted,
+ * it does not promise room under max_resting. */
+#define ME_PV_HAS_OPP 1u  /* the opposite side holds at least one order; opp_price_q4 is valid */
+#define ME_PV_CROSSES 2u  /* HAS_OPP and (MARKET, or the LIMIT's price reaches opp_price_q4) */
+#define ME_PV_RESTS   4u  /* accepted GTC / POST_ONLY LIMIT with remaining_qty > 0: that remainder would rest */
+typedef struct me_preview { /* 64 B */
+  int64_t first_price_q4;  /* price of the first fill (= opp_price_q4 whenever fill_count > 0) */
+  int64_t last_price_q4;   /* price of the last fill: the worst price reached */
+  int64_t opp_price_q4;    /* best price of the opposite side now (me_quote's rule: window level, else best far level) */
+  int64_t notional_hi;     /* sum over the fills of price_q4 * qty as a signed 128-bit integer: high half ... */
+  uint64_t notional_lo;    /* ... and low half (two's complement). Exact for any int64 price */
+  int32_t filled_qty, remaining_qty;  /* exactly me_order_result's */
+  uint32_t fill_count;     /* exactly me_order_result's: makers touched */
+  uint32_t levels;         /* distinct price levels the fills come from */
+  uint8_t status, reason;  /* exactly me_order_result's (ME_ST_*, ME_RJ_*) */
+  uint8_t flags;           /* ME_PV_* */
+  uint8_t pad[5];          /* zero */
+} me_preview;
+/* Synchronous: one H2D copy of the four arrays, one launch, one D2H copy of the answers (device buffers grown
+ * on demand, as me_order_query's). n == 0: ME_OK, nothing is launched. n > 2^24, or any of q, q->symbol,
+ * q->kind, q->price_q4, q->qty, out NULL with n > 0: ME_E_INVALID. Any kind with bit 3 set (a CANCEL or
+ * REDUCE; checked on the host before anything is copied): ME_E_INVALID, nothing launched, nothing answered.
+ * The argument checks come first: a failed engine given a bad argument or a CANCEL kind answers ME_E_INVALID;
+ * given valid arguments it answers what me_sync answers. A FIFO chain that cannot be walked: ME_E_STATE "corrupt
+ * FIFO chain", as the snapshot calls. Like the order query and the mass cancel, the call exists on an engine only:
+ * not on a cluster, not behind a me_matcher. */
+int me_order_preview(me_engine* e, const me_order_soa* q, size_t n, me_preview* out);
+
 /* ---- mass cancel: empty the named sides of the named symbols' books (no reference counterpart) -------
  * A halt, a delisting, the end-of-session purge, a kill switch: every resting order of sides[i]
  * (ME_SIDE_BUY = 1, ME_SIDE_SELL = 2, 3 = both) of symbols[i] is removed, window levels and far levels

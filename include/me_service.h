@@ -254,6 +254,17 @@ typedef struct me_order_status { /* 88 B */
 int me_service_order_status(me_service* s, const char* client_id, const char* const* order_ids, size_t n,
                             me_order_status* out);
 
+/* PreviewOrder (build extension): what SubmitOrder with this request and time in force would execute against
+ * the book now, from one me_order_preview (me_engine.h) — nothing is submitted. The request passes
+ * me_service_submit_order_tif's validations and Q4 normalisation: one that SubmitOrder would refuse in-band
+ * returns ME_E_INVALID with SubmitOrder's message in me_service_last_error. No OID is taken, nothing is
+ * persisted, nothing enters a slice and no book is claimed. The answer is taken on what was flushed before the
+ * call (me_order_preview's me_sync); like me_service_order_status it flushes no open slice, so orders still
+ * pending in a slice are not in the book it sees. A symbol name that has no book is answered as an empty book
+ * (a LIMIT rests whole, a MARKET / IOC / FOK fills nothing) without touching the engine. Admission control is
+ * not consulted (me_order_preview). A service over a me_matcher has no preview: ME_E_INVALID. */
+int me_service_preview_order(me_service* s, const me_order_request* req, int32_t tif, me_preview* out);
+
 /* Mass cancel (build extension): an operator's action — a halt, a delisting, the end-of-session purge — so
  * there is no owner check. Every resting order of `sides` (ME_SIDE_BUY = 1, ME_SIDE_SELL = 2, 3 = both) of the
  * n named symbols is removed by ONE me_mass_cancel; symbols == NULL means every symbol that has a book. The open

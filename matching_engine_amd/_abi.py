@@ -140,6 +140,19 @@ ORDER_INFO_DTYPE = np.dtype(
      ("found", "u1"), ("pad", "u1", (6,))]
 )
 assert ORDER_INFO_DTYPE.itemsize == 64
+# me_preview: one answer of me_order_preview (the notional is a signed 128-bit integer in two halves: preview_notional)
+PREVIEW_DTYPE = np.dtype(
+    [("first_price_q4", "<i8"), ("last_price_q4", "<i8"), ("opp_price_q4", "<i8"), ("notional_hi", "<i8"),
+     ("notional_lo", "<u8"), ("filled_qty", "<i4"), ("remaining_qty", "<i4"), ("fill_count", "<u4"), ("levels", "<u4"),
+     ("status", "u1"), ("reason", "u1"), ("flags", "u1"), ("pad", "u1", (5,))]
+)
+PV_HAS_OPP, PV_CROSSES, PV_RESTS = 1, 2, 4
+assert PREVIEW_DTYPE.itemsize == 64
+
+
+def preview_notional(row) -> int:
+    """The signed 128-bit notional (sum of price_q4 * qty over the fills) of one PREVIEW_DTYPE row as a Python int."""
+    return (int(row["notional_hi"]) << 64) | int(row["notional_lo"])
 
 
 # ---- raw export of the resident book (me_debug_layout / me_debug_export: diagnostic) -------------------
@@ -224,6 +237,7 @@ PROTOTYPES = {
     "me_book_levels_all": (C.c_int, [_P, C.c_uint32, _P, _P]),
     "me_resting_count": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "me_order_query": (C.c_int, [_P, _P, _SZ, _P]),
+    "me_order_preview": (C.c_int, [_P, C.POINTER(MeOrderSoa), _SZ, _P]),
     "me_mass_cancel": (C.c_int, [_P, _P, _P, _SZ, _P, _SZ, C.POINTER(_SZ), _P]),
     "me_timing_enable": (C.c_int, [_P, C.c_int]),
     "me_timing_read": (
@@ -505,6 +519,7 @@ PROTOTYPES.update({
     "me_service_order_book": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ),
                                         C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ)]),
     "me_service_order_status": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_char_p), _SZ, C.POINTER(MeOrderStatus)]),
+    "me_service_preview_order": (C.c_int, [_P, C.POINTER(MeOrderRequest), C.c_int32, _P]),
     "me_service_mass_cancel": (C.c_int, [_P, C.POINTER(C.c_char_p), _SZ, C.c_int32, C.POINTER(C.c_uint64)]),
     "me_service_cancel_order": (C.c_int, [_P, C.POINTER(MeCancelRequest), C.POINTER(MeOrderResponse)]),
     "me_service_reduce_order": (C.c_int, [_P, C.POINTER(MeReduceRequest), C.POINTER(MeOrderResponse)]),

@@ -295,6 +295,13 @@ struct me_engine {
     uint32_t* err = nullptr;
     size_t cap = 0;  // queries seqs and out hold
   } oq;
+  struct PreviewBufs {  // device buffers of the order preview kernel, grown on demand
+    uint8_t* in = nullptr;  // the four input arrays back to back: px [cap], qty [cap], sym [cap], kind [cap]
+    me_preview* out = nullptr;
+    uint32_t* err = nullptr;
+    size_t cap = 0;              // queries in and out hold
+    std::vector<uint8_t> stage;  // the same layout on the host: one copy carries all four arrays
+  } pv;
   struct PurgeBufs {  // device buffers of the mass cancel kernel, grown on demand
     uint32_t* sym = nullptr;
     uint8_t* sides = nullptr;
@@ -333,7 +340,7 @@ struct me_engine {
   static constexpr uint32_t ADM_RING = 256;
   unsigned long long* pub_host = nullptr;  // hipHostMalloc'd, device-mapped (bk.pub): [0] {launch, resting},
                                            // [1] {launch, hand-offs}, [2] me_sync's error-word copy,
-                                           // [3] me_order_query's
+                                           // [3] me_order_query's and me_order_preview's
   // grouped launches through the aggregate path (hot.agg_reg) chosen by shape, not by ME_REG_AGG: turned
   // off for good when symbols hand off to the continuation in more than 1/16 of their launches (cancels,
   // far prices — config 5's stream), which then pays both paths
@@ -497,7 +504,8 @@ static void free_all(me_engine* e) {
   {
     void* sp[] = {e->snap.sym, e->snap.lv,  e->snap.nlv, e->snap.ord, e->snap.nord,
                   e->snap.err, e->oq.seqs, e->oq.out,   e->oq.err,   e->pg.sym,
-                  e->pg.sides, e->pg.cnt,  e->pg.off,   e->pg.out,   e->pg.err};
+                  e->pg.sides, e->pg.cnt,  e->pg.off,   e->pg.out,   e->pg.err,
+                  e->pv.in,    e->pv.out,  e->pv.err};
     for (void* p : sp)
       if (p) (void)hipFree(p);
   }
@@ -2179,6 +2187,56 @@ extern "C" int me_order_query(me_engine* e, const uint64_t* seqs, size_t n, me_o
   uint32_t* bad = reinterpret_cast<uint32_t*>(e->pub_host + 3);
   HIP_TRY(hipMemcpyAsync(out, qb.out, n * sizeof(me_order_info), hipMemcpyDeviceToHost, e->stream), "D2H order query answers");
   HIP_TRY(hipMemcpyAsync(bad, qb.err, 4, hipMemcpyDeviceToHost, e->stream), "D2H order query error");
+  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+  if (*(volatile uint32_t*)bad) return e->fail(ME_E_STATE, "corrupt FIFO chain");
+  return ME_OK;
+}
+
+// ---- order preview (me_snapshot.hip k_order_preview): one wave per hypothetical record, answers in e->pv
+extern "C" int me_order_preview(me_engine* e, const me_order_soa* q, size_t n, me_preview* out) {
+  if (!e) return ME_E_INVALID;
+  if (n > ((size_t)1 << 24)) return e->fail(ME_E_INVALID, "order preview: more than 2^24 queries");
+  if (n && (!q || !q->symbol || !q->kind || !q->price_q4 || !q->qty || !out))
+    return e->fail(ME_E_INVALID, "order preview: null query arrays or out");
+  for (size_t i = 0; i < n; ++i)
+    if (q->kind[i] & 8u) return e->fail(ME_E_INVALID, "order preview: a CANCEL or REDUCE record cannot be previewed");
+  int rc = me_sync(e);
+  if (rc) return rc;
+  if (!n) return ME_OK;
+  auto& pb = e->pv;
+  if (n > pb.cap) {
+    if (pb.in) HIP_TRY(hipFree(pb.in), "hipFree");
+    pb.in = nullptr;
+    if (pb.out) HIP_TRY(hipFree(pb.out), "hipFree");
+    pb.out = nullptr;
+    pb.cap = 0;
+    HIP_TRY(hipMalloc((void**)&pb.in, n * 17), "hipMalloc order preview");
+    HIP_TRY(hipMalloc((void**)&pb.out, n * sizeof(me_preview)), "hipMalloc order preview");
+    pb.cap = n;
+  }
+  if (!pb.err) HIP_TRY(hipMalloc((void**)&pb.err, 4), "hipMalloc order preview");
+  // px at 0, qty at 8 n, sym at 12 n, kind at 16 n: every array stays aligned to its element
+  pb.stage.resize(n * 17);
+  memcpy(pb.stage.data(), q->price_q4, n * 8);
+  memcpy(pb.stage.data() + n * 8, q->qty, n * 4);
+  memcpy(pb.stage.data() + n * 12, q->symbol, n * 4);
+  memcpy(pb.stage.data() + n * 16, q->kind, n);
+  HIP_TRY(hipMemcpyAsync(pb.in, pb.stage.data(), n * 17, hipMemcpyHostToDevice, e->stream), "H2D order preview queries");
+  HIP_TRY(hipMemsetAsync(pb.err, 0, 4, e->stream), "hipMemset");
+  PreviewReq rq{};
+  rq.px = reinterpret_cast<const int64_t*>(pb.in);
+  rq.qty = reinterpret_cast<const int32_t*>(pb.in + n * 8);
+  rq.sym = reinterpret_cast<const uint32_t*>(pb.in + n * 12);
+  rq.kind = pb.in + n * 16;
+  rq.out = pb.out;
+  rq.err = pb.err;
+  rq.n = (uint32_t)n;
+  hipError_t he = launch_order_preview(e->stream, e->bk, rq);
+  if (he != hipSuccess) return e->hip_fail(he, "order preview launch");
+  // the error word rides behind the answers, as the order query's does
+  uint32_t* bad = reinterpret_cast<uint32_t*>(e->pub_host + 3);
+  HIP_TRY(hipMemcpyAsync(out, pb.out, n * sizeof(me_preview), hipMemcpyDeviceToHost, e->stream), "D2H order preview answers");
+  HIP_TRY(hipMemcpyAsync(bad, pb.err, 4, hipMemcpyDeviceToHost, e->stream), "D2H order preview error");
   HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
   if (*(volatile uint32_t*)bad) return e->fail(ME_E_STATE, "corrupt FIFO chain");
   return ME_OK;

@@ -44,6 +44,7 @@ hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q);
 hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d);
 hipError_t launch_trades(hipStream_t st, const BookDev& bk, const TradeDev& t, const TradeLaunch& tl);
 hipError_t launch_order_query(hipStream_t st, const BookDev& bk, const OrderQueryReq& rq);
+hipError_t launch_order_preview(hipStream_t st, const BookDev& bk, const PreviewReq& rq);
 // the mass cancel's passes: remove = false counts (read-only), true removes
 hipError_t launch_purge(hipStream_t st, const BookDev& bk, const PurgeReq& rq, bool remove);
 

@@ -511,6 +511,18 @@ struct OrderQueryReq {
   uint32_t pad;
 };
 
+// An order preview (me_snapshot.hip k_order_preview): one wave per hypothetical NEW record.
+struct PreviewReq {
+  const uint32_t* sym;       // [n]
+  const uint8_t* kind;       // [n] NEW records only (the host refuses bit 3)
+  const int64_t* px;         // [n]
+  const int32_t* qty;        // [n]
+  me_preview* out;           // [n] answers, in the order of the queries
+  uint32_t* err;             // set on a chain that cannot be walked or a far region outside the arena
+  uint32_t n;
+  uint32_t pad;
+};
+
 // A mass cancel (me_snapshot.hip k_purge): one workgroup per (request, side), index 2 * request + side
 // (0 bids, 1 asks). The count pass fills cnt; the remove pass writes request i's orders of side k to
 // out[off[2 i + k] ..) in dump order and frees the side.

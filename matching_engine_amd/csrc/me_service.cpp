@@ -1763,6 +1763,53 @@ extern "C" int me_service_order_status(me_service* s, const char* client_id, con
   return ME_OK;
 }
 
+// PreviewOrder (build extension): SubmitOrder's checks in SubmitOrder's order (a refusal it would answer in-band
+// is ME_E_INVALID with its message here), then one me_order_preview. Nothing of the service changes: no OID, no
+// slice, no live entry, and a name without a book is not interned — its book is empty, so is its answer.
+extern "C" int me_service_preview_order(me_service* s, const me_order_request* r, int32_t tif, me_preview* out) {
+  if (!s) return ME_E_INVALID;
+  if (!r || !out) return s->fail(ME_E_INVALID, "order preview: null request or out");
+  if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
+  if (!s->eng) return s->fail(ME_E_INVALID, "order preview: the backend has no order preview");
+  const char* symbol = r->symbol ? r->symbol : "";
+  if (!symbol[0]) return s->fail(ME_E_INVALID, "symbol is required");
+  if (r->quantity <= 0) return s->fail(ME_E_INVALID, "quantity must be > 0");
+  if (r->order_type == ME_TYPE_LIMIT && r->price <= 0) return s->fail(ME_E_INVALID, "price must be > 0 for LIMIT");
+  if (tif < ME_TIF_GTC || tif > ME_TIF_POST_ONLY || (tif == ME_TIF_POST_ONLY && r->order_type != ME_TYPE_LIMIT))
+    return s->fail(ME_E_INVALID, "invalid time in force");
+  int64_t q4 = 0;
+  const int nr = me_normalize_to_q4(r->price, r->scale, &q4);
+  if (nr != 0) return s->fail(ME_E_INVALID, nr == 1 ? "scale out of range" : (nr == 2 ? "overflow" : "underflow"));
+  if (r->side != ME_SIDE_BUY && r->side != ME_SIDE_SELL) return s->fail(ME_E_INVALID, "DB insert failed");
+  const bool limit = r->order_type == ME_TYPE_LIMIT;
+  const uint8_t kd = ME_KIND_TIF(r->side, limit ? ME_TYPE_LIMIT : ME_TYPE_MARKET, ME_OP_NEW, tif);
+  uint32_t sid = 0;
+  bool known = false;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    auto it = s->sym.find(symbol);
+    if ((known = it != s->sym.end())) sid = it->second;
+  }
+  if (!known) {  // an empty book: a GTC / POST_ONLY LIMIT rests whole, everything else fills nothing
+    memset(out, 0, sizeof *out);
+    out->remaining_qty = r->quantity;
+    const bool rests = limit && (tif == ME_TIF_GTC || tif == ME_TIF_POST_ONLY);
+    out->status = rests ? ME_ST_NEW : ME_ST_CANCELED;
+    out->flags = rests ? ME_PV_RESTS : 0;
+    return ME_OK;
+  }
+  const int32_t qty = r->quantity;
+  me_order_soa q{};
+  q.price_q4 = &q4;
+  q.qty = &qty;
+  q.symbol = &sid;
+  q.kind = &kd;
+  std::lock_guard<std::mutex> le(s->eng_mu);
+  const int rc = me_order_preview(s->eng, &q, 1, out);
+  if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
+  return ME_OK;
+}
+
 // Mass cancel (build extension): the purge itself is one me_mass_cancel; its outcome travels to the owners and
 // to the DB as a slice of CANCEL records that the engine never sees — one per removed order, answered CANCELED
 // with the removed quantity — through deliver(), so updates, live table, book counts and rows move exactly as

@@ -1144,6 +1144,253 @@ hipError_t launch_order_query(hipStream_t st, const BookDev& bk, const OrderQuer
   return hipGetLastError();
 }
 
+// ---- order preview (me_order_preview, include/me_engine.h) -------------------------------------------
+// k_order_preview: one wave per hypothetical NEW record, four per workgroup, read-only, no LDS. After the
+// matcher's rejects (BAD_SYMBOL, BAD_QTY, BAD_SIDE, BAD_TIF, in that order) the wave walks the side the record
+// would trade against, best level first, in BLOCKS of up to 64 levels, lane order = priority order:
+//   window  outward from the side's best hint (asks ascend, bids descend) through gate words, 64 words a
+//           load: a deep window's occupancy words, so that only the totals under set bits are loaded; for
+//           L <= 128 all-ones words, so that every level of the block is loaded (oq_window's two modes);
+//   far     once the window is exhausted, the side's far entries from the end (best last), 64 a block; the
+//           region is checked against the arena first, as k_order_query does.
+// pv_block does the rest. A level counts when its total is > 0 (the total decides, a set bit over a total
+// <= 0 and a dead far entry are stepped over). The first such level is the opposite best. The limit clips by
+// price: every lane compares its level's own price with the limit, a signed int64 compare — no price
+// difference is ever formed, so any int64 limit and any window base are exact — and the first counted level
+// beyond the limit ends the walk (prices only get worse behind it; by Invariant I that also keeps a limit
+// short of the window's far edge away from the far levels). A wave_incl_scan of the totals finds where the
+// running sum reaches the quantity wanted: lane i takes min(max(want - before_i, 0), total_i). Every lane
+// that takes anything adds price x taken to the notional as a 128-bit product from 64-bit halves, and the
+// wave then walks that level's FIFO for fill_count (pv_chain): lanes 0..15 hold a chunk's quantities, a scan
+// counts the live makers whose running quantity starts below what is taken there — all of them on a level
+// consumed whole. One dependent HBM round trip per chunk; every chunk id is checked against nchunks before
+// it is dereferenced, a walk ends after nchunks steps at the latest and must cover the quantity by the
+// level's tail; a violation sets the request's error word, nothing is read out of bounds.
+//   A POST_ONLY needs the opposite best alone: the same walk wanting nothing. A FOK walks twice: first the
+// totals only (no chain, nothing committed), and only when they cover its quantity the walk that counts.
+constexpr int PV_WAVES = 4;
+
+struct PvWalk {  // wave-uniform
+  long long limit;
+  long long want;  // quantity still to take
+  bool buy, market;
+  bool count;      // walk the chains of the levels taken (fill_count)
+  bool has_opp, bad;
+  long long opp_px, first_px, last_px;
+  unsigned long long nlo;  // notional: low half ...
+  long long nhi;           // ... and high half
+  uint32_t levels, fills;
+};
+
+// fill_count of one level: the live makers from the head whose running quantity starts below `need`.
+__device__ __forceinline__ void pv_chain(const BookDev& bk, PvWalk& w, uint32_t head, uint32_t tail, long long need) {
+  const int lane = lane_id();
+  const uint32_t NC = bk.nchunks;
+  uint32_t ch = head, steps = 0;
+  for (;;) {
+    if (ch >= NC || ++steps > NC) {  // (NIL too)
+      w.bad = true;
+      return;
+    }
+    const int qv = lane < ME_C ? bk.chunks[ch].qty[lane] : 0;
+    const uint32_t nx = rl32(bk.chunks[ch].hdr.next, 0);
+    const long long uq = qv > 0 ? qv : 0;
+    const long long incl = wave_incl_scan(uq);
+    w.fills += (uint32_t)__popcll(__ballot(uq > 0 && incl - uq < need));
+    const long long live = rli64(incl, 63);
+    if (live >= need) return;
+    need -= live;
+    if (ch == tail) {  // the chain holds less than the level's total says
+      w.bad = true;
+      return;
+    }
+    ch = nx;
+  }
+}
+
+// One block of the walk: this lane's level (total <= 0: none). True when the walk is over.
+__device__ __forceinline__ bool pv_block(const BookDev& bk, PvWalk& w, long long price, long long total, uint32_t head,
+                                         uint32_t tail) {
+  const int lane = lane_id();
+  const bool occ = total > 0;
+  const unsigned long long mo = __ballot(occ);
+  if (!mo) return false;
+  if (!w.has_opp) {
+    w.has_opp = true;
+    w.opp_px = rli64(price, __builtin_ctzll(mo));
+  }
+  const bool beyond = occ && !w.market && (w.buy ? price > w.limit : price < w.limit);
+  const unsigned long long mb = __ballot(beyond);
+  const bool in = occ && (!mb || lane < __builtin_ctzll(mb));
+  const long long t = in ? total : 0;
+  const long long incl = wave_incl_scan(t);
+  long long take = w.want - (incl - t);
+  take = take < 0 ? 0 : (take < t ? take : t);
+  const unsigned long long mt = __ballot(take > 0);
+  if (mt) {
+    if (!w.levels) w.first_px = rli64(price, __builtin_ctzll(mt));
+    w.last_px = rli64(price, 63 - __builtin_clzll(mt));
+    w.levels += (uint32_t)__popcll(mt);
+    // price x take, take <= INT32_MAX: the signed 128-bit product from 64-bit halves, summed over the wave in
+    // three 64-bit columns (the low half as two 32-bit columns: 64 of them cannot carry out of 64 bits)
+    const unsigned long long plo = (unsigned long long)price * (unsigned long long)take;
+    const long long phi = __mul64hi(price, take);
+    const unsigned long long c0 = (unsigned long long)oq_wave_sum((long long)(plo & 0xFFFFFFFFull));
+    const unsigned long long c1 = (unsigned long long)oq_wave_sum((long long)(plo >> 32));
+    const unsigned long long chi = (unsigned long long)oq_wave_sum(phi);
+    const unsigned long long lo = c0 + (c1 << 32);
+    const unsigned long long hi = chi + (c1 >> 32) + (lo < c0 ? 1ull : 0ull);
+    const unsigned long long nlo = w.nlo + lo;
+    w.nhi = (long long)((unsigned long long)w.nhi + hi + (nlo < lo ? 1ull : 0ull));
+    w.nlo = nlo;
+    if (w.count) {
+      for (unsigned long long m = mt; m; m &= m - 1ull) {
+        const int j = __builtin_ctzll(m);
+        pv_chain(bk, w, rl32(head, j), rl32(tail, j), rli64(take, j));
+      }
+    }
+    const long long got = rli64(incl, 63);
+    w.want -= got < w.want ? got : w.want;
+  }
+  return mb != 0ull || w.want == 0;
+}
+
+// The whole walk of symbol s's side opposite to the record: window, then far levels.
+__device__ __forceinline__ void pv_walk(const BookDev& bk, uint32_t s, PvWalk& w) {
+  const int lane = lane_id();
+  const SymState st = bk.sym[s];
+  const long long base = rli64(st.base, 0);
+  const int L = (int)bk.L, W = (int)bk.Lwords;
+  const bool bid = !w.buy;  // a SELL walks the bids
+  const int start = bid ? min(rli32(st.best_bid, 0), L - 1) : max(rli32(st.best_ask, 0), 0);
+  if (bid ? start >= 0 : start < L) {
+    const Level* lv = bk.levels + (size_t)s * L;
+    const unsigned long long* oc = bk.occ + (size_t)s * bk.Lwords;
+    const bool deep = bk.L > 128u;
+    const int sb = start & 63;
+    unsigned long long first = bid ? (sb == 63 ? ~0ull : (1ull << (sb + 1)) - 1ull) : ~0ull << sb;
+    for (int w0 = start >> 6; bid ? w0 >= 0 : w0 < W; w0 += bid ? -64 : 64) {
+      const int wi = bid ? w0 - lane : w0 + lane;
+      unsigned long long word = wi >= 0 && wi < W ? (deep ? oc[wi] : ~0ull) : 0ull;
+      if (lane == 0) word &= first;
+      first = ~0ull;
+      for (unsigned long long nz = __ballot(word != 0ull); nz; nz &= nz - 1ull) {
+        const int j = __builtin_ctzll(nz);
+        const unsigned long long g = rl64(word, j);
+        const int bit = bid ? 63 - lane : lane;  // a word's bids go from its top bit down
+        const int l = (bid ? w0 - j : w0 + j) * 64 + bit;
+        Level x;
+        x.total = 0;
+        x.head = x.tail = NIL;
+        if (((g >> bit) & 1ull) && l < L) x = lv[l];
+        if (pv_block(bk, w, base + l, x.total, x.head, x.tail)) return;
+      }
+    }
+  }
+  const uint32_t k = bid ? 0u : 1u;
+  const uint32_t nhint = rl32(bid ? st.nfar[0] : st.nfar[1], 0);
+  if (!nhint) return;
+  const FarDir fd = bk.fdir[(size_t)s * 2u + k];
+  const uint32_t nfar = min(nhint, rl32(fd.cap, 0));
+  const unsigned long long foff = rl64(fd.off, 0);
+  const unsigned long long fend = 2ull * bk.S * bk.fcap + 2ull * bk.far_half;  // entries of the arena
+  if (foff > fend || nfar > fend - foff) {
+    w.bad = true;
+    return;
+  }
+  const gptr<FarLevel> far = (gptr<FarLevel>)(bk.far + foff);  // (global_* loads, as k_order_query's)
+  for (uint32_t i0 = 0; i0 < nfar; i0 += 64u) {
+    const uint32_t i = i0 + (uint32_t)lane;
+    FarLevel f{};
+    if (i < nfar) f = far[nfar - 1u - i];
+    if (pv_block(bk, w, f.price, f.total, f.head, f.tail)) return;
+  }
+}
+
+__global__ __launch_bounds__(PV_WAVES * 64) void k_order_preview(BookDev bk, PreviewReq rq) {
+  const int lane = lane_id();
+  const uint32_t qi = blockIdx.x * PV_WAVES + (threadIdx.x >> 6);
+  if (qi >= rq.n) return;  // (whole waves leave: the kernel has no block barrier)
+  const uint32_t s = rl32(rq.sym[qi], 0);
+  const uint32_t kd = rl32((uint32_t)rq.kind[qi], 0);
+  const long long px = rli64(rq.px[qi], 0);
+  const int qty = rli32(rq.qty[qi], 0);
+  const uint32_t side = kd & 3u, tif = kd_tif(kd);
+  const bool market = (kd & 4u) != 0u;
+  me_preview o{};
+  bool bad = false;
+  uint32_t rj = ME_RJ_NONE;
+  if (s >= bk.S)
+    rj = ME_RJ_BAD_SYMBOL;
+  else if (qty <= 0)
+    rj = ME_RJ_BAD_QTY;
+  else if (side != (uint32_t)ME_SIDE_BUY && side != (uint32_t)ME_SIDE_SELL)
+    rj = ME_RJ_BAD_SIDE;
+  else if (tif == (uint32_t)ME_TIF_POST_ONLY && market)
+    rj = ME_RJ_BAD_TIF;
+  if (rj != ME_RJ_NONE) {
+    o.status = ME_ST_REJECTED;
+    o.reason = (uint8_t)rj;
+    o.remaining_qty = rj == ME_RJ_BAD_SYMBOL || rj == ME_RJ_BAD_QTY ? 0 : qty;
+  } else {
+    PvWalk w;
+    for (bool again = false;; again = true) {  // (a second time only for a fillable FOK: the walk that counts)
+      w = PvWalk{};
+      w.limit = px;
+      w.buy = side == (uint32_t)ME_SIDE_BUY;
+      w.market = market;
+      w.want = tif == (uint32_t)ME_TIF_POST_ONLY ? 0 : qty;
+      w.count = again || tif == (uint32_t)ME_TIF_GTC || tif == (uint32_t)ME_TIF_IOC;
+      pv_walk(bk, s, w);
+      if (again || tif != (uint32_t)ME_TIF_FOK || w.want != 0 || w.bad) break;
+    }
+    const bool has_opp = w.has_opp;
+    const long long opp_px = w.opp_px;
+    const bool crosses = has_opp && (market || (w.buy ? opp_px <= px : opp_px >= px));
+    const bool exec = w.count;  // w describes an execution
+    bad = w.bad;
+    o.remaining_qty = qty;
+    if (tif == (uint32_t)ME_TIF_POST_ONLY) {
+      o.status = crosses ? ME_ST_REJECTED : ME_ST_NEW;
+      o.reason = crosses ? ME_RJ_WOULD_CROSS : ME_RJ_NONE;
+      if (!crosses) o.flags |= ME_PV_RESTS;
+    } else if (!exec) {  // a killed FOK
+      o.status = ME_ST_CANCELED;
+    } else {
+      const int rem = (int)w.want;
+      o.filled_qty = qty - rem;
+      o.remaining_qty = rem;
+      o.fill_count = w.fills;
+      o.levels = w.levels;
+      o.first_price_q4 = w.first_px;
+      o.last_price_q4 = w.last_px;
+      o.notional_hi = w.nhi;
+      o.notional_lo = w.nlo;
+      if (market || tif != (uint32_t)ME_TIF_GTC) {
+        o.status = rem == 0 ? ME_ST_FILLED : ME_ST_CANCELED;
+      } else {
+        o.status = rem == 0 ? ME_ST_FILLED : (rem < qty ? ME_ST_PARTIALLY_FILLED : ME_ST_NEW);
+        if (rem > 0) o.flags |= ME_PV_RESTS;
+      }
+    }
+    if (has_opp) {
+      o.flags |= ME_PV_HAS_OPP;
+      o.opp_price_q4 = opp_px;
+    }
+    if (crosses) o.flags |= ME_PV_CROSSES;
+  }
+  if (lane == 0) {
+    if (bad) atomicOr(rq.err, 1u);
+    rq.out[qi] = o;
+  }
+}
+
+hipError_t launch_order_preview(hipStream_t st, const BookDev& bk, const PreviewReq& rq) {
+  if (!rq.n) return hipSuccess;
+  hipLaunchKernelGGL(k_order_preview, dim3((rq.n + PV_WAVES - 1u) / PV_WAVES), dim3(PV_WAVES * 64), 0, st, bk, rq);
+  return hipGetLastError();
+}
+
 // ---- mass cancel (me_mass_cancel, include/me_engine.h) -----------------------------------------------
 // k_purge<REMOVE>: k_book_snapshot's shape, one 1024-thread workgroup per (request, side), over ALL of the
 // side's levels, in passes of up to PURGE_P. The window levels of a pass come from the occupancy words, not

@@ -331,6 +331,18 @@ class Engine:
         _check(self.lib, self.h, self.lib.me_order_query(self.h, ptr(q), len(q), ptr(out)))
         return out
 
+    def order_preview(self, symbol, kind, price_q4, qty) -> np.ndarray:
+        """me_order_preview: one PREVIEW_DTYPE answer per hypothetical NEW record (symbol, kind, price_q4, qty) —
+        what it would execute against the books as they stand, from one read-only launch. Four equal-length
+        arrays, or scalars (broadcast against the others). Nothing is submitted and nothing changes."""
+        sy, kd, px, qt = np.broadcast_arrays(np.asarray(symbol, dtype=np.uint32), np.asarray(kind, dtype=np.uint8),
+                                             np.asarray(price_q4, dtype=np.int64), np.asarray(qty, dtype=np.int32))
+        sy, kd, px, qt = (np.ascontiguousarray(a).reshape(-1) for a in (sy, kd, px, qt))
+        out = np.zeros(len(sy), dtype=_abi.PREVIEW_DTYPE)
+        soa = MeOrderSoa(None, ptr(px), ptr(qt), ptr(sy), ptr(kd))
+        _check(self.lib, self.h, self.lib.me_order_preview(self.h, C.byref(soa), len(sy), ptr(out)))
+        return out
+
     def resting_count(self) -> int:
         v = C.c_uint64(0)
         _check(self.lib, self.h, self.lib.me_resting_count(self.h, C.byref(v)))

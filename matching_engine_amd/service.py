@@ -101,6 +101,20 @@ class MatchingEngineService:
         return {"order_id": resp.order_id.decode(), "success": bool(resp.success),
                 "error_message": resp.error_message.decode(), "grpc_status": resp.grpc_status}
 
+    def preview_order(self, client_id, symbol, order_type, side, price, scale, quantity, tif=0) -> np.ndarray:
+        """PreviewOrder (build extension, me_service_preview_order): what submit_order with the same arguments
+        would execute against the book now, as one PREVIEW_DTYPE row; nothing is submitted, no OID is taken. A
+        request submit_order would refuse in-band raises ServiceError (code ME_E_INVALID) with its message; so
+        does a service over a matcher."""
+        req = MeOrderRequest(client_id.encode(), symbol.encode(), order_type, side, price, scale, quantity)
+        out = np.zeros(1, dtype=_abi.PREVIEW_DTYPE)
+        rc = self.lib.me_service_preview_order(self.h, C.byref(req), tif, ptr(out))
+        if rc != 0:
+            e = ServiceError(f"preview_order failed ({rc}): {self.last_error()}")
+            e.code = rc
+            raise e
+        return out[0]
+
     def mass_cancel(self, symbols=None, sides=3) -> int:
         """me_service_mass_cancel: remove every resting order of `sides` (1 buy, 2 sell, 3 both) of the named
         symbols (None: every symbol that has a book); returns the number of orders removed. Each owner gets a
