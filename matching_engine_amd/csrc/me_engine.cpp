@@ -737,7 +737,7 @@ extern "C" me_engine* me_create(const me_config* cfg) {
   ALLOC(bk.sym, S);
   ALLOC(bk.chunks, nchunks);
   ALLOC(bk.loc, ring);
-  ALLOC(bk.far, S * 2 * (uint64_t)bk.fcap + 2 * bk.far_half);
+  ALLOC(bk.far, far_arena_entries(bk));
   ALLOC(bk.fdir, S * 2);
   ALLOC(bk.far_ctl, FC_N);
   ALLOC(bk.old, oldn);
@@ -2501,7 +2501,7 @@ extern "C" int me_debug_export(me_engine* e, uint32_t which, void* dst, size_t c
     case ME_DBG_LOC: src = bk.loc, nb = (size_t)(bk.ring_mask + 1) * sizeof(uint32_t); break;
     case ME_DBG_OLD: src = bk.old, nb = (size_t)(bk.old_mask + 1) * sizeof(OldEnt); break;
     case ME_DBG_SQ: src = bk.sq, nb = 2 * sizeof(SeqState); break;
-    case ME_DBG_FAR: src = bk.far, nb = (size_t)(2ull * S * bk.fcap + 2ull * bk.far_half) * sizeof(FarLevel); break;
+    case ME_DBG_FAR: src = bk.far, nb = (size_t)far_arena_entries(bk) * sizeof(FarLevel); break;
     case ME_DBG_FDIR: src = bk.fdir, nb = 2 * S * sizeof(FarDir); break;
     case ME_DBG_FAR_CTL: src = bk.far_ctl, nb = FC_N * sizeof(unsigned long long); break;
     case ME_DBG_CHUNK_TOP: src = bk.chunk_top, nb = sizeof(uint32_t); break;

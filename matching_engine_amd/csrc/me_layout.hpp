@@ -347,6 +347,10 @@ struct BookDev {
   uint32_t* recl;         // [nchunks] free chunk ids found by the last reclamation (k_seq_sweep)
   uint32_t* cpool;        // [CP_N] {nrecl, fresh, found counter, ticket}
 };
+// Entries of the far arena (BookDev::far): every FarDir region lies inside [0, far_arena_entries).
+__host__ __device__ __forceinline__ unsigned long long far_arena_entries(const BookDev& bk) {
+  return 2ull * bk.S * bk.fcap + 2ull * bk.far_half;
+}
 
 // ---- chunk pool ------------------------------------------------------------------------------------
 // Chunks are drawn by one atomic add on *chunk_top (a block of consecutive allocation numbers); the

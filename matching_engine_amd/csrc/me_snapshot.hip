@@ -14,8 +14,11 @@
 // Bytes per resting order: one 256-B chunk read per 16 orders (twice: count + write) + 24 B out;
 // per level 16 B (window) or 32 B (far) read + 24 B out. HBM-bound in principle, latency-bound in
 // practice (dependent chunk loads).
+//
+// The rules every reader kernel of this file follows, and the walks they share, are in me_bookread.hpp.
 #include <hip/hip_runtime.h>
 
+#include "me_bookread.hpp"
 #include "me_far.hpp"
 #include "me_launch.hpp"
 #include "me_layout.hpp"
@@ -63,9 +66,8 @@ __global__ __launch_bounds__(SNAP_T) void k_book_snapshot(BookDev bk, SnapReq rq
   const int L = (int)bk.L;
   const SymState st = bk.sym[s];
   const Level* lv = bk.levels + (size_t)s * L;
-  const FarDir fd = bk.fdir[(size_t)s * 2u + side];
-  const FarLevel* far = bk.far + fd.off;
-  const uint32_t nfar = min(st.nfar[side], fd.cap);
+  FarSide fs;
+  if (!far_side(bk, s, side, st.nfar[side], fs) && tid == 0) atomicOr(rq.err, 1u);  // (no far levels then)
   const size_t reg = (size_t)q * 2 + side;
   me_level* lv_out = rq.lv + reg * rq.depth;
   me_book_entry* ord_out = rq.ord ? rq.ord + reg * rq.ocap : nullptr;
@@ -113,9 +115,9 @@ __global__ __launch_bounds__(SNAP_T) void k_book_snapshot(BookDev bk, SnapReq rq
     {
       const uint32_t np = s_np;
       const uint32_t fr = s_far;
-      const uint32_t nf = min(want - np, nfar - fr);
+      const uint32_t nf = min(want - np, fs.n - fr);
       for (uint32_t j = tid; j < nf; j += SNAP_T) {
-        const FarLevel f = far[nfar - 1 - (fr + j)];
+        const FarLevel f = far_nth(fs, fr + j);
         p_price[np + j] = f.price;
         p_total[np + j] = f.total;
         p_head[np + j] = f.head;
@@ -137,23 +139,7 @@ __global__ __launch_bounds__(SNAP_T) void k_book_snapshot(BookDev bk, SnapReq rq
     for (int k = 0; k < SNAP_P / SNAP_T; ++k) {
       const uint32_t i = (uint32_t)tid * (SNAP_P / SNAP_T) + k;
       uint32_t c = 0;
-      if (i < np) {
-        uint32_t ch = p_head[i], guard = 0;
-        while (ch != NIL) {
-          if (ch >= bk.nchunks || ++guard > bk.nchunks) {
-            atomicOr(rq.err, 1u);
-            break;
-          }
-          const int4* qv = reinterpret_cast<const int4*>(bk.chunks[ch].qty);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int4 v = qv[u];
-            c += (v.x > 0) + (v.y > 0) + (v.z > 0) + (v.w > 0);
-          }
-          if (ch == p_tail[i]) break;
-          ch = bk.chunks[ch].hdr.next;
-        }
-      }
+      if (i < np && !chain_live(bk, p_head[i], p_tail[i], c)) atomicOr(rq.err, 1u);
       cnt[k] = c;
       mine += c;
     }
@@ -182,21 +168,7 @@ __global__ __launch_bounds__(SNAP_T) void k_book_snapshot(BookDev bk, SnapReq rq
         uint32_t ch = p_head[i], guard = 0;
         while (ch != NIL && ch < bk.nchunks && ++guard <= bk.nchunks) {
           const Chunk& c = bk.chunks[ch];
-          for (int u = 0; u < ME_C; ++u) {
-            const int qq = c.qty[u];
-            if (qq > 0) {
-              if (o < rq.ocap) {
-                me_book_entry e;
-                e.seq = c.seq[u];
-                e.price_q4 = p_price[i];
-                e.qty = qq;
-                e.side = side == 0 ? ME_SIDE_BUY : ME_SIDE_SELL;
-                e.pad[0] = e.pad[1] = e.pad[2] = 0;
-                ord_out[o] = e;
-              }
-              ++o;
-            }
-          }
+          o = chunk_entries(c, p_price[i], side == 0, ord_out, o, rq.ocap);
           if (ch == p_tail[i]) break;
           ch = c.hdr.next;
         }
@@ -260,12 +232,12 @@ __device__ __forceinline__ void feed_publish(const FeedRing<Ev>& r, unsigned lon
 __device__ __forceinline__ bool quote_far_best(const BookDev& bk, uint32_t s, uint32_t side, uint32_t nfar,
                                                long long& px, long long& qty) {
   if (!nfar) return false;
-  const FarDir fd = bk.fdir[(size_t)s * 2u + side];
-  const FarLevel* far = bk.far + fd.off;
-  for (uint32_t n = min(nfar, fd.cap); n; --n) {
-    const long long t = far[n - 1].total;
+  FarSide fs;
+  far_side(bk, s, side, nfar, fs);  // (a region outside the arena: no far level, the feed has no error word)
+  for (uint32_t n = fs.n; n; --n) {
+    const long long t = fs.lv[n - 1].total;
     if (t > 0) {
-      px = far[n - 1].price;
+      px = fs.lv[n - 1].price;
       qty = t;
       return true;
     }
@@ -369,12 +341,10 @@ hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q) {
 // occupied levels, window first, then far — diffs it against the published view and writes the side's
 // candidate events (at their ranks), its candidate view and its event count. A side whose window is empty
 // by the hints, with no far level and an empty published view, costs the 64-B state and one count.
-//   The window walk goes outward from the hint (a bound) in blocks of 64 levels: lane i
-// holds level 64 b + i, a ballot of total > 0 and a popcount of the bits of better priority compact the
-// occupied levels into the view. Windows of L <= 128 load every total of a block (two blocks at most);
-// deeper windows read the occ words, 64 words = 4,096 levels per load, visit only blocks with a set bit
-// and load only the totals under set bits: the total decides, a set bit over a total <= 0 is skipped.
-// The ask walk starts no lower than one level above the best bid found, as k_quote_scan's does.
+//   Both parts come in blocks of 64 levels in priority order (walk_window, walk_far: me_bookread.hpp); a
+// ballot of total > 0 and a popcount of the lanes below compact a block's occupied levels into the view.
+// The ask walk starts no lower than one level above the best bid found (a bid walk wanting one level), as
+// k_quote_scan's does.
 //   The diff stages both lists (<= 32 entries each, sorted) in LDS: lanes 0..31 own the new view's
 // entries, lanes 32..63 the published ones; each runs down the other list once for "is my price there,
 // with which total" and "how many of its entries beat my price". A new entry emits a SET unless published
@@ -396,62 +366,19 @@ constexpr uint32_t DEPTH_EMIT_WAVES = 2048;  // waves of the emit pass at most (
 
 __device__ __forceinline__ void depth_wave_order() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 
-// Block b of the window (levels 64 b .. 64 b + 63): the lanes of `gate` load their level's total; the
-// occupied ones go to view[found ..] in priority order (view may be null: a search). `best` takes the
-// first occupied level found.
-__device__ __forceinline__ void depth_take_block(const Level* lv, long long base, int b, unsigned long long gate,
-                                                 bool bid, DepthLvl* view, uint32_t want, uint32_t& found, int& best) {
-  const int lane = (int)(threadIdx.x & 63u);
-  const int l = b * 64 + lane;
-  long long t = 0;
-  if ((gate >> lane) & 1ull) t = lv[l].total;
+// One block of a side's levels, lane order = priority order: this lane's price and total (<= 0: none). The
+// occupied ones go to view[found ..]. True when the view is full.
+__device__ __forceinline__ bool depth_take(DepthLvl* view, uint32_t want, uint32_t& found, long long px, long long t) {
   const unsigned long long m = __ballot(t > 0);
-  if (!m) return;
-  const unsigned long long ahead = bid ? (lane == 63 ? 0ull : m >> (lane + 1)) : m & ((1ull << lane) - 1ull);
-  const uint32_t at = found + (uint32_t)__popcll(ahead);
-  if (t > 0 && at < want && view) {
+  const uint32_t at = found + (uint32_t)__popcll(m & lanemask_lt());
+  if (t > 0 && at < want) {
     DepthLvl x;
-    x.price = base + l;
+    x.price = px;
     x.qty = t;
     view[at] = x;
   }
-  if (found == 0u) best = bid ? b * 64 + 63 - __builtin_clzll(m) : b * 64 + __builtin_ctzll(m);
   found = min(want, found + (uint32_t)__popcll(m));
-}
-
-// The window part of a view: from level `start` (inside the window) outward until `want` levels are
-// found or the window's edge is reached.
-__device__ __forceinline__ void depth_window(const BookDev& bk, uint32_t s, long long base, bool bid, int start,
-                                             DepthLvl* view, uint32_t want, uint32_t& found, int& best) {
-  const int lane = (int)(threadIdx.x & 63u);
-  const int W = (int)bk.Lwords;
-  const Level* lv = bk.levels + (size_t)s * bk.L;
-  const int sb = start & 63;
-  unsigned long long first = bid ? (sb == 63 ? ~0ull : (1ull << (sb + 1)) - 1ull) : ~0ull << sb;
-  int w0 = start >> 6;
-  if (bk.L <= 128u) {
-    for (int b = w0; (bid ? b >= 0 : b < W) && found < want; b += bid ? -1 : 1) {
-      depth_take_block(lv, base, b, first, bid, view, want, found, best);
-      first = ~0ull;
-    }
-    return;
-  }
-  const unsigned long long* oc = bk.occ + (size_t)s * bk.Lwords;
-  while (bid ? w0 >= 0 : w0 < W) {
-    const int wi = bid ? w0 - lane : w0 + lane;
-    unsigned long long word = wi >= 0 && wi < W ? oc[wi] : 0ull;
-    if (lane == 0) word &= first;
-    first = ~0ull;
-    unsigned long long nz = __ballot(word != 0ull);
-    while (nz && found < want) {
-      const int j = __builtin_ctzll(nz);
-      nz &= nz - 1ull;
-      const unsigned long long g = (unsigned long long)__shfl((long long)word, j, 64);
-      depth_take_block(lv, base, bid ? w0 - j : w0 + j, g, bid, view, want, found, best);
-    }
-    if (found >= want) break;
-    w0 += bid ? -64 : 64;
-  }
+  return found >= want;
 }
 
 __global__ __launch_bounds__(DEPTH_WAVES * 64) void k_depth_scan(BookDev bk, DepthDev d) {
@@ -477,46 +404,29 @@ __global__ __launch_bounds__(DEPTH_WAVES * 64) void k_depth_scan(BookDev bk, Dep
   // the published view and the far region's place do not depend on the walk: their loads go out ahead of it
   DepthLvl pubv{};
   if (lane < np) pubv = d.pub[(size_t)sidx * D + lane];
-  FarDir fd{};
-  if (nfar_hint) fd = bk.fdir[(size_t)s * 2u + (bid ? 0u : 1u)];
+  FarSide fs{};
+  if (nfar_hint) far_side(bk, s, bid ? 0u : 1u, nfar_hint, fs);  // (a region outside the arena: no far levels, no error word)
   // ---- gather the view
   uint32_t n = 0;
   if (win) {
-    int best = -1;
-    if (bid) {
-      depth_window(bk, s, st.base, true, min(st.best_bid, L - 1), nv, D, n, best);
-    } else {
+    const Level* lv = bk.levels + (size_t)s * L;
+    const int bb = min(st.best_bid, L - 1);
+    int from = bb, to = 0;
+    if (!bid) {  // the best bid found (a walk wanting one level): the ask walk starts above it
       int lb = -1;
-      if (st.best_bid >= 0) {  // the best bid found: the ask walk starts above it
-        uint32_t one = 0;
-        depth_window(bk, s, st.base, true, min(st.best_bid, L - 1), nullptr, 1u, one, lb);
-      }
-      const int la = max(max(st.best_ask, 0), lb + 1);
-      if (la < L) depth_window(bk, s, st.base, false, la, nv, D, n, best);
+      walk_window(bk, s, true, bb, 0, [&](int l, bool gate) {
+        const unsigned long long m = __ballot(gate && lv[l].total > 0);
+        if (m) lb = rli32(l, __builtin_ctzll(m));
+        return m != 0ull;
+      });
+      from = max(max(st.best_ask, 0), lb + 1);
+      to = L - 1;
     }
+    walk_window(bk, s, bid, from, to,
+                [&](int l, bool gate) { return depth_take(nv, D, n, st.base + l, gate ? lv[l].total : 0); });
   }
-  if (n < D && nfar_hint) {  // complete it from the far region: entries from the end, occupied ones only
-    const FarLevel* far = bk.far + fd.off;
-    const uint32_t nfar = min(nfar_hint, fd.cap);
-    for (uint32_t k = 0; k < nfar && n < D; k += 64u) {
-      const uint32_t i = k + lane;
-      long long t = 0, px = 0;
-      if (i < nfar) {
-        const FarLevel f = far[nfar - 1u - i];
-        t = f.total;
-        px = f.price;
-      }
-      const unsigned long long m = __ballot(t > 0);
-      const uint32_t at = n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      if (t > 0 && at < D) {
-        DepthLvl x;
-        x.price = px;
-        x.qty = t;
-        nv[at] = x;
-      }
-      n = min(D, n + (uint32_t)__popcll(m));
-    }
-  }
+  // complete it from the far levels, occupied ones only
+  if (n < D) walk_far(fs, fs.n, [&](const FarLevel& f) { return depth_take(nv, D, n, f.price, f.total); });
   if (lane < np) pv[lane] = pubv;
   depth_wave_order();
   // ---- diff: lanes 0..31 own the new entries, lanes 32..63 the published ones
@@ -674,10 +584,6 @@ hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d) {
 // k_trade_emit: k_quote_emit's shape — prefix the popcounts, feed_fits, and only if the job fits write the
 // events in symbol order and empty the pending summaries (never the cumulative pair); every writer fences
 // at system scope, and after the barrier thread 0 runs feed_publish.
-__device__ __forceinline__ unsigned long long trade_wave_add(unsigned long long x) {
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
 __device__ __forceinline__ unsigned long long trade_wave_min(unsigned long long x) {
   for (int d = 32; d >= 1; d >>= 1) x = min(x, (unsigned long long)__shfl_xor(x, d, 64));
   return x;
@@ -762,7 +668,7 @@ __global__ __launch_bounds__(TF_T) void k_trade_fold(TradeDev t, TradeLaunch tl,
         h = max(h, p);
         l = min(l, p);
       }
-      v = trade_wave_add(v);
+      v = (unsigned long long)wave_sum((long long)v);
       h = trade_wave_max(h);
       l = trade_wave_min(l);
       if ((int)lane == j) {
@@ -783,8 +689,8 @@ __global__ __launch_bounds__(TF_T) void k_trade_fold(TradeDev t, TradeLaunch tl,
     if ((t.wave_reduce & TF_WAVE) && (am & (am - 1ull))) {
       const uint32_t s0 = (uint32_t)__shfl((int)s, lead, 64);
       if (!__ballot(active && s != s0)) {
-        vol = trade_wave_add(vol);  // (inactive lanes hold the identities)
-        cnt = trade_wave_add(cnt);
+        vol = (unsigned long long)wave_sum((long long)vol);  // (inactive lanes hold the identities)
+        cnt = (unsigned long long)wave_sum((long long)cnt);
         hi = trade_wave_max(hi);
         lo = trade_wave_min(lo);
         kf = trade_wave_min(kf);
@@ -959,51 +865,11 @@ hipError_t launch_trades(hipStream_t st, const BookDev& bk, const TradeDev& t, c
 //      located by far_rank. The walk must have ended at that level's head;
 //   4. adds up the better levels of the side: the occupied window levels between the side's best hint and
 //      the order's level (all of the side's window levels for a far order: a window level always beats a far
-//      level) and, for a far order, the occupied far entries behind its own (the best is last).
+//      level) and, for a far order, the occupied far entries behind its own (the best is last): walk_window
+//      over a bounded range and walk_far (me_bookread.hpp), as per-lane partial sums.
 // Whatever does not fit (an id out of range, the step bound, a level that is not there, a head that is not
 // the walk's end) sets the request's error word and answers found = 0; nothing is read out of bounds.
 constexpr int OQ_WAVES = 4;
-
-__device__ __forceinline__ long long oq_wave_sum(long long x) { return rli64(wave_incl_scan(x), 63); }
-
-// Occupied levels of window levels [lo, hi) and their totals, as per-lane partial sums. L <= 128: every
-// total of the range, 64 per load. Deeper windows: the occ words, 64 per load, and only the totals under set
-// bits; the total decides (k_depth_scan's rule).
-__device__ __forceinline__ void oq_window(const BookDev& bk, uint32_t s, int lo, int hi, long long& qty, long long& cnt) {
-  const int lane = lane_id();
-  const Level* lv = bk.levels + (size_t)s * bk.L;
-  if (lo >= hi) return;
-  if (bk.L <= 128u) {
-    for (int l0 = lo; l0 < hi; l0 += 64) {
-      const int l = l0 + lane;
-      const long long t = l < hi ? lv[l].total : 0;
-      if (t > 0) {
-        qty += t;
-        cnt += 1;
-      }
-    }
-    return;
-  }
-  const unsigned long long* oc = bk.occ + (size_t)s * bk.Lwords;
-  const int wlo = lo >> 6, whi = (hi - 1) >> 6;  // words [wlo, whi]
-  for (int w0 = wlo; w0 <= whi; w0 += 64) {
-    const int wi = w0 + lane;
-    unsigned long long word = wi <= whi ? oc[wi] : 0ull;
-    if (wi == wlo) word &= ~0ull << (lo & 63);
-    if (wi == whi && (hi & 63)) word &= (1ull << (hi & 63)) - 1ull;
-    unsigned long long nz = __ballot(word != 0ull);
-    while (nz) {
-      const int j = __builtin_ctzll(nz);
-      nz &= nz - 1ull;
-      const unsigned long long g = rl64(word, j);
-      const long long t = (g >> lane) & 1ull ? lv[(w0 + j) * 64 + lane].total : 0;
-      if (t > 0) {
-        qty += t;
-        cnt += 1;
-      }
-    }
-  }
-}
 
 __global__ __launch_bounds__(OQ_WAVES * 64) void k_order_query(BookDev bk, OrderQueryReq rq) {
   const int lane = lane_id();
@@ -1066,66 +932,56 @@ __global__ __launch_bounds__(OQ_WAVES * 64) void k_order_query(BookDev bk, Order
       const int L = (int)bk.L;
       const int bb = min(rli32(st.best_bid, 0), L - 1), ba = max(rli32(st.best_ask, 0), 0);
       const unsigned long long off = (unsigned long long)price - (unsigned long long)base;
-      long long b_qty = 0, b_cnt = 0;
+      long long b_qty = 0, b_cnt = 0;  // per-lane partial sums
+      const auto better = [&](long long t) {
+        b_qty += t > 0 ? t : 0;
+        b_cnt += t > 0;
+        return false;
+      };
+      const Level* lv = bk.levels + (size_t)s * L;
+      const auto window = [&](int lo, int hi) {  // (in no particular order: as asks)
+        walk_window(bk, s, false, lo, hi, [&](int l, bool gate) { return better(gate ? lv[l].total : 0); });
+      };
       long long level_qty = 0;
       uint32_t head = NIL;
       bool bid = false;
       if (off < (unsigned long long)L) {
         const int lvl = (int)off;
-        const Level x = bk.levels[(size_t)s * L + lvl];
+        const Level x = lv[lvl];
         level_qty = rli64(x.total, 0);
         head = rl32(x.head, 0);
         bid = lvl <= bb;
         if (bid == (lvl >= ba)) bad = true;  // between the hints (or both): no level of either side
         // ---- 4. better: strictly between the side's best hint and the order's level
-        if (!bad) {
-          if (bid)
-            oq_window(bk, s, lvl + 1, bb + 1, b_qty, b_cnt);
-          else
-            oq_window(bk, s, ba, lvl, b_qty, b_cnt);
-        }
+        if (!bad) window(bid ? lvl + 1 : ba, bid ? bb : lvl - 1);
       } else {
         bid = price < base;
         const uint32_t k = bid ? 0u : 1u;
-        const FarDir fd = bk.fdir[(size_t)s * 2u + k];
-        const uint32_t nfar = min(rl32(bid ? st.nfar[0] : st.nfar[1], 0), rl32(fd.cap, 0));
-        const unsigned long long foff = rl64(fd.off, 0);
-        const unsigned long long fend = 2ull * bk.S * bk.fcap + 2ull * bk.far_half;  // entries of the arena
-        const gptr<FarLevel> far = (gptr<FarLevel>)(bk.far + foff);
-        const bool region = nfar != 0u && foff <= fend && nfar <= fend - foff;
-        const uint32_t pos = region ? far_rank(far, nfar, price, k) : nfar;
-        if (pos >= nfar) {
+        FarSide fs;
+        far_side(bk, s, k, bid ? st.nfar[0] : st.nfar[1], fs);  // (a bad region is an empty one: the level is not there)
+        const uint32_t pos = fs.n ? far_rank(fs.lv, fs.n, price, k) : 0u;
+        if (pos >= fs.n) {
           bad = true;
         } else {
-          const FarLevel e = far_get(far, pos);
+          const FarLevel e = far_get(fs.lv, pos);
           level_qty = e.total;
           head = e.head;
           bad = e.price != price;
         }
-        if (!bad) {
-          if (bid)
-            oq_window(bk, s, 0, bb + 1, b_qty, b_cnt);
-          else
-            oq_window(bk, s, ba, L, b_qty, b_cnt);
-          for (uint32_t i0 = pos + 1u; i0 < nfar; i0 += 64u) {
-            const uint32_t i = i0 + (uint32_t)lane;
-            const long long t = i < nfar ? far[i].total : 0;
-            if (t > 0) {
-              b_qty += t;
-              b_cnt += 1;
-            }
-          }
+        if (!bad) {  // every window level of the side, and the far entries behind the order's
+          window(bid ? 0 : ba, bid ? bb : L - 1);
+          walk_far(fs, fs.n - 1u - pos, [&](const FarLevel& e) { return better(e.total); });
         }
       }
       bad = bad || head != cur;  // the walk ended at another chunk than the level's first
       if (!bad) {
         o.price_q4 = price;
-        o.qty_ahead = oq_wave_sum(a_qty);
+        o.qty_ahead = wave_sum(a_qty);
         o.level_qty = level_qty;
-        o.qty_better = oq_wave_sum(b_qty);
+        o.qty_better = wave_sum(b_qty);
         o.qty = q;
-        o.orders_ahead = (uint32_t)oq_wave_sum(a_cnt);
-        o.levels_better = (uint32_t)oq_wave_sum(b_cnt);
+        o.orders_ahead = (uint32_t)wave_sum(a_cnt);
+        o.levels_better = (uint32_t)wave_sum(b_cnt);
         o.symbol = bk.gsym ? bk.gsym[s] : s;
         o.side = bid ? ME_SIDE_BUY : ME_SIDE_SELL;
         o.found = 1;
@@ -1147,14 +1003,10 @@ hipError_t launch_order_query(hipStream_t st, const BookDev& bk, const OrderQuer
 // ---- order preview (me_order_preview, include/me_engine.h) -------------------------------------------
 // k_order_preview: one wave per hypothetical NEW record, four per workgroup, read-only, no LDS. After the
 // matcher's rejects (BAD_SYMBOL, BAD_QTY, BAD_SIDE, BAD_TIF, in that order) the wave walks the side the record
-// would trade against, best level first, in BLOCKS of up to 64 levels, lane order = priority order:
-//   window  outward from the side's best hint (asks ascend, bids descend) through gate words, 64 words a
-//           load: a deep window's occupancy words, so that only the totals under set bits are loaded; for
-//           L <= 128 all-ones words, so that every level of the block is loaded (oq_window's two modes);
-//   far     once the window is exhausted, the side's far entries from the end (best last), 64 a block; the
-//           region is checked against the arena first, as k_order_query does.
-// pv_block does the rest. A level counts when its total is > 0 (the total decides, a set bit over a total
-// <= 0 and a dead far entry are stepped over). The first such level is the opposite best. The limit clips by
+// would trade against, best level first, in blocks of up to 64 levels, lane order = priority order: the window
+// outward from the side's best hint, then the far levels (walk_window, walk_far: me_bookread.hpp; a far region
+// outside the arena sets the error word). pv_block does the rest. A level counts when its total is > 0 (the
+// total decides). The first such level is the opposite best. The limit clips by
 // price: every lane compares its level's own price with the limit, a signed int64 compare — no price
 // difference is ever formed, so any int64 limit and any window base are exact — and the first counted level
 // beyond the limit ends the walk (prices only get worse behind it; by Invariant I that also keeps a limit
@@ -1235,9 +1087,9 @@ __device__ __forceinline__ bool pv_block(const BookDev& bk, PvWalk& w, long long
     // three 64-bit columns (the low half as two 32-bit columns: 64 of them cannot carry out of 64 bits)
     const unsigned long long plo = (unsigned long long)price * (unsigned long long)take;
     const long long phi = __mul64hi(price, take);
-    const unsigned long long c0 = (unsigned long long)oq_wave_sum((long long)(plo & 0xFFFFFFFFull));
-    const unsigned long long c1 = (unsigned long long)oq_wave_sum((long long)(plo >> 32));
-    const unsigned long long chi = (unsigned long long)oq_wave_sum(phi);
+    const unsigned long long c0 = (unsigned long long)wave_sum((long long)(plo & 0xFFFFFFFFull));
+    const unsigned long long c1 = (unsigned long long)wave_sum((long long)(plo >> 32));
+    const unsigned long long chi = (unsigned long long)wave_sum(phi);
     const unsigned long long lo = c0 + (c1 << 32);
     const unsigned long long hi = chi + (c1 >> 32) + (lo < c0 ? 1ull : 0ull);
     const unsigned long long nlo = w.nlo + lo;
@@ -1257,54 +1109,22 @@ __device__ __forceinline__ bool pv_block(const BookDev& bk, PvWalk& w, long long
 
 // The whole walk of symbol s's side opposite to the record: window, then far levels.
 __device__ __forceinline__ void pv_walk(const BookDev& bk, uint32_t s, PvWalk& w) {
-  const int lane = lane_id();
   const SymState st = bk.sym[s];
-  const long long base = rli64(st.base, 0);
-  const int L = (int)bk.L, W = (int)bk.Lwords;
+  const int L = (int)bk.L;
   const bool bid = !w.buy;  // a SELL walks the bids
-  const int start = bid ? min(rli32(st.best_bid, 0), L - 1) : max(rli32(st.best_ask, 0), 0);
-  if (bid ? start >= 0 : start < L) {
-    const Level* lv = bk.levels + (size_t)s * L;
-    const unsigned long long* oc = bk.occ + (size_t)s * bk.Lwords;
-    const bool deep = bk.L > 128u;
-    const int sb = start & 63;
-    unsigned long long first = bid ? (sb == 63 ? ~0ull : (1ull << (sb + 1)) - 1ull) : ~0ull << sb;
-    for (int w0 = start >> 6; bid ? w0 >= 0 : w0 < W; w0 += bid ? -64 : 64) {
-      const int wi = bid ? w0 - lane : w0 + lane;
-      unsigned long long word = wi >= 0 && wi < W ? (deep ? oc[wi] : ~0ull) : 0ull;
-      if (lane == 0) word &= first;
-      first = ~0ull;
-      for (unsigned long long nz = __ballot(word != 0ull); nz; nz &= nz - 1ull) {
-        const int j = __builtin_ctzll(nz);
-        const unsigned long long g = rl64(word, j);
-        const int bit = bid ? 63 - lane : lane;  // a word's bids go from its top bit down
-        const int l = (bid ? w0 - j : w0 + j) * 64 + bit;
-        Level x;
-        x.total = 0;
-        x.head = x.tail = NIL;
-        if (((g >> bit) & 1ull) && l < L) x = lv[l];
-        if (pv_block(bk, w, base + l, x.total, x.head, x.tail)) return;
-      }
-    }
-  }
-  const uint32_t k = bid ? 0u : 1u;
-  const uint32_t nhint = rl32(bid ? st.nfar[0] : st.nfar[1], 0);
-  if (!nhint) return;
-  const FarDir fd = bk.fdir[(size_t)s * 2u + k];
-  const uint32_t nfar = min(nhint, rl32(fd.cap, 0));
-  const unsigned long long foff = rl64(fd.off, 0);
-  const unsigned long long fend = 2ull * bk.S * bk.fcap + 2ull * bk.far_half;  // entries of the arena
-  if (foff > fend || nfar > fend - foff) {
-    w.bad = true;
-    return;
-  }
-  const gptr<FarLevel> far = (gptr<FarLevel>)(bk.far + foff);  // (global_* loads, as k_order_query's)
-  for (uint32_t i0 = 0; i0 < nfar; i0 += 64u) {
-    const uint32_t i = i0 + (uint32_t)lane;
-    FarLevel f{};
-    if (i < nfar) f = far[nfar - 1u - i];
-    if (pv_block(bk, w, f.price, f.total, f.head, f.tail)) return;
-  }
+  const Level* lv = bk.levels + (size_t)s * L;
+  const bool done = walk_window(bk, s, bid, bid ? min(st.best_bid, L - 1) : max(st.best_ask, 0), bid ? 0 : L - 1,
+                                [&](int l, bool gate) {
+                                  Level x;
+                                  x.total = 0;
+                                  x.head = x.tail = NIL;
+                                  if (gate) x = lv[l];
+                                  return pv_block(bk, w, st.base + l, x.total, x.head, x.tail);
+                                });
+  if (done) return;
+  FarSide fs;
+  if (!far_side(bk, s, bid ? 0u : 1u, bid ? st.nfar[0] : st.nfar[1], fs)) w.bad = true;
+  walk_far(fs, fs.n, [&](const FarLevel& f) { return pv_block(bk, w, f.price, f.total, f.head, f.tail); });
 }
 
 __global__ __launch_bounds__(PV_WAVES * 64) void k_order_preview(BookDev bk, PreviewReq rq) {
@@ -1397,7 +1217,10 @@ hipError_t launch_order_preview(hipStream_t st, const BookDev& bk, const Preview
 // from the totals (a window has up to 2^20 levels): every thread takes one word of the side's range, going
 // outward from the best level; a block scan of the popcounts places the words' levels in the pass, and the
 // words that still fit it — a prefix, whole words only — are taken; the cursor stops at the first that does
-// not. Windows of L <= 128 form their (at most two) words from the totals, as the scans do. Far levels
+// not. Windows of L <= 128 form their (at most two) words from the totals, as the scans do. (The two block
+// gathers stay apart because their units differ: k_book_snapshot compacts level totals, 1,024 levels a round,
+// and stops inside a round at `depth`; this one places whole occupancy words, 65,536 levels a round. What
+// follows a gather is shared: far_nth, chain_live, chunk_entries, me_bookread.hpp.) Far levels
 // follow once the window is exhausted, best (last) first. Every thread then walks the chains of two levels
 // of the pass to count their live slots, and a block scan turns the counts into output offsets.
 //   REMOVE = false writes the side's count and nothing else. REMOVE = true walks each chain a second time:
@@ -1448,17 +1271,14 @@ __global__ __launch_bounds__(SNAP_T) void k_purge(BookDev bk, PurgeReq rq) {
   const SymState st = bk.sym[s];
   Level* lv = bk.levels + (size_t)s * L;
   unsigned long long* oc = bk.occ + (size_t)s * bk.Lwords;
-  const FarDir fd = bk.fdir[(size_t)s * 2u + side];
-  const uint32_t nfar = min(st.nfar[side], fd.cap);
-  const unsigned long long fend = 2ull * bk.S * bk.fcap + 2ull * bk.far_half;  // entries of the arena
-  if (nfar && (fd.off > fend || nfar > fend - fd.off)) {
+  FarSide fs;
+  if (!far_side(bk, s, side, st.nfar[side], fs)) {
     if (tid == 0) {
       atomicOr(rq.err, 1u);
       if (!REMOVE) rq.cnt[reg] = 0ull;
     }
     return;
   }
-  const FarLevel* far = bk.far + fd.off;
   // the side's window levels [lo, hi] (none: lo > hi), words [wlo, whi]
   const int lo = bid ? 0 : max(st.best_ask, 0);
   const int hi = bid ? min(st.best_bid, L - 1) : L - 1;
@@ -1482,11 +1302,7 @@ __global__ __launch_bounds__(SNAP_T) void k_purge(BookDev bk, PurgeReq rq) {
       if (tid == 0) s_first = SNAP_T;
       const int wi = bid ? cur - tid : cur + tid;
       unsigned long long word = 0;
-      if (wi >= wlo && wi <= whi) {
-        word = purge_occ_word(bk, lv, oc, wi);
-        if (wi == wlo) word &= ~0ull << (lo & 63);
-        if (wi == whi && (hi & 63) != 63) word &= (2ull << (hi & 63)) - 1ull;
-      }
+      if (wi >= wlo && wi <= whi) word = purge_occ_word(bk, lv, oc, wi) & word_range(wi, lo, hi);
       const uint32_t pc = (uint32_t)__popcll(word);
       uint32_t all = 0;
       const uint32_t pos = snap_block_excl_scan(pc, wsum, all);
@@ -1519,9 +1335,9 @@ __global__ __launch_bounds__(SNAP_T) void k_purge(BookDev bk, PurgeReq rq) {
     // ---- far levels, once the window is exhausted
     const bool win_done = bid ? s_cur < wlo : s_cur > whi;
     const uint32_t fr = s_far;
-    const uint32_t nf = win_done ? min((uint32_t)PURGE_P - nw, nfar - fr) : 0u;
+    const uint32_t nf = win_done ? min((uint32_t)PURGE_P - nw, fs.n - fr) : 0u;
     for (uint32_t j = tid; j < nf; j += SNAP_T) {
-      const FarLevel f = far[nfar - 1u - (fr + j)];
+      const FarLevel f = far_nth(fs, fr + j);
       p_lvl[nw + j] = -1;
       p_price[nw + j] = f.price;
       p_head[nw + j] = f.total > 0 ? f.head : NIL;
@@ -1538,24 +1354,10 @@ __global__ __launch_bounds__(SNAP_T) void k_purge(BookDev bk, PurgeReq rq) {
     for (int k = 0; k < PURGE_P / SNAP_T; ++k) {
       const uint32_t i = (uint32_t)tid * (PURGE_P / SNAP_T) + k;
       uint32_t c = 0;
-      if (i < np && p_head[i] != NIL) {
-        uint32_t ch = p_head[i], guard = 0;
-        for (;;) {
-          if (ch >= bk.nchunks || ++guard > bk.nchunks) {  // (NIL too: the chain ended before its tail)
-            atomicOr(rq.err, 1u);
-            p_head[i] = NIL;  // (this thread's own entry)
-            c = 0;
-            break;
-          }
-          const int4* qv = reinterpret_cast<const int4*>(bk.chunks[ch].qty);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int4 v = qv[u];
-            c += (v.x > 0) + (v.y > 0) + (v.z > 0) + (v.w > 0);
-          }
-          if (ch == p_tail[i]) break;
-          ch = bk.chunks[ch].hdr.next;
-        }
+      if (i < np && !chain_live(bk, p_head[i], p_tail[i], c)) {  // a broken chain is left alone
+        atomicOr(rq.err, 1u);
+        p_head[i] = NIL;  // (this thread's own entry)
+        c = 0;
       }
       cnt[k] = c;
       mine += c;
@@ -1573,21 +1375,7 @@ __global__ __launch_bounds__(SNAP_T) void k_purge(BookDev bk, PurgeReq rq) {
           for (;;) {  // (the count walk went head -> tail inside [0, nchunks))
             Chunk& c = bk.chunks[ch];
             const uint32_t nxt = c.hdr.next;
-            for (int u = 0; u < ME_C; ++u) {
-              const int qq = c.qty[u];
-              if (qq > 0) {
-                if (o < rq.cap) {
-                  me_book_entry e;
-                  e.seq = c.seq[u];
-                  e.price_q4 = p_price[i];
-                  e.qty = qq;
-                  e.side = bid ? ME_SIDE_BUY : ME_SIDE_SELL;
-                  e.pad[0] = e.pad[1] = e.pad[2] = 0;
-                  rq.out[o] = e;
-                }
-                ++o;
-              }
-            }
+            o = chunk_entries(c, p_price[i], bid, rq.out, o, rq.cap);
             int4* qv = reinterpret_cast<int4*>(c.qty);
 #pragma unroll
             for (int u = 0; u < 4; ++u) qv[u] = make_int4(0, 0, 0, 0);

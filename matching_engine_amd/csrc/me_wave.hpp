@@ -47,6 +47,8 @@ __device__ __forceinline__ long long wave_incl_scan(long long x) {
   x += dpp64<0x143, 0xC>(x);  // row_bcast:31 into rows 2, 3
   return x;
 }
+// The sum over the wave's 64 lanes (wave-uniform; wraps like the type).
+__device__ __forceinline__ long long wave_sum(long long x) { return rli64(wave_incl_scan(x), 63); }
 // Inclusive scan of a 16-lane row (each DPP row scans on its own), saturating at 2^32 - 1. The row
 // shifts use bound_ctrl (a lane with no source reads 0), so no "old" value is materialised.
 template <int kCtrl>
