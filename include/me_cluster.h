@@ -23,9 +23,17 @@
  *   QUOTES   the top-of-book change feed (me_quotes_*, me_engine.h): every rank drains its shard's events
  *            and sends them to rank 0, which concatenates them in rank order (QUOTES_ENABLE turns every
  *            shard's feed on or off).
- *            (The depth feed, me_depth_* in me_engine.h, has no collective yet: rank 0 fronting the shards'
- *            depth feeds, and a me_cluster_matcher hook for me_service_depth_subscribe, is a later change; a
- *            service over me_cluster_matcher answers ME_E_INVALID to me_service_depth_subscribe.)
+ *   DEPTH / DEPTH_ENABLE, TRADES / TRADES_ENABLE
+ *            the depth feed (me_depth_*) and the trade feed (me_trades_*) carried the same way: one drain-and-
+ *            gather routine serves the three feeds.
+ *   ORDER_QUERY   me_order_query over the cluster: a seq names no symbol, so rank 0 broadcasts the seqs, every
+ *            shard answers all of them and rank 0 keeps, per seq, the one answer with found = 1.
+ *   ORDER_PREVIEW me_order_preview over the cluster: the queries are split by owner as a slice is, scattered,
+ *            previewed on their shards, gathered and put back into query order. Nothing changes on any shard.
+ *            (The mass cancel, me_mass_cancel, stays engine-only: it changes the books and is all-or-nothing
+ *            on a capacity summed over the shards, which needs a count / vote / remove protocol of its own.)
+ *            A cluster that enables no feed and makes neither call issues exactly the commands it issued
+ *            without them.
  *   STOP     the serve loops return.
  * The service keeps two slices in flight through the matcher's submit / collect (SUBMIT of slice k+1
  * runs before COLLECT of slice k), so the shards match k+1 while rank 0 merges and persists k.
@@ -84,6 +92,17 @@ typedef struct me_shard_ops {
   /* optional (NULL: no feed): me_quotes_read's contract over its local symbols (local ids; `batches` = the
    * parts it has matched) */
   int (*quotes)(void* ctx, me_quote* out, size_t cap, size_t* n, size_t* left);
+  /* All optional, local symbol ids; a NULL hook on any shard makes the collective that needs it return
+   * ME_E_INVALID on every rank (not sticky: the next slice matches as before).
+   * depth_enable / depth: me_depth_enable's / me_depth_read's contract; trades_enable / trades: me_trades_enable's
+   * / me_trades_read's (`batches` = the parts it has matched, as in `quotes`). */
+  int (*depth_enable)(void* ctx, uint32_t depth, uint64_t cap_events);
+  int (*depth)(void* ctx, me_depth_event* out, size_t cap, size_t* n, size_t* left);
+  int (*trades_enable)(void* ctx, uint64_t cap_events);
+  int (*trades)(void* ctx, me_trade* out, size_t cap, size_t* n, size_t* left);
+  /* me_order_query's contract (`symbol` a local id) and me_order_preview's (q->symbol local ids, q->seq NULL) */
+  int (*order_query)(void* ctx, const uint64_t* seqs, size_t n, me_order_info* out);
+  int (*order_preview)(void* ctx, const me_order_soa* q, size_t n, me_preview* out);
 } me_shard_ops;
 
 typedef struct me_cluster me_cluster;
@@ -133,8 +152,31 @@ int me_cluster_quotes_enable(me_cluster* c, uint64_t cap_events);
  * a cluster-wide number. Through me_cluster_matcher's `quotes` the same events are stamped with the slice's
  * number instead (slices the cluster has matched, from 1), as the service requires. */
 int me_cluster_quotes(me_cluster* c, me_quote* out, size_t cap, size_t* n, size_t* left);
+/* Rank 0: me_depth_enable / me_depth_read and me_trades_enable / me_trades_read over the whole cluster, with
+ * me_cluster_quotes_enable's / me_cluster_quotes' contract: enabling (depth 0 or cap_events 0: off) reaches
+ * every shard, starts the feed afresh and drops what rank 0 had gathered; depth > ME_DEPTH_MAX is ME_E_INVALID
+ * from every shard and the cluster stays usable. A read, once everything gathered before has been handed out,
+ * has every rank drain its shard until nothing is left and rank 0 append the events in rank order (each
+ * shard's own order kept); symbols are global ids, `batches` the shard's own count (through
+ * me_cluster_matcher's hooks: the slice's number). *n and *left are written on every return. */
+int me_cluster_depth_enable(me_cluster* c, uint32_t depth, uint64_t cap_events);
+int me_cluster_depth(me_cluster* c, me_depth_event* out, size_t cap, size_t* n, size_t* left);
+int me_cluster_trades_enable(me_cluster* c, uint64_t cap_events);
+int me_cluster_trades(me_cluster* c, me_trade* out, size_t cap, size_t* n, size_t* left);
+/* Rank 0: me_order_query over the cluster (its n > 2^24 / NULL rules, checked before any command is issued;
+ * n == 0: ME_OK, no command). out[i] is the answer of the one shard that holds seqs[i] (symbol: a global id);
+ * found = 0 with seq echoed and every other field zero when none does; two shards holding it is ME_E_STATE.
+ * More than max_batch seqs are handled in chunks of max_batch. The books are those after every slice
+ * SUBMITTED so far; outstanding tickets stay collectable with their outputs unchanged. */
+int me_cluster_order_query(me_cluster* c, const uint64_t* seqs, size_t n, me_order_info* out);
+/* Rank 0: me_order_preview over the cluster (global symbol ids; q->seq ignored). A kind with bit 3 set is
+ * ME_E_INVALID before any command is issued; a symbol >= num_symbols is answered by rank 0 with the BAD_SYMBOL
+ * row of a single engine. Chunked like the order query; the same books; nothing changes on any shard: the call
+ * takes no seq, is no batch and produces no feed event. */
+int me_cluster_order_preview(me_cluster* c, const me_order_soa* q, size_t n, me_preview* out);
 /* Rank 0: the me_matcher over this cluster for me_service_create_matcher (submit / collect set: the
- * service keeps two slices in flight). max_resting = the sum over the shards. */
+ * service keeps two slices in flight; quotes, the depth and trade feeds with slice-number stamps, order query and
+ * order preview set). max_resting = the sum over the shards. */
 int me_cluster_matcher(me_cluster* c, me_matcher* out);
 
 /* Counters: slices matched, bytes moved by the transport (this rank, both directions). */

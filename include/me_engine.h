@@ -383,8 +383,8 @@ typedef struct me_preview { /* 64 B */
  * REDUCE; checked on the host before anything is copied): ME_E_INVALID, nothing launched, nothing answered.
  * The argument checks come first: a failed engine given a bad argument or a CANCEL kind answers ME_E_INVALID;
  * given valid arguments it answers what me_sync answers. A FIFO chain that cannot be walked: ME_E_STATE "corrupt
- * FIFO chain", as the snapshot calls. Like the order query and the mass cancel, the call exists on an engine only:
- * not on a cluster, not behind a me_matcher. */
+ * FIFO chain", as the snapshot calls. Over a cluster: me_cluster_order_preview (me_cluster.h), and the
+ * me_matcher's order_preview hook. */
 int me_order_preview(me_engine* e, const me_order_soa* q, size_t n, me_preview* out);
 
 /* ---- mass cancel: empty the named sides of the named symbols' books (no reference counterpart) -------
@@ -413,7 +413,8 @@ int me_order_preview(me_engine* e, const me_order_soa* q, size_t n, me_preview* 
  * Feeds: with the quote and / or depth feed on, their jobs run once behind the remove launch (quote, then
  * depth), exactly as behind a match launch; a purged side comes out as a quote with its flag clear and as
  * DELETEs of its published view. The trade feed logs nothing: there are no fills.
- * Like the order query, the call exists on an engine only: not on a cluster, not behind a me_matcher. */
+ * Unlike the order query and the preview, the call exists on an engine only: not on a cluster, not behind a
+ * me_matcher (it changes the books and is all-or-nothing on a capacity that would be summed over the shards). */
 int me_mass_cancel(me_engine* e, const uint32_t* symbols, const uint8_t* sides, size_t n, me_book_entry* out,
                    size_t cap, size_t* n_out, uint64_t* counts /* [n][2] or NULL */);
 

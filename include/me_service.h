@@ -116,9 +116,21 @@ typedef struct me_matcher {
    * must count the slices the matcher has matched (slice k of this service is stamped k, from 1): the service
    * names an event's symbol by it (me_service_market_stream). */
   int (*quotes)(void* ctx, me_quote* out, size_t cap, size_t* n, size_t* left);
+  /* All optional (NULL: the service answers as it does without the facility). depth_enable / depth and
+   * trades_enable / trades: me_depth_enable's / me_depth_read's and me_trades_enable's / me_trades_read's
+   * contracts over the matcher's books, `symbol` and `batches` as in `quotes` (slice numbers). order_query /
+   * order_preview: me_order_query's / me_order_preview's contracts in the id space of `match`. */
+  int (*depth_enable)(void* ctx, uint32_t depth, uint64_t cap_events);
+  int (*depth)(void* ctx, me_depth_event* out, size_t cap, size_t* n, size_t* left);
+  int (*trades_enable)(void* ctx, uint64_t cap_events);
+  int (*trades)(void* ctx, me_trade* out, size_t cap, size_t* n, size_t* left);
+  int (*order_query)(void* ctx, const uint64_t* seqs, size_t n, me_order_info* out);
+  int (*order_preview)(void* ctx, const me_order_soa* q, size_t n, me_preview* out);
 } me_matcher;
 
-/* The service over a matcher instead of an engine (same contract otherwise). NULL on a bad matcher. */
+/* The service over a matcher instead of an engine (same contract otherwise). NULL on a bad matcher. The
+ * matcher must outlive the service: me_service_destroy (like an unsubscribe) turns the depth and trade feeds
+ * it enabled off through depth_enable / trades_enable. */
 me_service* me_service_create_matcher(const me_matcher* m, const char* const* symbols, uint32_t num_symbols,
                                       const char* db_path);
 
@@ -241,8 +253,8 @@ int me_service_reduce_order(me_service* s, const me_reduce_request* req, me_orde
  *   ME_OS_RESTING      side, quantity (what it still holds), price (Q4) and the position fields exactly as
  *                      me_order_info defines them.
  * out[i] answers order_ids[i] (order_id echoed, truncated to fit). The call matches what was flushed before
- * it (me_order_query's me_sync) but flushes no open slice. A service over a me_matcher has no order query:
- * ME_E_INVALID. n == 0: ME_OK. */
+ * it (me_order_query's me_sync) but flushes no open slice. A service over a me_matcher asks its `order_query`
+ * hook; a matcher without one has no order query: ME_E_INVALID. n == 0: ME_OK. */
 enum { ME_OS_NOT_RESTING = 0, ME_OS_PENDING = 1, ME_OS_RESTING = 2 };
 typedef struct me_order_status { /* 88 B */
   char order_id[32];
@@ -262,7 +274,8 @@ int me_service_order_status(me_service* s, const char* client_id, const char* co
  * call (me_order_preview's me_sync); like me_service_order_status it flushes no open slice, so orders still
  * pending in a slice are not in the book it sees. A symbol name that has no book is answered as an empty book
  * (a LIMIT rests whole, a MARKET / IOC / FOK fills nothing) without touching the engine. Admission control is
- * not consulted (me_order_preview). A service over a me_matcher has no preview: ME_E_INVALID. */
+ * not consulted (me_order_preview). A service over a me_matcher asks its `order_preview` hook; a matcher
+ * without one has no preview: ME_E_INVALID. */
 int me_service_preview_order(me_service* s, const me_order_request* req, int32_t tif, me_preview* out);
 
 /* Mass cancel (build extension): an operator's action — a halt, a delisting, the end-of-session purge — so
@@ -363,7 +376,8 @@ typedef struct me_depth_book {
 } me_depth_book;
 /* depth in 1..ME_DEPTH_MAX: me_depth_enable on the service's own engine (which must have been fresh when the
  * service was created, as for me_service_market_subscribe) and queue the books as they stand; it waits for a
- * running flush. A service backed by a me_matcher has no depth feed: ME_E_INVALID. depth == 0: the stream
+ * running flush. A service backed by a me_matcher uses its `depth_enable` / `depth` hooks; a matcher without
+ * them has no depth feed: ME_E_INVALID. depth == 0: the stream
  * stops, the views and the queue are dropped. Independent of me_service_market_subscribe. */
 int me_service_depth_subscribe(me_service* s, uint32_t depth);
 /* Hand out the whole current top-D book of up to cap changed symbols, in first-change order (symbol NULL or
@@ -391,7 +405,8 @@ typedef struct me_trade_update {
 } me_trade_update;
 /* on != 0: me_trades_enable on the service's own engine (which must have been fresh when the service was
  * created, as for me_service_market_subscribe); fills matched before are not counted and nothing is queued. It
- * waits for a running flush. A service backed by a me_matcher has no trade feed: ME_E_INVALID. on == 0: the
+ * waits for a running flush. A service backed by a me_matcher uses its `trades_enable` / `trades` hooks; a
+ * matcher without them has no trade feed: ME_E_INVALID. on == 0: the
  * stream stops, queued updates and the totals are dropped. Independent of the market and depth streams. */
 int me_service_trades_subscribe(me_service* s, int on);
 /* Drain up to cap queued updates (symbol NULL or "": every symbol; else only that symbol's, the others stay

@@ -464,6 +464,20 @@ SUBMIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(MeOrderSoa), C.c_size_t, 
 COLLECT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                          C.POINTER(C.c_void_p))
 QUOTES_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t))
+# the depth and trade feeds' readers have QUOTES_FN's shape (events out, cap, n, left)
+DEPTH_ENABLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint64)
+TRADES_ENABLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64)
+ORDER_QUERY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.c_void_p)
+ORDER_PREVIEW_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(MeOrderSoa), C.c_size_t, C.c_void_p)
+# the optional hooks me_matcher and me_shard_ops share after `quotes`, in declaration order
+PARITY_HOOKS = [
+    ("depth_enable", DEPTH_ENABLE_FN),
+    ("depth", QUOTES_FN),
+    ("trades_enable", TRADES_ENABLE_FN),
+    ("trades", QUOTES_FN),
+    ("order_query", ORDER_QUERY_FN),
+    ("order_preview", ORDER_PREVIEW_FN),
+]
 
 
 class MeMatcher(C.Structure):
@@ -477,7 +491,7 @@ class MeMatcher(C.Structure):
         ("submit", SUBMIT_FN),
         ("collect", COLLECT_FN),
         ("quotes", QUOTES_FN),
-    ]
+    ] + PARITY_HOOKS
 
 
 # ---- include/me_cluster.h ---------------------------------------------------------------------
@@ -511,7 +525,7 @@ class MeShardOps(C.Structure):
         ("book", BOOK_FN),
         ("levels_all", LEVELS_FN),
         ("quotes", QUOTES_FN),
-    ]
+    ] + PARITY_HOOKS
 
 
 PROTOTYPES.update({
@@ -532,6 +546,12 @@ PROTOTYPES.update({
     "me_service_trades_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeTradeUpdate), _SZ, C.POINTER(_SZ)]),
     "me_cluster_quotes_enable": (C.c_int, [_P, C.c_uint64]),
     "me_cluster_quotes": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "me_cluster_depth_enable": (C.c_int, [_P, C.c_uint32, C.c_uint64]),
+    "me_cluster_depth": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "me_cluster_trades_enable": (C.c_int, [_P, C.c_uint64]),
+    "me_cluster_trades": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "me_cluster_order_query": (C.c_int, [_P, _P, _SZ, _P]),
+    "me_cluster_order_preview": (C.c_int, [_P, C.POINTER(MeOrderSoa), _SZ, _P]),
     "me_service_updates": (C.c_int, [_P, C.c_char_p, C.POINTER(MeOrderUpdate), _SZ, C.POINTER(_SZ)]),
     "me_service_create": (_P, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p]),
     "me_service_destroy": (None, [_P]),

@@ -77,6 +77,85 @@ def _quotes_cb(obj):
     return quotes_cb
 
 
+def _events_cb(read, dtype):
+    """me_quotes_read's contract for another event type over read(cap) -> (events, events left unread)."""
+
+    def events_cb(ctx, out, cap, n, left):
+        if n:
+            n[0] = 0
+        if left:
+            left[0] = 0
+        try:
+            ev, rest = read(int(cap))
+            ev = np.ascontiguousarray(ev, dtype=dtype)
+            assert len(ev) <= cap
+            if len(ev):
+                C.memmove(out, ev.ctypes.data, ev.nbytes)
+            if n:
+                n[0] = len(ev)
+            if left:
+                left[0] = int(rest)
+            return 0
+        except ValueError:  # the feed is off
+            return _abi.ME_E_INVALID
+        except Exception:
+            return _abi.ME_E_STATE
+
+    return events_cb
+
+
+def _set_parity_hooks(struct, obj):
+    """The optional hooks me_matcher and me_shard_ops share after `quotes`, each set only when obj has a method
+    of that name (else NULL: the facility is absent, as before): depth_enable(depth, cap_events) and
+    trades_enable(cap_events) (raise ValueError for me's ME_E_INVALID), depth(cap) / trades(cap) -> (events,
+    left), order_query(seqs uint64[n]) -> ORDER_INFO_DTYPE[n], order_preview(symbol, kind, price_q4, qty arrays)
+    -> PREVIEW_DTYPE[n]. Returns the callbacks, which must live as long as the struct."""
+    keep = []
+
+    def guard(fn):
+        def cb(ctx, *a):
+            try:
+                fn(*a)
+                return 0
+            except ValueError:
+                return _abi.ME_E_INVALID
+            except Exception:
+                return _abi.ME_E_STATE
+
+        return cb
+
+    def rows_out(out, rows, dtype, n):
+        rows = np.ascontiguousarray(rows, dtype=dtype)
+        assert len(rows) == n
+        if n:
+            C.memmove(out, rows.ctypes.data, rows.nbytes)
+
+    def query(seqs, n, out):
+        q = np.ctypeslib.as_array(seqs, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+        rows_out(out, obj.order_query(q), _abi.ORDER_INFO_DTYPE, n)
+
+    def preview(soa, n, out):
+        s = soa.contents
+        cols = [np.ctypeslib.as_array(C.cast(getattr(s, f), C.POINTER(t)), shape=(n,)).copy()
+                for f, t in (("symbol", C.c_uint32), ("kind", C.c_uint8), ("price_q4", C.c_int64), ("qty", C.c_int32))]
+        rows_out(out, obj.order_preview(*cols), _abi.PREVIEW_DTYPE, n)
+
+    hooks = {
+        "depth_enable": lambda: _abi.DEPTH_ENABLE_FN(guard(lambda d, cap: obj.depth_enable(int(d), int(cap)))),
+        "depth": lambda: _abi.QUOTES_FN(_events_cb(obj.depth, _abi.DEPTH_DTYPE)),
+        "trades_enable": lambda: _abi.TRADES_ENABLE_FN(guard(lambda cap: obj.trades_enable(int(cap)))),
+        "trades": lambda: _abi.QUOTES_FN(_events_cb(obj.trades, _abi.TRADE_DTYPE)),
+        "order_query": lambda: _abi.ORDER_QUERY_FN(guard(query)),
+        "order_preview": lambda: _abi.ORDER_PREVIEW_FN(guard(preview)),
+    }
+    for name, make in hooks.items():
+        if hasattr(obj, name):
+            fn = make()
+            setattr(struct, name, fn)
+            keep.append(fn)
+    return tuple(keep)
+
+
 def python_matcher(obj) -> MeMatcher:
     """me_matcher over a Python object with match(batch) -> (results, tape), book_orders(symbol, depth)
     -> (bid entries, ask entries, bid levels, ask levels), num_symbols, max_batch, max_resting. Test
@@ -113,6 +192,7 @@ def python_matcher(obj) -> MeMatcher:
     if hasattr(obj, "quotes"):  # the top-of-book change feed: quotes(cap) -> (events QUOTE_DTYPE, left)
         m.quotes = _abi.QUOTES_FN(_quotes_cb(obj))
         m._keep += (m.quotes,)
+    m._keep += _set_parity_hooks(m, obj)
     return m
 
 
@@ -164,6 +244,7 @@ class ShardOps:
                                  _abi.BOOK_FN(book_cb), _abi.LEVELS_FN(levels_cb))
         if hasattr(book, "quotes"):  # quotes(cap) -> (events QUOTE_DTYPE with local ids, events left unread)
             self.struct.quotes = _abi.QUOTES_FN(_quotes_cb(book))
+        self._hooks = _set_parity_hooks(self.struct, book)  # depth / trades / order_query / order_preview
 
 
 def shard_symbols(num_symbols: int, world: int, rank: int) -> np.ndarray:
@@ -289,6 +370,68 @@ class Cluster:
             parts.append(ev)
             if not left:
                 return np.concatenate(parts)
+
+    def _feed(self, fn, dtype, cap: int):
+        cap = int(cap) or max(4 * self.num_symbols, 1)
+        out = np.zeros(cap, dtype=dtype)
+        n, left = C.c_size_t(0), C.c_size_t(0)
+        self._check(fn(self.h, ptr(out), cap, C.byref(n), C.byref(left)))
+        return out[: n.value], left.value
+
+    def _drain(self, read) -> np.ndarray:
+        parts = []
+        while True:
+            ev, left = read()
+            parts.append(ev)
+            if not left:
+                return np.concatenate(parts)
+
+    def depth_enable(self, depth: int, cap_events: int):
+        """me_cluster_depth_enable: every shard's depth feed on at `depth` levels per side (a log of cap_events
+        events), or off with depth 0 or cap_events 0."""
+        self._check(self.lib.me_cluster_depth_enable(self.h, int(depth), int(cap_events)))
+
+    def depth(self, cap: int = 0):
+        """me_cluster_depth: (events DEPTH_DTYPE with global symbol ids, left); `batches` is each shard's own count."""
+        return self._feed(self.lib.me_cluster_depth, _abi.DEPTH_DTYPE, cap)
+
+    def depth_drain(self) -> np.ndarray:
+        return self._drain(self.depth)
+
+    def trades_enable(self, cap_events: int):
+        """me_cluster_trades_enable: every shard's trade feed on (a log of cap_events events) or off (0)."""
+        self._check(self.lib.me_cluster_trades_enable(self.h, int(cap_events)))
+
+    def trades(self, cap: int = 0):
+        """me_cluster_trades: (events TRADE_DTYPE with global symbol ids, left)."""
+        return self._feed(self.lib.me_cluster_trades, _abi.TRADE_DTYPE, cap)
+
+    def trades_drain(self) -> np.ndarray:
+        return self._drain(self.trades)
+
+    def order_query(self, seqs) -> np.ndarray:
+        """me_cluster_order_query: one ORDER_INFO_DTYPE answer per seq (global symbol ids), from the shard that
+        holds it; found 0 when none does."""
+        q = np.ascontiguousarray(seqs, dtype=np.uint64)
+        out = np.zeros(len(q), dtype=_abi.ORDER_INFO_DTYPE)
+        self._check(self.lib.me_cluster_order_query(self.h, ptr(q) if len(q) else None, len(q),
+                                                    ptr(out) if len(q) else None))
+        return out
+
+    def order_preview(self, symbol, kind, price_q4, qty) -> np.ndarray:
+        """me_cluster_order_preview: one PREVIEW_DTYPE answer per query (global symbol ids); no book changes."""
+        sym = np.ascontiguousarray(symbol, dtype=np.uint32)
+        kd = np.ascontiguousarray(kind, dtype=np.uint8)
+        px = np.ascontiguousarray(price_q4, dtype=np.int64)
+        qt = np.ascontiguousarray(qty, dtype=np.int32)
+        n = len(sym)
+        assert len(kd) == len(px) == len(qt) == n
+        soa = MeOrderSoa()
+        for f, a in (("price_q4", px), ("qty", qt), ("symbol", sym), ("kind", kd)):
+            setattr(soa, f, a.ctypes.data)
+        out = np.zeros(n, dtype=_abi.PREVIEW_DTYPE)
+        self._check(self.lib.me_cluster_order_preview(self.h, C.byref(soa), n, ptr(out) if n else None))
+        return out
 
     def c_matcher(self) -> MeMatcher:
         """me_cluster_matcher: the service on rank 0 is created over it (two slices in flight)."""

@@ -45,7 +45,9 @@ std::mutex g_err_mu;
 std::string g_create_err;
 
 constexpr size_t kRec = 8 + 8 + 4 + 4 + 1;  // packed slice record: seq, price_q4, qty, symbol, kind
-enum : int64_t { CMD_SUBMIT = 1, CMD_COLLECT = 2, CMD_BOOK = 3, CMD_SNAPSHOT = 4, CMD_STOP = 5, CMD_QUOTES = 6, CMD_QUOTES_ENABLE = 7 };
+enum : int64_t { CMD_SUBMIT = 1, CMD_COLLECT = 2, CMD_BOOK = 3, CMD_SNAPSHOT = 4, CMD_STOP = 5, CMD_QUOTES = 6, CMD_QUOTES_ENABLE = 7,
+                CMD_DEPTH = 8, CMD_DEPTH_ENABLE = 9, CMD_TRADES = 10, CMD_TRADES_ENABLE = 11, CMD_ORDER_QUERY = 12,
+                CMD_ORDER_PREVIEW = 13 };
 constexpr int kMaxInflight = 2;
 // rank 0's time per protocol phase (me_cluster_phases)
 enum { PH_SPLIT, PH_CTRL, PH_SCATTER, PH_VOTE, PH_MATCH, PH_COLLECT, PH_GATHER, PH_MERGE, PH_SPLIT_COUNT, PH_SPLIT_SLOT, PH_N };
@@ -544,6 +546,7 @@ struct Part {
   char* in = nullptr;   // transport buffer: the packed part
   char* out = nullptr;  // transport buffer (device mode): tape, then results
   uint64_t eng_ticket = 0;       // engine over TCP: me_submit_host's ticket
+  uint64_t ord = 0;              // this part was the shard's ord-th batch (0: an empty part)
   std::vector<char> h_out;       // host mode: tape, then results
 };
 
@@ -566,6 +569,17 @@ struct PackView {
   PackView(char* p, size_t n)
       : seq((uint64_t*)p), px((int64_t*)(p + 8 * n)), qty((int32_t*)(p + 16 * n)), sym((uint32_t*)(p + 20 * n)),
         kind((uint8_t*)(p + 24 * n)) {}
+};
+
+// One change feed (quotes, depth, trades) as the cluster carries it. Rank 0 keeps what it gathered in `buf`
+// until it has been handed out. Every rank notes how far its shard's feed has got through the shard's batches:
+// no event stamped below `passed` is still to come (stamps never decrease within a feed).
+template <class E>
+struct Feed {
+  std::vector<E> buf;
+  size_t pos = 0;
+  bool on = false;
+  uint64_t passed = 0;
 };
 
 // Rank 0's split of a slice by owner, stable (each part keeps slice order = seq order), in two passes:
@@ -751,13 +765,17 @@ struct me_cluster {
   uint64_t max_resting_total = 0;
   bool failed = false;
   bool stopped = false;
-  // the quote feed (QUOTES): rank 0 keeps what it gathered until me_cluster_quotes handed it out; every rank
-  // notes which slices (counted over the whole cluster, from 1) its shard matched a part of, so a shard's own
-  // batch count can be turned into the slice's number for the service's matcher
-  std::vector<me_quote> qbuf;
-  size_t qpos = 0;
+  // the feeds (QUOTES, DEPTH, TRADES): every rank notes which slices (counted over the whole cluster, from 1)
+  // its shard matched a part of, so a shard's own batch count can be turned into the slice's number for the
+  // service's matcher. The three feeds read that map at different times: an entry goes only when every feed
+  // that is on has passed it (trim_slices).
+  Feed<me_quote> fq;
+  Feed<me_depth_event> fd;
+  Feed<me_trade> ft;
   std::deque<uint64_t> qslice;  // qslice[b - 1 - qbase]: the slice that was this shard's b-th batch
   uint64_t qbase = 0, nslices = 0;
+  uint64_t collected_b = 0;     // the shard's batch count at the last part collected: its events are logged
+  uint64_t batches() const { return qbase + qslice.size(); }
   uint64_t slices = 0;
   std::string err;
 
@@ -836,6 +854,7 @@ extern "C" me_cluster* me_cluster_create(const me_cluster_config* cfg, const me_
   if (ops) {
     c->ops = *ops;
     c->use_ops = true;
+    c->fq.on = ops->quotes != nullptr;  // (a shard that is not an engine feeds quotes whenever it is asked)
     my_resting = ops->max_resting;
     c->tape_cap = ops->max_resting + 2ull * cfg->max_batch;
   } else {
@@ -954,6 +973,7 @@ static int run_submit(me_cluster* c, const int64_t* hdr) {
   p.nl = (uint64_t)hdr[6 + W + me];
   p.nf = 0;
   p.eng_ticket = 0;
+  p.ord = 0;
   std::vector<size_t> bytes(W);
   for (uint32_t r = 0; r < W; ++r) bytes[r] = kRec * (size_t)hdr[6 + r];
   if (direct) bytes[0] = 0;
@@ -1022,7 +1042,10 @@ static int run_submit(me_cluster* c, const int64_t* hdr) {
   }
   p.used = true;
   ++c->nslices;
-  if (p.n) c->qslice.push_back(c->nslices);
+  if (p.n) {
+    c->qslice.push_back(c->nslices);
+    p.ord = c->batches();
+  }
   return ME_OK;
 }
 
@@ -1060,6 +1083,7 @@ static int run_collect(me_cluster* c, const int64_t* hdr) {
     c->failed = true;
     return c->fail(ME_E_STATE, "a shard lost its part of the slice");
   }
+  if (p.ord) c->collected_b = std::max(c->collected_b, p.ord);
   t = now_s();
   // payloads padded to 8 B, so every rank's tape starts aligned in rank 0's gather buffer (rank 0's own
   // outputs, direct, stay where the engine put them)
@@ -1310,42 +1334,72 @@ static int run_snapshot(me_cluster* c, const int64_t* hdr, me_level* levels, uin
   return ME_OK;
 }
 
-// QUOTES_ENABLE: every shard's feed on (hdr[3] = the log's capacity in events) or off (0).
-static int run_quotes_enable(me_cluster* c, const int64_t* hdr) {
-  const uint64_t cap = (uint64_t)hdr[3];
+// ---- the three feeds: one enable and one drain-and-gather routine, over the event type ---------------
+// Slice-map entries that every feed that is on has passed are dropped; a feed that is off has passed them all
+// (its next events, if it is ever enabled, are stamped with the batch count of that moment or later). The entry
+// of batch `passed` itself stays: a feed may still log events with the stamp it showed last.
+static void trim_slices(me_cluster* c) {
+  uint64_t m = c->batches();
+  if (c->fq.on) m = std::min(m, c->fq.passed);
+  if (c->fd.on) m = std::min(m, c->fd.passed);
+  if (c->ft.on) m = std::min(m, c->ft.passed);
+  while (c->qbase + 1 < m && !c->qslice.empty()) {
+    c->qslice.pop_front();
+    ++c->qbase;
+  }
+}
+
+// gather_host for the feeds and the two queries; one shard whose rank 0 drives its engine directly has nothing
+// to move (as collect, which hands out the engine's outputs in place)
+static bool gather_rows(me_cluster* c, const std::vector<char>& mine, std::vector<char>& all,
+                        std::vector<size_t>& bytes) {
+  if (c->cfg.world == 1 && c->direct0) {
+    all = mine;
+    bytes.assign(1, mine.size());
+    return true;
+  }
+  return gather_host(c, mine, all, bytes);
+}
+
+// *_ENABLE: every shard's feed on or off. set(on) switches this rank's shard and answers the state it is in
+// afterwards through *now (a failing engine call leaves the feed off).
+template <class E, class S>
+static int run_feed_enable(me_cluster* c, Feed<E>& f, bool on, S&& set, const char* what) {
   int rc = ME_OK;
-  if (!c->failed) {
-    if (c->use_ops)
-      rc = cap && !c->ops.quotes ? ME_E_INVALID : ME_OK;  // (a shard that is not an engine feeds whenever it is asked)
-    else
-      rc = me_quotes_enable(c->eng, cap);
-  }
+  bool now = f.on;
+  if (!c->failed) rc = set(on, &now);
   if (!agree(c, rc)) return c->tfail("status");
-  if (rc != ME_OK) return c->fail(rc, "a shard has no quote feed or failed to enable it");
-  if (c->cfg.rank == 0) {
-    c->qbuf.clear();
-    c->qpos = 0;
+  if (rc != ME_OK) {
+    if (on && !c->failed) (void)set(false, &now);  // on every shard or on none: a failing call leaves the feed off
+    f.on = now;
+    trim_slices(c);
+    return c->fail(rc, std::string("a shard has no ") + what + " feed or failed to enable it");
   }
+  f.on = now;
+  f.passed = c->batches();  // a fresh feed: its first events carry the batch count of this moment
+  trim_slices(c);
+  f.buf.clear();
+  f.pos = 0;
   return ME_OK;
 }
 
-// QUOTES: every rank drains its shard's feed (global symbol ids) and sends the events to rank 0, which
-// appends them in rank order. hdr[3] != 0: `batches` is turned from the shard's own count into the number
-// of the slice (the service's matcher); else it stays the shard's own count.
-static int run_quotes(me_cluster* c, const int64_t* hdr) {
-  const bool restamp = hdr[3] != 0;
-  std::vector<me_quote> ev;
+// QUOTES / DEPTH / TRADES: every rank drains its shard's feed with read() until nothing is left (global symbol
+// ids) and sends the events to rank 0, which appends them in rank order. restamp: `batches` is turned from the
+// shard's own count into the number of the slice (the service's matcher); else it stays the shard's own count.
+template <class E, class R>
+static int run_feed(me_cluster* c, Feed<E>& f, bool restamp, R&& read, const char* what) {
+  std::vector<E> ev;
   int rc = ME_OK;
   if (!c->failed) {
-    std::vector<me_quote> buf(4096);
+    constexpr size_t kChunk = 1 << 14;  // events per read, straight into ev's tail
+    size_t have = 0;
     for (size_t n = 0, left = 1; rc == ME_OK && left;) {
-      left = 0;
-      if (c->use_ops)
-        rc = c->ops.quotes ? c->ops.quotes(c->ops.ctx, buf.data(), buf.size(), &n, &left) : ME_E_INVALID;
-      else
-        rc = me_quotes_read(c->eng, buf.data(), buf.size(), &n, &left);
-      if (rc == ME_OK) ev.insert(ev.end(), buf.begin(), buf.begin() + std::min(n, buf.size()));
+      ev.resize(have + kChunk);
+      n = left = 0;
+      rc = read(ev.data() + have, kChunk, &n, &left);
+      if (rc == ME_OK) have += std::min(n, kChunk);
     }
+    ev.resize(have);
     const std::vector<uint32_t>& ids = c->members[c->cfg.rank];
     uint64_t last = 0;
     for (auto& q : ev) {
@@ -1362,28 +1416,227 @@ static int run_quotes(me_cluster* c, const int64_t* hdr) {
         q.batches = k >= c->qbase && k - c->qbase < c->qslice.size() ? c->qslice[k - c->qbase] : c->nslices;
       }
     }
-    while (last > 1 && c->qbase + 1 < last && !c->qslice.empty()) {  // stamps never decrease: older entries are done
-      c->qslice.pop_front();
-      ++c->qbase;
+    if (rc == ME_OK) {
+      // stamps never decrease, and the log is empty now: whatever the parts collected so far had to log is out
+      f.passed = std::max({f.passed, last, c->collected_b});
+      trim_slices(c);
     }
   }
   if (!agree(c, rc)) return c->tfail("status");
-  if (rc != ME_OK) return c->fail(rc, "a shard failed to read its quote feed");
-  std::vector<char> mine((const char*)ev.data(), (const char*)ev.data() + ev.size() * sizeof(me_quote)), all;
+  if (rc != ME_OK) return c->fail(rc, std::string("a shard failed to read its ") + what + " feed");
+  if (c->cfg.world == 1 && c->direct0) {  // one shard driven directly: its events are the cluster's, no copy
+    if (f.buf.empty())
+      f.buf = std::move(ev);
+    else
+      f.buf.insert(f.buf.end(), ev.begin(), ev.end());
+    return ME_OK;
+  }
+  std::vector<char> mine((const char*)ev.data(), (const char*)ev.data() + ev.size() * sizeof(E)), all;
   std::vector<size_t> bytes;
-  if (!gather_host(c, mine, all, bytes)) return c->tfail("quotes gather");
+  if (!gather_rows(c, mine, all, bytes)) return c->tfail("feed gather");
   if (c->cfg.rank != 0) return ME_OK;
   size_t off = 0;
   for (uint32_t r = 0; r < c->cfg.world; ++r) {
-    const me_quote* q = (const me_quote*)(all.data() + off);
-    c->qbuf.insert(c->qbuf.end(), q, q + bytes[r] / sizeof(me_quote));
+    const E* q = (const E*)(all.data() + off);
+    f.buf.insert(f.buf.end(), q, q + bytes[r] / sizeof(E));
     off += bytes[r];
   }
   return ME_OK;
 }
 
-static int dispatch(me_cluster* c, const int64_t* hdr, const BookReq* q, me_level* levels, uint32_t* counts) {
+// hdr[3] = the log's capacity in events (0: off); DEPTH_ENABLE: hdr[4] = the depth (0: off)
+static int run_quotes_enable(me_cluster* c, const int64_t* hdr) {
+  const uint64_t cap = (uint64_t)hdr[3];
+  return run_feed_enable(c, c->fq, cap != 0, [&](bool on, bool* now) -> int {
+    if (c->use_ops) {  // (a shard that is not an engine has no switch: it feeds whenever it is asked)
+      *now = c->ops.quotes != nullptr;
+      return on && !c->ops.quotes ? ME_E_INVALID : ME_OK;
+    }
+    const int rc = me_quotes_enable(c->eng, on ? cap : 0);
+    *now = on && rc == ME_OK;
+    return rc;
+  }, "quote");
+}
+static int run_depth_enable(me_cluster* c, const int64_t* hdr) {
+  const uint64_t cap = (uint64_t)hdr[3];
+  const uint32_t depth = (uint32_t)hdr[4];
+  return run_feed_enable(c, c->fd, cap != 0 && depth != 0, [&](bool on, bool* now) -> int {
+    int rc;
+    if (on && depth > ME_DEPTH_MAX)
+      rc = ME_E_INVALID;
+    else if (c->use_ops)
+      rc = c->ops.depth_enable && c->ops.depth ? c->ops.depth_enable(c->ops.ctx, on ? depth : 0, on ? cap : 0)
+                                               : (on ? ME_E_INVALID : ME_OK);
+    else
+      rc = me_depth_enable(c->eng, on ? depth : 0, on ? cap : 0);
+    *now = on && rc == ME_OK;
+    return rc;
+  }, "depth");
+}
+static int run_trades_enable(me_cluster* c, const int64_t* hdr) {
+  const uint64_t cap = (uint64_t)hdr[3];
+  return run_feed_enable(c, c->ft, cap != 0, [&](bool on, bool* now) -> int {
+    int rc;
+    if (c->use_ops)
+      rc = c->ops.trades_enable && c->ops.trades ? c->ops.trades_enable(c->ops.ctx, on ? cap : 0)
+                                                 : (on ? ME_E_INVALID : ME_OK);
+    else
+      rc = me_trades_enable(c->eng, on ? cap : 0);
+    *now = on && rc == ME_OK;
+    return rc;
+  }, "trade");
+}
+
+// hdr[3] != 0: restamp
+static int run_quotes(me_cluster* c, const int64_t* hdr) {
+  return run_feed(c, c->fq, hdr[3] != 0, [&](me_quote* out, size_t cap, size_t* n, size_t* left) -> int {
+    if (c->use_ops) return c->ops.quotes ? c->ops.quotes(c->ops.ctx, out, cap, n, left) : ME_E_INVALID;
+    return me_quotes_read(c->eng, out, cap, n, left);
+  }, "quote");
+}
+static int run_depth(me_cluster* c, const int64_t* hdr) {
+  return run_feed(c, c->fd, hdr[3] != 0, [&](me_depth_event* out, size_t cap, size_t* n, size_t* left) -> int {
+    if (c->use_ops) return c->ops.depth ? c->ops.depth(c->ops.ctx, out, cap, n, left) : ME_E_INVALID;
+    return me_depth_read(c->eng, out, cap, n, left);
+  }, "depth");
+}
+static int run_trades(me_cluster* c, const int64_t* hdr) {
+  return run_feed(c, c->ft, hdr[3] != 0, [&](me_trade* out, size_t cap, size_t* n, size_t* left) -> int {
+    if (c->use_ops) return c->ops.trades ? c->ops.trades(c->ops.ctx, out, cap, n, left) : ME_E_INVALID;
+    return me_trades_read(c->eng, out, cap, n, left);
+  }, "trade");
+}
+
+// Rank 0's caller buffers for ORDER_QUERY and ORDER_PREVIEW.
+struct RowReq {
+  const uint64_t* seqs = nullptr;  // ORDER_QUERY: the chunk's seqs ...
+  me_order_info* info = nullptr;   // ... and its answers
+  const char* packed = nullptr;    // ORDER_PREVIEW: the parts, rank order (preview_bytes each)
+  const uint32_t* prank = nullptr; // per query: its rank (world: answered by rank 0 itself) ...
+  const uint32_t* pidx = nullptr;  // ... and its index in that rank's part
+  me_preview* pv = nullptr;
+  size_t n = 0;
+};
+// a preview part of n queries: px[n] qty[n] sym[n] kind[n], padded so that the next part starts aligned
+inline size_t preview_bytes(size_t n) { return round8(17 * n); }
+
+// ORDER_QUERY (hdr[3] = n): the seqs go to every rank, every shard answers all of them, rank 0 keeps per seq
+// the one answer that found it.
+static int run_order_query(me_cluster* c, const int64_t* hdr, const RowReq* x) {
+  const size_t n = (size_t)hdr[3];
+  const uint32_t W = c->cfg.world;
+  std::vector<int64_t> seqs(n);
+  if (c->cfg.rank == 0) memcpy(seqs.data(), x->seqs, 8 * n);
+  if (!c->tp->bcast(seqs.data(), n)) return c->tfail("seq broadcast");
+  std::vector<me_order_info> info(n);
+  int rc = ME_E_STATE;
+  if (!c->failed) {
+    if (c->use_ops)
+      rc = c->ops.order_query ? c->ops.order_query(c->ops.ctx, (const uint64_t*)seqs.data(), n, info.data()) : ME_E_INVALID;
+    else
+      rc = me_order_query(c->eng, (const uint64_t*)seqs.data(), n, info.data());
+    if (rc == ME_OK && c->use_ops) {  // local ids -> global (an engine shard writes symbol_ids itself)
+      const std::vector<uint32_t>& ids = c->members[c->cfg.rank];
+      for (auto& a : info) {
+        if (!a.found) continue;
+        if (a.symbol >= ids.size()) {
+          rc = ME_E_STATE;
+          break;
+        }
+        a.symbol = ids[a.symbol];
+      }
+    }
+  }
+  if (!agree(c, rc)) return c->tfail("status");
+  if (rc != ME_OK) return c->fail(rc, "a shard has no order query or failed it" + (c->eng ? ": " + eng_err(c->eng) : std::string()));
+  std::vector<char> mine((const char*)info.data(), (const char*)info.data() + n * sizeof(me_order_info)), all;
+  std::vector<size_t> bytes;
+  if (!gather_rows(c, mine, all, bytes)) return c->tfail("order query gather");
+  if (c->cfg.rank != 0) return ME_OK;
+  for (size_t i = 0; i < n; ++i) {
+    me_order_info& o = x->info[i];
+    memset(&o, 0, sizeof o);
+    o.seq = (uint64_t)seqs[i];
+  }
+  size_t off = 0;
+  for (uint32_t r = 0; r < W; ++r) {
+    if (bytes[r] < n * sizeof(me_order_info)) return c->fail(ME_E_STATE, "shard " + std::to_string(r) + " sent short order query answers");
+    const me_order_info* a = (const me_order_info*)(all.data() + off);
+    for (size_t i = 0; i < n; ++i) {
+      if (!a[i].found) continue;
+      if (x->info[i].found) return c->fail(ME_E_STATE, "two shards hold seq " + std::to_string((uint64_t)seqs[i]));
+      x->info[i] = a[i];
+    }
+    off += bytes[r];
+  }
+  return ME_OK;
+}
+
+// ORDER_PREVIEW (hdr[6 + r] = rank r's queries): the parts are scattered, every shard previews its own, the
+// answers are gathered and rank 0 puts them back into query order.
+static int run_order_preview(me_cluster* c, const int64_t* hdr, const RowReq* x) {
+  const uint32_t W = c->cfg.world, me = c->cfg.rank;
+  const size_t n = (size_t)hdr[6 + me];
+  std::vector<size_t> bytes(W);
+  size_t tot = 0;
+  for (uint32_t r = 0; r < W; ++r) tot += (bytes[r] = preview_bytes((size_t)hdr[6 + r]));
+  std::vector<char> part(bytes[me]);
+  if (me == 0 ? tot > 0 : bytes[me] > 0) {  // a rank with nothing to send or receive stays out of the scatter
+    char* ts = me == 0 ? c->tp->alloc(tot) : nullptr;
+    char* tr = c->tp->alloc(bytes[me]);
+    const bool ok = tr && (me != 0 || (ts && c->tp->put(ts, x->packed, tot))) && c->tp->scatterv(ts, bytes, tr) &&
+                    c->tp->get(part.data(), tr, bytes[me]);
+    c->tp->release(ts);
+    c->tp->release(tr);
+    if (!ok) return c->tfail("preview scatter");
+  }
+  std::vector<me_preview> pv(n);
+  int rc = ME_E_STATE;
+  if (!c->failed) {
+    char* p = part.data();
+    me_order_soa q{};
+    q.price_q4 = (const int64_t*)p;
+    q.qty = (const int32_t*)(p + 8 * n);
+    q.symbol = (const uint32_t*)(p + 12 * n);
+    q.kind = (const uint8_t*)(p + 16 * n);
+    if (c->use_ops)
+      rc = c->ops.order_preview ? (n ? c->ops.order_preview(c->ops.ctx, &q, n, pv.data()) : ME_OK) : ME_E_INVALID;
+    else
+      rc = n ? me_order_preview(c->eng, &q, n, pv.data()) : ME_OK;
+  }
+  if (!agree(c, rc)) return c->tfail("status");
+  if (rc != ME_OK) return c->fail(rc, "a shard has no order preview or failed it" + (c->eng ? ": " + eng_err(c->eng) : std::string()));
+  std::vector<char> mine((const char*)pv.data(), (const char*)pv.data() + n * sizeof(me_preview)), all;
+  std::vector<size_t> got;
+  if (!gather_rows(c, mine, all, got)) return c->tfail("preview gather");
+  if (me != 0) return ME_OK;
+  std::vector<const me_preview*> rows(W);
+  size_t off = 0;
+  for (uint32_t r = 0; r < W; ++r) {
+    if (got[r] < (size_t)hdr[6 + r] * sizeof(me_preview)) return c->fail(ME_E_STATE, "shard " + std::to_string(r) + " sent short preview answers");
+    rows[r] = (const me_preview*)(all.data() + off);
+    off += got[r];
+  }
+  for (size_t k = 0; k < x->n; ++k)
+    if (x->prank[k] < W) x->pv[k] = rows[x->prank[k]][x->pidx[k]];
+  return ME_OK;
+}
+
+static int dispatch(me_cluster* c, const int64_t* hdr, const BookReq* q, me_level* levels, uint32_t* counts,
+                    const RowReq* x) {
   switch (hdr[0]) {
+    case CMD_DEPTH:
+      return run_depth(c, hdr);
+    case CMD_DEPTH_ENABLE:
+      return run_depth_enable(c, hdr);
+    case CMD_TRADES:
+      return run_trades(c, hdr);
+    case CMD_TRADES_ENABLE:
+      return run_trades_enable(c, hdr);
+    case CMD_ORDER_QUERY:
+      return run_order_query(c, hdr, x);
+    case CMD_ORDER_PREVIEW:
+      return run_order_preview(c, hdr, x);
     case CMD_QUOTES:
       return run_quotes(c, hdr);
     case CMD_QUOTES_ENABLE:
@@ -1410,20 +1663,22 @@ extern "C" int me_cluster_serve(me_cluster* c) {
   while (!c->stopped) {
     if (!c->tp->bcast(hdr.data(), hdr.size())) return c->tfail("command channel");
     BookReq none{};
-    (void)dispatch(c, hdr.data(), &none, nullptr, nullptr);  // failures are agreed on inside
+    RowReq nox{};
+    (void)dispatch(c, hdr.data(), &none, nullptr, nullptr, &nox);  // failures are agreed on inside
   }
   return ME_OK;
 }
 
 static int issue(me_cluster* c, std::vector<int64_t>& hdr, const BookReq* q = nullptr, me_level* levels = nullptr,
-                 uint32_t* counts = nullptr) {
+                 uint32_t* counts = nullptr, const RowReq* x = nullptr) {
   if (c->cfg.rank != 0) return c->fail(ME_E_INVALID, "only rank 0 issues commands");
   if (c->stopped) return c->fail(ME_E_STATE, "cluster stopped");
   const double t = now_s();
   if (!c->tp->bcast(hdr.data(), hdr.size())) return c->tfail("command channel");
   c->ph[PH_CTRL] += now_s() - t;
   BookReq none{};
-  return dispatch(c, hdr.data(), q ? q : &none, levels, counts);
+  RowReq nox{};
+  return dispatch(c, hdr.data(), q ? q : &none, levels, counts, x ? x : &nox);
 }
 
 extern "C" int me_cluster_submit(me_cluster* c, const me_order_soa* b, size_t n, uint64_t* ticket) {
@@ -1542,29 +1797,153 @@ extern "C" int me_cluster_quotes_enable(me_cluster* c, uint64_t cap_events) {
   return issue(c, hdr);
 }
 
-static int cluster_quotes(me_cluster* c, me_quote* out, size_t cap, size_t* n, size_t* left, bool restamp) {
+// me_cluster_quotes / _depth / _trades: hand out what rank 0 gathered; drain the shards when that is used up
+template <class E>
+static int cluster_feed(me_cluster* c, Feed<E>* f, int64_t cmd, E* out, size_t cap, size_t* n, size_t* left,
+                        bool restamp) {
   if (n) *n = 0;
   if (left) *left = 0;
   if (!c || (cap && !out)) return ME_E_INVALID;
-  if (c->qpos == c->qbuf.size()) {  // everything gathered so far was handed out: drain the shards
-    c->qbuf.clear();
-    c->qpos = 0;
+  if (f->pos == f->buf.size()) {  // everything gathered so far was handed out: drain the shards
+    f->buf.clear();
+    f->pos = 0;
     std::vector<int64_t> hdr(c->hdr_words(), 0);
-    hdr[0] = CMD_QUOTES;
+    hdr[0] = cmd;
     hdr[3] = restamp ? 1 : 0;
     const int rc = issue(c, hdr);
     if (rc != ME_OK) return rc;
   }
-  const size_t k = std::min(cap, c->qbuf.size() - c->qpos);
-  if (k) memcpy(out, c->qbuf.data() + c->qpos, k * sizeof(me_quote));
-  c->qpos += k;
+  const size_t k = std::min(cap, f->buf.size() - f->pos);
+  if (k) memcpy(out, f->buf.data() + f->pos, k * sizeof(E));
+  f->pos += k;
   if (n) *n = k;
-  if (left) *left = c->qbuf.size() - c->qpos;
+  if (left) *left = f->buf.size() - f->pos;
   return ME_OK;
 }
 
 extern "C" int me_cluster_quotes(me_cluster* c, me_quote* out, size_t cap, size_t* n, size_t* left) {
-  return cluster_quotes(c, out, cap, n, left, false);
+  return cluster_feed(c, c ? &c->fq : nullptr, CMD_QUOTES, out, cap, n, left, false);
+}
+
+extern "C" int me_cluster_depth_enable(me_cluster* c, uint32_t depth, uint64_t cap_events) {
+  if (!c) return ME_E_INVALID;
+  std::vector<int64_t> hdr(c->hdr_words(), 0);
+  hdr[0] = CMD_DEPTH_ENABLE;
+  hdr[3] = (int64_t)cap_events;
+  hdr[4] = depth;
+  return issue(c, hdr);
+}
+
+extern "C" int me_cluster_depth(me_cluster* c, me_depth_event* out, size_t cap, size_t* n, size_t* left) {
+  return cluster_feed(c, c ? &c->fd : nullptr, CMD_DEPTH, out, cap, n, left, false);
+}
+
+extern "C" int me_cluster_trades_enable(me_cluster* c, uint64_t cap_events) {
+  if (!c) return ME_E_INVALID;
+  std::vector<int64_t> hdr(c->hdr_words(), 0);
+  hdr[0] = CMD_TRADES_ENABLE;
+  hdr[3] = (int64_t)cap_events;
+  return issue(c, hdr);
+}
+
+extern "C" int me_cluster_trades(me_cluster* c, me_trade* out, size_t cap, size_t* n, size_t* left) {
+  return cluster_feed(c, c ? &c->ft : nullptr, CMD_TRADES, out, cap, n, left, false);
+}
+
+// one shard whose rank 0 drives its engine directly: the two queries go straight to the engine, as collect does
+static bool direct_only(const me_cluster* c) { return c->cfg.world == 1 && c->direct0; }
+static int rows_ready(me_cluster* c) {  // what issue() checks, for the calls that may issue nothing
+  if (c->cfg.rank != 0) return c->fail(ME_E_INVALID, "only rank 0 issues commands");
+  if (c->stopped) return c->fail(ME_E_STATE, "cluster stopped");
+  return ME_OK;
+}
+
+extern "C" int me_cluster_order_query(me_cluster* c, const uint64_t* seqs, size_t n, me_order_info* out) {
+  if (!c) return ME_E_INVALID;
+  if (n > ((size_t)1 << 24)) return c->fail(ME_E_INVALID, "order query: more than 2^24 seqs");
+  if (n && (!seqs || !out)) return c->fail(ME_E_INVALID, "order query: null seqs or out");
+  if (!n) return ME_OK;
+  int rc = rows_ready(c);
+  if (rc != ME_OK) return rc;
+  if (direct_only(c)) {
+    if (c->failed) return c->fail(ME_E_STATE, "cluster failed: " + c->err);
+    rc = me_order_query(c->eng, seqs, n, out);
+    return rc == ME_OK ? ME_OK : c->fail(rc, "order query: " + eng_err(c->eng));
+  }
+  for (size_t at = 0; at < n; at += c->cfg.max_batch) {
+    const size_t k = std::min<size_t>(c->cfg.max_batch, n - at);
+    std::vector<int64_t> hdr(c->hdr_words(), 0);
+    hdr[0] = CMD_ORDER_QUERY;
+    hdr[3] = (int64_t)k;
+    RowReq x;
+    x.seqs = seqs + at;
+    x.info = out + at;
+    x.n = k;
+    if ((rc = issue(c, hdr, nullptr, nullptr, nullptr, &x)) != ME_OK) return rc;
+  }
+  return ME_OK;
+}
+
+extern "C" int me_cluster_order_preview(me_cluster* c, const me_order_soa* q, size_t n, me_preview* out) {
+  if (!c) return ME_E_INVALID;
+  if (n > ((size_t)1 << 24)) return c->fail(ME_E_INVALID, "order preview: more than 2^24 queries");
+  if (n && (!q || !q->symbol || !q->kind || !q->price_q4 || !q->qty || !out))
+    return c->fail(ME_E_INVALID, "order preview: null query arrays or out");
+  for (size_t i = 0; i < n; ++i)
+    if (q->kind[i] & 0x08u) return c->fail(ME_E_INVALID, "order preview: a CANCEL or REDUCE kind cannot be previewed");
+  if (!n) return ME_OK;
+  int rc = rows_ready(c);
+  if (rc != ME_OK) return rc;
+  if (direct_only(c)) {
+    if (c->failed) return c->fail(ME_E_STATE, "cluster failed: " + c->err);
+    rc = me_order_preview(c->eng, q, n, out);
+    return rc == ME_OK ? ME_OK : c->fail(rc, "order preview: " + eng_err(c->eng));
+  }
+  const uint32_t W = c->cfg.world, S = c->cfg.num_symbols;
+  std::vector<uint32_t> prank, pidx;
+  std::vector<char> packed;
+  for (size_t at = 0; at < n; at += c->cfg.max_batch) {
+    const size_t k = std::min<size_t>(c->cfg.max_batch, n - at);
+    std::vector<int64_t> hdr(c->hdr_words(), 0);
+    hdr[0] = CMD_ORDER_PREVIEW;
+    prank.assign(k, W);
+    pidx.assign(k, 0);
+    // the split me_cluster_submit uses, over the four arrays: by owner, stable, local ids; a symbol no shard
+    // owns is answered here with the row one engine of num_symbols symbols gives it (BAD_SYMBOL, all else zero)
+    for (size_t i = 0; i < k; ++i) {
+      const uint32_t s = q->symbol[at + i];
+      if (s >= S) {
+        memset(&out[at + i], 0, sizeof(me_preview));
+        out[at + i].status = ME_ST_REJECTED;
+        out[at + i].reason = ME_RJ_BAD_SYMBOL;
+        continue;
+      }
+      prank[i] = c->owner[s];
+      pidx[i] = (uint32_t)hdr[6 + prank[i]]++;
+    }
+    std::vector<size_t> off(W + 1, 0);
+    for (uint32_t r = 0; r < W; ++r) off[r + 1] = off[r] + preview_bytes((size_t)hdr[6 + r]);
+    if (!off[W]) continue;  // nothing for any shard
+    packed.assign(off[W], 0);
+    for (size_t i = 0; i < k; ++i) {
+      const uint32_t r = prank[i];
+      if (r >= W) continue;
+      const size_t nr = (size_t)hdr[6 + r], j = pidx[i];
+      char* p = packed.data() + off[r];
+      ((int64_t*)p)[j] = q->price_q4[at + i];
+      ((int32_t*)(p + 8 * nr))[j] = q->qty[at + i];
+      ((uint32_t*)(p + 12 * nr))[j] = c->local[q->symbol[at + i]];
+      ((uint8_t*)(p + 16 * nr))[j] = q->kind[at + i];
+    }
+    RowReq x;
+    x.packed = packed.data();
+    x.prank = prank.data();
+    x.pidx = pidx.data();
+    x.pv = out + at;
+    x.n = k;
+    if ((rc = issue(c, hdr, nullptr, nullptr, nullptr, &x)) != ME_OK) return rc;
+  }
+  return ME_OK;
 }
 
 extern "C" int me_cluster_stop(me_cluster* c) {
@@ -1591,7 +1970,24 @@ static int m_collect(void* ctx, uint64_t t, const me_fill** f, size_t* nf, const
 }
 // the service names events by slice number (me_service.h me_matcher.quotes): the shards translate their counts
 static int m_quotes(void* ctx, me_quote* out, size_t cap, size_t* n, size_t* left) {
-  return cluster_quotes((me_cluster*)ctx, out, cap, n, left, true);
+  me_cluster* c = (me_cluster*)ctx;
+  return cluster_feed(c, c ? &c->fq : nullptr, CMD_QUOTES, out, cap, n, left, true);
+}
+static int m_depth_enable(void* ctx, uint32_t depth, uint64_t cap) { return me_cluster_depth_enable((me_cluster*)ctx, depth, cap); }
+static int m_depth(void* ctx, me_depth_event* out, size_t cap, size_t* n, size_t* left) {
+  me_cluster* c = (me_cluster*)ctx;
+  return cluster_feed(c, c ? &c->fd : nullptr, CMD_DEPTH, out, cap, n, left, true);
+}
+static int m_trades_enable(void* ctx, uint64_t cap) { return me_cluster_trades_enable((me_cluster*)ctx, cap); }
+static int m_trades(void* ctx, me_trade* out, size_t cap, size_t* n, size_t* left) {
+  me_cluster* c = (me_cluster*)ctx;
+  return cluster_feed(c, c ? &c->ft : nullptr, CMD_TRADES, out, cap, n, left, true);
+}
+static int m_order_query(void* ctx, const uint64_t* seqs, size_t n, me_order_info* out) {
+  return me_cluster_order_query((me_cluster*)ctx, seqs, n, out);
+}
+static int m_order_preview(void* ctx, const me_order_soa* q, size_t n, me_preview* out) {
+  return me_cluster_order_preview((me_cluster*)ctx, q, n, out);
 }
 
 extern "C" int me_cluster_matcher(me_cluster* c, me_matcher* out) {
@@ -1607,6 +2003,12 @@ extern "C" int me_cluster_matcher(me_cluster* c, me_matcher* out) {
   out->submit = m_submit;
   out->collect = m_collect;
   out->quotes = m_quotes;
+  out->depth_enable = m_depth_enable;
+  out->depth = m_depth;
+  out->trades_enable = m_trades_enable;
+  out->trades = m_trades;
+  out->order_query = m_order_query;
+  out->order_preview = m_order_preview;
   return ME_OK;
 }
 

@@ -688,8 +688,9 @@ static int dp_pull(me_service* s) {
   std::vector<me_depth_event> buf(4096);
   for (;;) {
     size_t n = 0, left = 0;
-    const int rc = me_depth_read(s->eng, buf.data(), buf.size(), &n, &left);
-    if (rc != ME_OK) return s->fail(rc, "depth stream: reading the engine's depth feed failed: " + backend_err(s));
+    const int rc = s->eng ? me_depth_read(s->eng, buf.data(), buf.size(), &n, &left)
+                          : s->m.depth(s->m.ctx, buf.data(), buf.size(), &n, &left);
+    if (rc != ME_OK) return s->fail(rc, "depth stream: reading the backend's depth feed failed: " + backend_err(s));
     std::lock_guard<std::mutex> lm(s->md_mu);
     for (size_t i = 0; i < n; ++i) {
       const me_depth_event& ev = buf[i];
@@ -768,8 +769,9 @@ static int tr_pull(me_service* s) {
   std::vector<me_trade> buf(1024);
   for (;;) {
     size_t n = 0, left = 0;
-    const int rc = me_trades_read(s->eng, buf.data(), buf.size(), &n, &left);
-    if (rc != ME_OK) return s->fail(rc, "trade stream: reading the engine's trade feed failed: " + backend_err(s));
+    const int rc = s->eng ? me_trades_read(s->eng, buf.data(), buf.size(), &n, &left)
+                          : s->m.trades(s->m.ctx, buf.data(), buf.size(), &n, &left);
+    if (rc != ME_OK) return s->fail(rc, "trade stream: reading the backend's trade feed failed: " + backend_err(s));
     std::lock_guard<std::mutex> lm(s->md_mu);
     for (size_t i = 0; i < n; ++i) {
       const me_trade& ev = buf[i];
@@ -1643,6 +1645,11 @@ extern "C" void me_service_destroy(me_service* s) {
     s->pq_cv.notify_all();
   }
   if (s->persister.joinable()) s->persister.join();
+  if (!s->eng) {  // a matcher outlives its service: the feeds this service turned on go off with it
+    std::lock_guard<std::mutex> le(s->eng_mu);
+    if (s->dp_on && s->m.depth_enable) (void)s->m.depth_enable(s->m.ctx, 0, 0);
+    if (s->tr_on && s->m.trades_enable) (void)s->m.trades_enable(s->m.ctx, 0);
+  }
   close_db(s);
   delete s;
 }
@@ -1723,7 +1730,7 @@ extern "C" int me_service_order_status(me_service* s, const char* client_id, con
   if (n > ((size_t)1 << 24)) return s->fail(ME_E_INVALID, "order status: more than 2^24 ids");
   if (n && (!order_ids || !out)) return s->fail(ME_E_INVALID, "order status: null order_ids or out");
   if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
-  if (!s->eng) return s->fail(ME_E_INVALID, "order status: the backend has no order query");
+  if (!s->eng && !s->m.order_query) return s->fail(ME_E_INVALID, "order status: the backend has no order query");
   if (!n) return ME_OK;
   const std::string client = client_id ? client_id : "";
   std::vector<uint64_t> seqs(n);
@@ -1731,7 +1738,8 @@ extern "C" int me_service_order_status(me_service* s, const char* client_id, con
   std::vector<me_order_info> info(n);
   {
     std::lock_guard<std::mutex> le(s->eng_mu);
-    const int rc = me_order_query(s->eng, seqs.data(), n, info.data());
+    const int rc = s->eng ? me_order_query(s->eng, seqs.data(), n, info.data())
+                          : s->m.order_query(s->m.ctx, seqs.data(), n, info.data());
     if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
   }
   std::lock_guard<std::mutex> lv(s->live_mu);
@@ -1770,7 +1778,7 @@ extern "C" int me_service_preview_order(me_service* s, const me_order_request* r
   if (!s) return ME_E_INVALID;
   if (!r || !out) return s->fail(ME_E_INVALID, "order preview: null request or out");
   if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
-  if (!s->eng) return s->fail(ME_E_INVALID, "order preview: the backend has no order preview");
+  if (!s->eng && !s->m.order_preview) return s->fail(ME_E_INVALID, "order preview: the backend has no order preview");
   const char* symbol = r->symbol ? r->symbol : "";
   if (!symbol[0]) return s->fail(ME_E_INVALID, "symbol is required");
   if (r->quantity <= 0) return s->fail(ME_E_INVALID, "quantity must be > 0");
@@ -1805,7 +1813,7 @@ extern "C" int me_service_preview_order(me_service* s, const me_order_request* r
   q.symbol = &sid;
   q.kind = &kd;
   std::lock_guard<std::mutex> le(s->eng_mu);
-  const int rc = me_order_preview(s->eng, &q, 1, out);
+  const int rc = s->eng ? me_order_preview(s->eng, &q, 1, out) : s->m.order_preview(s->m.ctx, &q, 1, out);
   if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
   return ME_OK;
 }
@@ -1995,14 +2003,16 @@ extern "C" int me_service_depth_subscribe(me_service* s, uint32_t depth) {
   };
   if (!depth) {
     if (s->dp_on && s->eng) me_depth_enable(s->eng, 0, 0);
+    if (s->dp_on && !s->eng && s->m.depth_enable) s->m.depth_enable(s->m.ctx, 0, 0);
     std::lock_guard<std::mutex> lm(s->md_mu);
     reset(false, 0);
     return ME_OK;
   }
-  if (!s->eng) return s->fail(ME_E_INVALID, "depth stream: the matcher has no depth feed");
+  if (!s->eng && !(s->m.depth_enable && s->m.depth)) return s->fail(ME_E_INVALID, "depth stream: the matcher has no depth feed");
   if (depth > ME_DEPTH_MAX) return s->fail(ME_E_INVALID, "depth stream: depth above ME_DEPTH_MAX");
   // room for four jobs in which every level of every view changes
-  const int rc = me_depth_enable(s->eng, depth, std::max<uint64_t>(16ull * depth * s->sym_cap, 4096));
+  const uint64_t cap_ev = std::max<uint64_t>(16ull * depth * s->sym_cap, 4096);
+  const int rc = s->eng ? me_depth_enable(s->eng, depth, cap_ev) : s->m.depth_enable(s->m.ctx, depth, cap_ev);
   if (rc != ME_OK) return s->fail(rc, "depth stream: me_depth_enable failed: " + backend_err(s));
   std::vector<std::string> names;
   {
@@ -2072,13 +2082,15 @@ extern "C" int me_service_trades_subscribe(me_service* s, int on) {
   };
   if (!on) {
     if (s->tr_on && s->eng) me_trades_enable(s->eng, 0);
+    if (s->tr_on && !s->eng && s->m.trades_enable) s->m.trades_enable(s->m.ctx, 0);
     std::lock_guard<std::mutex> lm(s->md_mu);
     reset(false);
     return ME_OK;
   }
-  if (!s->eng) return s->fail(ME_E_INVALID, "trade stream: the matcher has no trade feed");
+  if (!s->eng && !(s->m.trades_enable && s->m.trades)) return s->fail(ME_E_INVALID, "trade stream: the matcher has no trade feed");
   // room for four jobs in which every symbol trades
-  const int rc = me_trades_enable(s->eng, std::max<uint64_t>(4ull * s->sym_cap, 1024));
+  const uint64_t cap_ev = std::max<uint64_t>(4ull * s->sym_cap, 1024);
+  const int rc = s->eng ? me_trades_enable(s->eng, cap_ev) : s->m.trades_enable(s->m.ctx, cap_ev);
   if (rc != ME_OK) return s->fail(rc, "trade stream: me_trades_enable failed: " + backend_err(s));
   std::vector<std::string> names;
   {

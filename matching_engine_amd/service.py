@@ -105,7 +105,7 @@ class MatchingEngineService:
         """PreviewOrder (build extension, me_service_preview_order): what submit_order with the same arguments
         would execute against the book now, as one PREVIEW_DTYPE row; nothing is submitted, no OID is taken. A
         request submit_order would refuse in-band raises ServiceError (code ME_E_INVALID) with its message; so
-        does a service over a matcher."""
+        does a service over a matcher without the order_preview hook."""
         req = MeOrderRequest(client_id.encode(), symbol.encode(), order_type, side, price, scale, quantity)
         out = np.zeros(1, dtype=_abi.PREVIEW_DTYPE)
         rc = self.lib.me_service_preview_order(self.h, C.byref(req), tif, ptr(out))
@@ -136,7 +136,7 @@ class MatchingEngineService:
         """OrderStatus (build extension, me_service_order_status): one dict per id with state (OS_NOT_RESTING /
         OS_PENDING / OS_RESTING), side, quantity, price, scale and the queue position (qty_ahead, orders_ahead,
         level_qty, qty_better, levels_better), from one device query for all ids. Only the owner's resting
-        orders answer RESTING. ServiceError (code ME_E_INVALID) on a matcher."""
+        orders answer RESTING. ServiceError (code ME_E_INVALID) on a matcher without the hook."""
         ids = [o.encode() for o in order_ids]
         n = len(ids)
         arr = (C.c_char_p * max(n, 1))(*ids)
@@ -219,7 +219,7 @@ class MatchingEngineService:
 
     def depth_subscribe(self, depth: int):
         """The depth stream (me_service_depth_subscribe): enable the engine's depth feed at `depth` levels per
-        side and queue the books as they stand; 0 turns it off. ServiceError (code ME_E_INVALID) on a matcher."""
+        side and queue the books as they stand; 0 turns it off. ServiceError (code ME_E_INVALID) on a matcher without the hook."""
         rc = self.lib.me_service_depth_subscribe(self.h, int(depth))
         if rc != 0:
             e = ServiceError(f"depth_subscribe failed ({rc}): {self.last_error()}")
@@ -247,7 +247,7 @@ class MatchingEngineService:
 
     def trades_subscribe(self, on: bool = True):
         """The trade stream (me_service_trades_subscribe): enable the engine's trade feed; fills matched before
-        are not counted. ServiceError (code ME_E_INVALID) on a matcher."""
+        are not counted. ServiceError (code ME_E_INVALID) on a matcher without the hook."""
         rc = self.lib.me_service_trades_subscribe(self.h, 1 if on else 0)
         if rc != 0:
             e = ServiceError(f"trades_subscribe failed ({rc}): {self.last_error()}")
