@@ -26,9 +26,9 @@
 //   ref_mu    per-book reference counts (which books an idle symbol may hand over)
 //   err_mu    the last error text
 //
-// The flusher keeps two slices in flight: slice k+1 is submitted to the backend (me_submit_host, or
-// the matcher's submit) before slice k is collected, so the backend's work on k+1 overlaps the
-// collect of k and its hand-off to the persister.
+// The flusher keeps two slices in flight: slice k+1 is submitted to the backend (its own engine or a
+// sharded deployment's matcher: one table of calls, Backend below) before slice k is collected, so the
+// backend's work on k+1 overlaps the collect of k and its hand-off to the persister.
 //
 // SQLite is loaded at run time (dlopen libsqlite3.so.0) so the library has no build-time
 // dependency on a sqlite3 header.
@@ -50,6 +50,7 @@
 
 #include "me_engine.h"
 #include "me_service.h"
+#include "me_service_feed.hpp"
 
 namespace {
 
@@ -203,13 +204,121 @@ constexpr size_t kMaxQueuedUpdates = size_t(1) << 24;  // oldest events are drop
 constexpr int kRows = 64;  // rows per multi-row INSERT (11 * 64 parameters < SQLite's 999 floor)
 constexpr size_t kMaxMatchedAhead = 4;  // matched slices the flusher may run ahead of the persister
 
+// ---- the backend: everything the service asks of what matches its slices -------------------------
+// Built in two places, backend_of(me_engine*) and backend_of(const me_matcher*); the rest of the file calls
+// through it and never asks which of the two it fronts. A facility the backend lacks is a NULL pointer
+// (`book` NULL: no backend at all). The reads and enables follow me_engine.h's contracts of the same names.
+struct Backend {
+  void* ctx = nullptr;
+  // submit / collect, both or neither: a slice now, its outputs later (two slices in flight). Without them
+  // `match` does both at once and one slice is in flight.
+  decltype(me_matcher::submit) submit = nullptr;
+  decltype(me_matcher::collect) collect = nullptr;
+  decltype(me_matcher::match) match = nullptr;
+  decltype(me_matcher::book) book = nullptr;
+  int (*quotes_enable)(void*, uint64_t cap_events) = nullptr;  // NULL with `quotes` set: the feed needs no enabling
+  decltype(me_matcher::quotes) quotes = nullptr;
+  decltype(me_matcher::depth_enable) depth_enable = nullptr;
+  decltype(me_matcher::depth) depth = nullptr;
+  decltype(me_matcher::trades_enable) trades_enable = nullptr;
+  decltype(me_matcher::trades) trades = nullptr;
+  decltype(me_matcher::order_query) order_query = nullptr;
+  decltype(me_matcher::order_preview) order_preview = nullptr;
+  int (*mass_cancel)(void*, const uint32_t* symbols, const uint8_t* sides, size_t n, me_book_entry* out, size_t cap,
+                     size_t* n_out, uint64_t* counts) = nullptr;
+  std::string (*last_error)(void*) = nullptr;
+  uint64_t (*fill_bound)(const Backend&, uint64_t n) = nullptr;  // fills n records can produce at most
+  uint32_t num_symbols = UINT32_MAX;  // books it holds (local ids 0 .. num_symbols-1)
+  uint32_t max_batch = 0;             // largest slice
+  uint64_t max_resting = 0;           // (a matcher's fill bound)
+  uint64_t seq_span = 1ull << 20;     // seqs one restart-recovery chunk may span
+  // A failed submit other than ME_E_CAPACITY: the slice was taken and is lost (the service fails). Else only
+  // ME_OK is "accepted" and every failure is a refusal that applied nothing.
+  bool failure_loses_slice = false;
+  // The depth and trade feeds the service turned on go off when it is destroyed (the backend outlives it).
+  bool feeds_off_at_destroy = false;
+};
+
+template <auto F, class... A>
+int eng_call(void* e, A... a) {
+  return F(static_cast<me_engine*>(e), a...);
+}
+
+Backend backend_of(me_engine* e) {
+  Backend b;
+  if (!e) return b;
+  b.ctx = e;
+  b.submit = eng_call<me_submit_host>;
+  b.collect = [](void* e, uint64_t t, const me_fill** f, size_t* nf, const me_order_result** r) {
+    size_t nr = 0;
+    return me_collect(static_cast<me_engine*>(e), t, f, nf, r, &nr);
+  };
+  b.book = [](void* e, uint32_t sid, uint32_t depth, me_book_entry* bids, size_t bids_cap, size_t* n_bids,
+              me_book_entry* asks, size_t asks_cap, size_t* n_asks, me_level* bl, me_level* al, size_t* nbl,
+              size_t* nal) {
+    if (!depth) depth = 0xFFFFFFFFu;  // the whole book: every window level plus the far levels
+    return me_book_orders(static_cast<me_engine*>(e), sid, depth, bids, bids_cap, n_bids, asks, asks_cap, n_asks, bl,
+                          al, nbl, nal);
+  };
+  b.quotes_enable = eng_call<me_quotes_enable>;
+  b.quotes = eng_call<me_quotes_read>;
+  b.depth_enable = eng_call<me_depth_enable>;
+  b.depth = eng_call<me_depth_read>;
+  b.trades_enable = eng_call<me_trades_enable>;
+  b.trades = eng_call<me_trades_read>;
+  b.order_query = eng_call<me_order_query>;
+  b.order_preview = eng_call<me_order_preview>;
+  b.mass_cancel = eng_call<me_mass_cancel>;
+  b.last_error = [](void* e) {
+    char t[512];
+    me_last_error(static_cast<me_engine*>(e), t, sizeof t);
+    return std::string(t);
+  };
+  b.fill_bound = [](const Backend& b, uint64_t n) { return me_fill_bound(static_cast<me_engine*>(b.ctx), n); };
+  me_config c{};
+  if (me_get_config(e, &c) == ME_OK) {
+    b.num_symbols = c.num_symbols;
+    b.max_batch = c.max_batch;
+    // one launch group must span fewer seqs than the seq ring: a recovery chunk stays below half of it
+    if (c.seq_ring) b.seq_span = std::max<uint64_t>(c.seq_ring / 2, 1);
+  }
+  // the flusher keeps two slices in flight, and me_collect holds the last collected slot back: three
+  // warm pinned slots, so no slot is pinned inside the serving path
+  me_host_reserve(e, 3);
+  return b;
+}
+
+Backend backend_of(const me_matcher* m) {
+  Backend b;
+  b.ctx = m->ctx;
+  if (m->submit && m->collect) {
+    b.submit = m->submit;
+    b.collect = m->collect;
+  }
+  b.match = m->match;
+  b.book = m->book;
+  b.quotes = m->quotes;  // (a matcher has no quote enable)
+  b.depth_enable = m->depth_enable;
+  b.depth = m->depth;
+  b.trades_enable = m->trades_enable;
+  b.trades = m->trades;
+  b.order_query = m->order_query;
+  b.order_preview = m->order_preview;
+  b.last_error = [](void*) { return std::string("matcher failed"); };
+  b.fill_bound = [](const Backend& b, uint64_t n) { return b.max_resting + 2 * n; };
+  b.num_symbols = m->num_symbols;
+  b.max_batch = m->max_batch;
+  b.max_resting = m->max_resting;
+  b.failure_loses_slice = true;
+  b.feeds_off_at_destroy = true;
+  return b;
+}
+
 }  // namespace
 
 struct me_service {
-  me_engine* eng = nullptr;
-  me_matcher m{};           // the matcher when the service fronts shards it does not own (m.match set)
-  uint32_t sym_cap = UINT32_MAX;  // symbols the engine holds (local ids 0 .. sym_cap-1)
-  size_t slice_max = 0;           // records per slice (the engine's max_batch)
+  Backend be;
+  size_t slice_max = 0;         // records per slice (the backend's max_batch, or me_service_start's)
   // --- mu
   std::mutex mu;
   std::unordered_map<std::string, uint32_t> sym;
@@ -247,36 +356,22 @@ struct me_service {
   std::vector<uint8_t> in_idle;   // ... each at most once: a book's count returns to 0 again and again
   uint64_t reclaimed = 0;
   uint64_t recovered = 0;
-  // --- md_mu: the market-data change stream (me_service_market_subscribe / _stream). Lock order:
-  // flush_mu, eng_mu, md_mu. One pending update per symbol, in first-change order; md_owner names a book's
-  // symbol per slice: {first slice ordinal, symbol}, oldest first (a book changes hands at submit time while
-  // events of earlier slices for its id may still be unread).
+  // --- md_mu: the three change streams (me_service_market_ / _depth_ / _trades_ subscribe and stream). Lock
+  // order: flush_mu, eng_mu, md_mu. Each is a me::ServiceFeed (me_service_feed.hpp): one pending item per
+  // symbol name in first-change order, and its own history of which symbol owned a book from which slice on.
   std::mutex md_mu;
-  std::atomic<bool> md_on{false};
-  std::list<me_market_update> md_q;
-  std::unordered_map<std::string, std::list<me_market_update>::iterator> md_at;
-  std::vector<std::deque<std::pair<uint64_t, std::string>>> md_owner;
-  // The depth stream (me_service_depth_subscribe / _stream), also under md_mu. The engine sends deltas, the
-  // service materialises views: dp_view holds every named symbol's top-D {price: qty} per side, dp_q the
-  // symbols whose view changed since they were last handed out, in first-change order (one entry each).
-  // dp_owner is the depth feed's own ownership history: the two feeds are read at different moments, and each
-  // pops only what its own stamps have passed.
+  me::ServiceFeed<me_market_update, sizeof(me_market_update::symbol) - 1> md;  // the pending quote
+  // The backend sends depth deltas, the service materialises views: dp_view holds every named symbol's top-D
+  // {price: qty} per side, and dp queues the names whose view changed since it was last handed out.
   struct DepthView {
     std::map<int64_t, int64_t> side[2];  // [0] bids, [1] asks, ascending price
   };
-  std::atomic<bool> dp_on{false};
-  uint32_t dp_depth = 0;
+  struct Changed {};
+  me::ServiceFeed<Changed, sizeof(me_depth_book::symbol) - 1> dp;
   std::unordered_map<std::string, DepthView> dp_view;
-  std::list<std::string> dp_q;
-  std::unordered_map<std::string, std::list<std::string>::iterator> dp_at;
-  std::vector<std::deque<std::pair<uint64_t, std::string>>> dp_owner;
-  // The trade stream (me_service_trades_subscribe / _stream), also under md_mu: one pending update per symbol
-  // name in first-trade order, the names' totals since the subscription, and the feed's own ownership history.
-  std::atomic<bool> tr_on{false};
-  std::list<me_trade_update> tr_q;
-  std::unordered_map<std::string, std::list<me_trade_update>::iterator> tr_at;
+  // The pending trade update, and the names' totals since the subscription.
+  me::ServiceFeed<me_trade_update, sizeof(me_trade_update::symbol) - 1> tr;
   std::unordered_map<std::string, std::pair<int64_t, uint64_t>> tr_cum;
-  std::vector<std::deque<std::pair<uint64_t, std::string>>> tr_owner;
   uint64_t nsub = 0;  // slices the backend accepted since create (eng_mu): slice k's events are stamped k
   // --- background flusher
   std::thread flusher;
@@ -404,7 +499,7 @@ static bool intern(me_service* s, const std::string& symbol, uint32_t& sid) {
     return true;
   }
   std::lock_guard<std::mutex> lr(s->ref_mu);
-  if (s->names.size() < s->sym_cap) {
+  if (s->names.size() < s->be.num_symbols) {
     sid = (uint32_t)s->names.size();
     s->names.push_back(symbol);
     s->sym.emplace(symbol, sid);
@@ -447,11 +542,7 @@ static bool load_resting(me_service* s, std::string& err) {
   const size_t cap = s->slice_max ? s->slice_max : 65536;
   // a recovery chunk is matched alone (flush_closed collects it before the next submit), so one launch
   // group spans only its own OIDs: below half the engine's seq ring (a matcher: 2^20)
-  uint64_t span = 1ull << 20;
-  if (s->eng) {
-    me_config c{};
-    if (me_get_config(s->eng, &c) == ME_OK && c.seq_ring) span = std::max<uint64_t>(c.seq_ring / 2, 1);
-  }
+  const uint64_t span = s->be.seq_span;
   bool ok = true;
   std::lock_guard<std::mutex> lk(s->mu);
   Slice cur;
@@ -499,24 +590,10 @@ static bool load_resting(me_service* s, std::string& err) {
   return ok;
 }
 
-static me_service* create(me_engine* engine, const me_matcher* m, const char* const* symbols, uint32_t num_symbols,
-                          const char* db_path) {
+static me_service* create(const Backend& be, const char* const* symbols, uint32_t num_symbols, const char* db_path) {
   me_service* s = new me_service();
-  s->eng = engine;
-  if (engine) {
-    me_config c{};
-    if (me_get_config(engine, &c) == ME_OK) {
-      s->sym_cap = c.num_symbols;
-      s->slice_max = c.max_batch;
-    }
-    // the flusher keeps two slices in flight, and me_collect holds the last collected slot back: three
-    // warm pinned slots, so no slot is pinned inside the serving path
-    me_host_reserve(engine, 3);
-  } else if (m) {
-    s->m = *m;
-    s->sym_cap = m->num_symbols;
-    s->slice_max = m->max_batch;
-  }
+  s->be = be;
+  s->slice_max = be.max_batch;
   for (uint32_t i = 0; i < num_symbols; ++i) {
     s->names.emplace_back(symbols[i]);
     s->sym.emplace(s->names.back(), i);
@@ -524,7 +601,7 @@ static me_service* create(me_engine* engine, const me_matcher* m, const char* co
     s->in_idle.push_back(1);
   }
   for (uint32_t i = num_symbols; i-- > 0;) s->idle.push_back(i);  // nothing rests on them yet
-  if (s->names.size() > s->sym_cap) s->fail(ME_E_INVALID, "me_service_create: more symbols than the engine holds");
+  if (s->names.size() > s->be.num_symbols) s->fail(ME_E_INVALID, "me_service_create: more symbols than the engine holds");
   std::string err;
   if (db_path && !open_db(s, db_path, err)) {
     // keep the object so the caller can read the error; persistence is disabled
@@ -555,24 +632,19 @@ static me_service* create(me_engine* engine, const me_matcher* m, const char* co
 
 extern "C" me_service* me_service_create(me_engine* engine, const char* const* symbols, uint32_t num_symbols,
                                          const char* db_path) {
-  return create(engine, nullptr, symbols, num_symbols, db_path);
+  return create(backend_of(engine), symbols, num_symbols, db_path);
 }
 
 extern "C" me_service* me_service_create_matcher(const me_matcher* m, const char* const* symbols,
                                                  uint32_t num_symbols, const char* db_path) {
   if (!m || !m->match || !m->book || !m->max_batch) return nullptr;
-  return create(nullptr, m, symbols, num_symbols, db_path);
+  return create(backend_of(m), symbols, num_symbols, db_path);
 }
 
-// The backend behind the service: its own engine, or the matcher of a sharded deployment.
-static bool has_backend(const me_service* s) { return s->eng || s->m.match; }
+// (a service created without an engine takes orders and answers every call that needs a backend with an error)
+static bool has_backend(const me_service* s) { return s->be.book != nullptr; }
 
-static std::string backend_err(me_service* s) {
-  if (!s->eng) return "matcher failed";
-  char e[512];
-  me_last_error(s->eng, e, sizeof e);
-  return e;
-}
+static std::string backend_err(me_service* s) { return s->be.last_error(s->be.ctx); }
 
 // A slice handed to the backend and not collected yet.
 struct Inflight {
@@ -583,34 +655,20 @@ struct Inflight {
   std::vector<me_fill> tape;
 };
 
-// Backends that take a slice now and hand its outputs back later: the engine (host slots and
-// tickets) and matchers with submit / collect. The flusher keeps two slices in flight with them.
-static bool backend_async(const me_service* s) { return s->eng || (s->m.submit && s->m.collect); }
-
 // Hand one slice to the backend (eng_mu held). accepted = the backend took it (a later failure loses
 // it); ME_E_CAPACITY with accepted false: refused, nothing of it was applied.
 static int backend_submit(me_service* s, Inflight& f, bool& accepted) {
+  const Backend& be = s->be;
   Slice& sl = f.sl;
   const size_t n = sl.size();
   me_order_soa b{sl.seq.data(), sl.px.data(), sl.qty.data(), sl.sid.data(), sl.kind.data()};
-  accepted = false;
-  if (s->eng) {
-    const int rc = me_submit_host(s->eng, &b, n, &f.ticket);
-    accepted = rc == ME_OK;
-    return rc;
-  }
-  if (s->m.submit && s->m.collect) {
-    const int rc = s->m.submit(s->m.ctx, &b, n, &f.ticket);
-    accepted = rc != ME_E_CAPACITY;
-    return rc;
-  }
   const me_fill* tape = nullptr;
   const me_order_result* res = nullptr;
   size_t nf = 0;
-  const int rc = s->m.match(s->m.ctx, &b, n, &tape, &nf, &res);
-  accepted = rc != ME_E_CAPACITY;
-  if (rc != ME_OK) return rc;
-  // the matcher's output views stay valid until its next call: copy them out under eng_mu
+  const int rc = be.submit ? be.submit(be.ctx, &b, n, &f.ticket) : be.match(be.ctx, &b, n, &tape, &nf, &res);
+  accepted = be.failure_loses_slice ? rc != ME_E_CAPACITY : rc == ME_OK;
+  if (rc != ME_OK || be.submit) return rc;
+  // matched at once, and the output views stay valid until the backend's next call: copy them out under eng_mu
   f.res.assign(res, res + n);
   f.tape.assign(tape, tape + nf);
   f.done = true;
@@ -622,24 +680,13 @@ static int backend_collect(me_service* s, Inflight& f) {
   if (f.done) return ME_OK;
   const me_fill* tape = nullptr;
   const me_order_result* res = nullptr;
-  size_t nf = 0, nr = 0;
-  const int rc = s->eng ? me_collect(s->eng, f.ticket, &tape, &nf, &res, &nr)
-                        : s->m.collect(s->m.ctx, f.ticket, &tape, &nf, &res);
+  size_t nf = 0;
+  const int rc = s->be.collect(s->be.ctx, f.ticket, &tape, &nf, &res);
   if (rc != ME_OK) return rc;
   f.res.assign(res, res + f.sl.size());
   f.tape.assign(tape, tape + nf);
   f.done = true;
   return ME_OK;
-}
-
-static int backend_book(me_service* s, uint32_t sid, uint32_t depth, me_book_entry* bids, size_t bids_cap,
-                        size_t* n_bids, me_book_entry* asks, size_t asks_cap, size_t* n_asks, me_level* bl,
-                        me_level* al, size_t* nbl, size_t* nal) {
-  if (s->eng) {
-    if (!depth) depth = 0xFFFFFFFFu;  // the whole book: every window level plus the far levels
-    return me_book_orders(s->eng, sid, depth, bids, bids_cap, n_bids, asks, asks_cap, n_asks, bl, al, nbl, nal);
-  }
-  return s->m.book(s->m.ctx, sid, depth, bids, bids_cap, n_bids, asks, asks_cap, n_asks, bl, al, nbl, nal);
 }
 
 static void put(char* dst, size_t cap, const std::string& v) {
@@ -648,169 +695,135 @@ static void put(char* dst, size_t cap, const std::string& v) {
   dst[k] = 0;
 }
 
-// ---- the market-data change stream ------------------------------------------------------------
+// ---- the change streams: quotes (md), depth (dp), trades (tr) -----------------------------------
+static int md_pull(me_service* s);
+static int dp_pull(me_service* s);
+static int tr_pull(me_service* s);
+
+// f(feed, its pull) for each of the three, in the order they are read after a slice.
+template <class F>
+static void each_feed(me_service* s, F&& f) {
+  f(s->md, md_pull);
+  f(s->dp, dp_pull);
+  f(s->tr, tr_pull);
+}
+
 // Slice number k was accepted by the backend (eng_mu held): the symbols that own its records' books from
-// slice k on. A book's entry is added only when its symbol differs from the last one noted.
+// slice k on, in every enabled feed's own history.
 static void md_note_owners(me_service* s, const Slice& sl, uint64_t k) {
+  bool any = false;
+  each_feed(s, [&](auto& f, auto) { any |= f.on; });
+  if (!any) return;
   std::lock_guard<std::mutex> lm(s->md_mu);
   for (size_t i = 0; i < sl.size(); ++i) {
-    const uint32_t sid = sl.sid[i];
-    if (sid == kNoBook) continue;
-    if (s->md_on) {
-      if (sid >= s->md_owner.size()) s->md_owner.resize((size_t)sid + 1);
-      auto& h = s->md_owner[sid];
-      if (h.empty() || h.back().second != sl.meta[i].symbol) h.emplace_back(k, sl.meta[i].symbol);
-    }
-    if (s->dp_on) {  // the depth feed's own history
-      if (sid >= s->dp_owner.size()) s->dp_owner.resize((size_t)sid + 1);
-      auto& h = s->dp_owner[sid];
-      if (h.empty() || h.back().second != sl.meta[i].symbol) h.emplace_back(k, sl.meta[i].symbol);
-    }
-    if (s->tr_on) {  // and the trade feed's
-      if (sid >= s->tr_owner.size()) s->tr_owner.resize((size_t)sid + 1);
-      auto& h = s->tr_owner[sid];
-      if (h.empty() || h.back().second != sl.meta[i].symbol) h.emplace_back(k, sl.meta[i].symbol);
-    }
+    if (sl.sid[i] == kNoBook) continue;
+    each_feed(s, [&](auto& f, auto) {
+      if (f.on) f.note(sl.sid[i], k, sl.meta[i].symbol);
+    });
   }
 }
 
-// (md_mu held) `name`'s view changed: it gets its place in the queue unless it has one
-static void dp_mark(me_service* s, const std::string& name) {
-  if (s->dp_at.count(name)) return;
-  s->dp_q.push_back(name);
-  s->dp_at.emplace(name, std::prev(s->dp_q.end()));
-}
-
-// Read the engine's depth events and apply them to the views (eng_mu held). Naming as in md_pull, by the
-// depth feed's own history. A book changes hands only when it is empty: the symbol that loses it ends
-// with an empty view, whatever the conflated events said.
-static int dp_pull(me_service* s) {
-  std::vector<me_depth_event> buf(4096);
+// Read a feed's events from the backend, `room` at a time, until none is left (eng_mu held). An event is
+// named by the symbol that owned its book at slice `batches` (a book no slice ever named: skipped) and
+// applied under md_mu: apply(event, name); popped(name) for each owner its stamp has passed.
+template <class Ev, class Feed, class Popped, class Apply>
+static int feed_pull(me_service* s, Feed& f, int (*read)(void*, Ev*, size_t, size_t*, size_t*), size_t room,
+                     const char* read_failed, Popped&& popped, Apply&& apply) {
+  std::vector<Ev> buf(room);
   for (;;) {
     size_t n = 0, left = 0;
-    const int rc = s->eng ? me_depth_read(s->eng, buf.data(), buf.size(), &n, &left)
-                          : s->m.depth(s->m.ctx, buf.data(), buf.size(), &n, &left);
-    if (rc != ME_OK) return s->fail(rc, "depth stream: reading the backend's depth feed failed: " + backend_err(s));
+    const int rc = read(s->be.ctx, buf.data(), buf.size(), &n, &left);
+    if (rc != ME_OK) return s->fail(rc, read_failed + backend_err(s));
     std::lock_guard<std::mutex> lm(s->md_mu);
-    for (size_t i = 0; i < n; ++i) {
-      const me_depth_event& ev = buf[i];
-      if (ev.symbol >= s->dp_owner.size() || s->dp_owner[ev.symbol].empty()) continue;  // (a book no slice ever named)
-      auto& h = s->dp_owner[ev.symbol];
-      const size_t name_max = sizeof(((me_depth_book*)nullptr)->symbol) - 1;  // views are keyed as handed out
-      while (h.size() > 1 && h[1].first <= ev.batches) {
-        auto old = s->dp_view.find(h.front().second.substr(0, name_max));
+    for (size_t i = 0; i < n; ++i)
+      if (const std::string* name = f.owner_at(buf[i].symbol, buf[i].batches, popped)) apply(buf[i], *name);
+    if (!left) return ME_OK;
+  }
+}
+
+// Depth events set or erase a level of the name's view and queue the name. A book changes hands only when
+// it is empty: the symbol that loses it ends with an empty view, whatever the conflated events said.
+static int dp_pull(me_service* s) {
+  auto& f = s->dp;
+  return feed_pull<me_depth_event>(
+      s, f, s->be.depth, 4096, "depth stream: reading the backend's depth feed failed: ",
+      [&](const std::string& old_name) {
+        auto old = s->dp_view.find(f.key_of(old_name));
         if (old != s->dp_view.end() && (!old->second.side[0].empty() || !old->second.side[1].empty())) {
           old->second.side[0].clear();
           old->second.side[1].clear();
-          dp_mark(s, old->first);
+          f.pending(old->first);
         }
-        h.pop_front();
-      }
-      const std::string name = h.front().second.substr(0, name_max);
-      auto& side = s->dp_view[name].side[ev.side == ME_SIDE_SELL ? 1 : 0];
-      if (ev.qty > 0)
-        side[ev.price_q4] = ev.qty;
-      else
-        side.erase(ev.price_q4);
-      dp_mark(s, name);
-    }
-    if (!left) return ME_OK;
-  }
+      },
+      [&](const me_depth_event& ev, const std::string& name) {
+        auto& side = s->dp_view[f.key_of(name)].side[ev.side == ME_SIDE_SELL ? 1 : 0];  // views are keyed as handed out
+        if (ev.qty > 0)
+          side[ev.price_q4] = ev.qty;
+        else
+          side.erase(ev.price_q4);
+        f.pending(name);
+      });
 }
 
-// Read the backend's quote events and queue them, conflated (eng_mu held). An event is named by the symbol
-// that owned its book at slice `batches`; stamps never decrease, so older owners are dropped on the way.
+// Quote events conflate: the newer update replaces the name's pending one, in its place.
 static int md_pull(me_service* s) {
-  std::vector<me_quote> buf(1024);
   auto sat = [](int64_t v) { return (int32_t)(v > INT32_MAX ? INT32_MAX : v); };
-  for (;;) {
-    size_t n = 0, left = 0;
-    const int rc = s->eng ? me_quotes_read(s->eng, buf.data(), buf.size(), &n, &left)
-                          : s->m.quotes(s->m.ctx, buf.data(), buf.size(), &n, &left);
-    if (rc != ME_OK) return s->fail(rc, "market stream: reading the backend's quote feed failed: " + backend_err(s));
-    std::lock_guard<std::mutex> lm(s->md_mu);
-    for (size_t i = 0; i < n; ++i) {
-      const me_quote& q = buf[i];
-      if (q.symbol >= s->md_owner.size() || s->md_owner[q.symbol].empty()) continue;  // (a book no slice ever named)
-      auto& h = s->md_owner[q.symbol];
-      while (h.size() > 1 && h[1].first <= q.batches) h.pop_front();
-      const std::string& name = h.front().second;
-      me_market_update u;
-      memset(&u, 0, sizeof u);
-      put(u.symbol, sizeof u.symbol, name);
-      u.md.scale = 4;
-      if (q.flags & ME_QUOTE_HAS_BID) {
-        u.md.has_bid = 1;
-        u.md.best_bid = q.bid_price_q4;
-        u.md.bid_size = sat(q.bid_qty);
-      }
-      if (q.flags & ME_QUOTE_HAS_ASK) {
-        u.md.has_ask = 1;
-        u.md.best_ask = q.ask_price_q4;
-        u.md.ask_size = sat(q.ask_qty);
-      }
-      const std::string key = u.symbol;  // (the name as the update carries it)
-      auto it = s->md_at.find(key);
-      if (it != s->md_at.end()) {
-        *it->second = u;  // newer payload, same place
-      } else {
-        s->md_q.push_back(u);
-        s->md_at.emplace(key, std::prev(s->md_q.end()));
-      }
-    }
-    if (!left) return ME_OK;
-  }
+  return feed_pull<me_quote>(
+      s, s->md, s->be.quotes, 1024, "market stream: reading the backend's quote feed failed: ",
+      [](const std::string&) {},
+      [&](const me_quote& q, const std::string& name) {
+        me_market_update u;
+        memset(&u, 0, sizeof u);
+        put(u.symbol, sizeof u.symbol, name);
+        u.md.scale = 4;
+        if (q.flags & ME_QUOTE_HAS_BID) {
+          u.md.has_bid = 1;
+          u.md.best_bid = q.bid_price_q4;
+          u.md.bid_size = sat(q.bid_qty);
+        }
+        if (q.flags & ME_QUOTE_HAS_ASK) {
+          u.md.has_ask = 1;
+          u.md.best_ask = q.ask_price_q4;
+          u.md.ask_size = sat(q.ask_qty);
+        }
+        s->md.pending(name) = u;
+      });
 }
 
-// Read the engine's trade events and queue them, merged per symbol name (eng_mu held). Naming as in md_pull,
-// by the trade feed's own history; the names' totals are summed from the events' own volume and trades (a
-// reused book's device counters span two names).
+// Trade events merge into the name's pending update; the names' totals are summed from the events' own
+// volume and trades (a reused book's device counters span two names).
 static int tr_pull(me_service* s) {
-  std::vector<me_trade> buf(1024);
-  for (;;) {
-    size_t n = 0, left = 0;
-    const int rc = s->eng ? me_trades_read(s->eng, buf.data(), buf.size(), &n, &left)
-                          : s->m.trades(s->m.ctx, buf.data(), buf.size(), &n, &left);
-    if (rc != ME_OK) return s->fail(rc, "trade stream: reading the backend's trade feed failed: " + backend_err(s));
-    std::lock_guard<std::mutex> lm(s->md_mu);
-    for (size_t i = 0; i < n; ++i) {
-      const me_trade& ev = buf[i];
-      if (ev.symbol >= s->tr_owner.size() || s->tr_owner[ev.symbol].empty()) continue;  // (a book no slice ever named)
-      auto& h = s->tr_owner[ev.symbol];
-      while (h.size() > 1 && h[1].first <= ev.batches) h.pop_front();
-      me_trade_update u;
-      memset(&u, 0, sizeof u);
-      put(u.symbol, sizeof u.symbol, h.front().second);
-      const std::string key = u.symbol;  // (the name as the update carries it)
-      auto& cum = s->tr_cum[key];
-      cum.first += ev.volume;
-      cum.second += ev.trades;
-      u.scale = 4;
-      u.last_size = ev.last_qty;
-      u.last_price = ev.last_price_q4;
-      u.open_price = ev.open_price_q4;
-      u.high_price = ev.high_price_q4;
-      u.low_price = ev.low_price_q4;
-      u.volume = ev.volume;
-      u.trades = ev.trades;
-      u.cum_volume = cum.first;
-      u.cum_trades = cum.second;
-      auto it = s->tr_at.find(key);
-      if (it != s->tr_at.end()) {  // merge into the pending update, which keeps its place
-        const me_trade_update& p = *it->second;
-        u.open_price = p.open_price;
-        u.high_price = std::max(u.high_price, p.high_price);
-        u.low_price = std::min(u.low_price, p.low_price);
-        u.volume += p.volume;
-        u.trades += p.trades;
-        *it->second = u;
-      } else {
-        s->tr_q.push_back(u);
-        s->tr_at.emplace(key, std::prev(s->tr_q.end()));
-      }
-    }
-    if (!left) return ME_OK;
-  }
+  return feed_pull<me_trade>(
+      s, s->tr, s->be.trades, 1024, "trade stream: reading the backend's trade feed failed: ",
+      [](const std::string&) {},
+      [&](const me_trade& ev, const std::string& name) {
+        me_trade_update u;
+        memset(&u, 0, sizeof u);
+        put(u.symbol, sizeof u.symbol, name);
+        auto& cum = s->tr_cum[u.symbol];  // (the name as the update carries it)
+        cum.first += ev.volume;
+        cum.second += ev.trades;
+        u.scale = 4;
+        u.last_size = ev.last_qty;
+        u.last_price = ev.last_price_q4;
+        u.open_price = ev.open_price_q4;
+        u.high_price = ev.high_price_q4;
+        u.low_price = ev.low_price_q4;
+        u.volume = ev.volume;
+        u.trades = ev.trades;
+        u.cum_volume = cum.first;
+        u.cum_trades = cum.second;
+        bool fresh = false;
+        me_trade_update& p = s->tr.pending(name, &fresh);
+        if (!fresh) {  // merge into the pending update, which keeps its place
+          u.open_price = p.open_price;
+          u.high_price = std::max(u.high_price, p.high_price);
+          u.low_price = std::min(u.low_price, p.low_price);
+          u.volume += p.volume;
+          u.trades += p.trades;
+        }
+        p = u;
+      });
 }
 
 // Close the open slice (mu held).
@@ -1470,9 +1483,9 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
     {
       std::lock_guard<std::mutex> le(s->eng_mu);
       r = backend_collect(s, fl.front());
-      if (r == ME_OK && s->md_on) (void)md_pull(s);  // (a failed read is in last_error; the slice is matched)
-      if (r == ME_OK && s->dp_on) (void)dp_pull(s);
-      if (r == ME_OK && s->tr_on) (void)tr_pull(s);
+      each_feed(s, [&](auto& f, auto pull) {
+        if (r == ME_OK && f.on) (void)pull(s);  // (a failed read is in last_error; the slice is matched)
+      });
     }
     if (r != ME_OK) return lost(r, "engine lost an accepted slice: ");
     Inflight& f = fl.front();
@@ -1503,7 +1516,7 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
       r = backend_submit(s, f, accepted);
       if (accepted) {
         ++s->nsub;
-        if (s->md_on || s->dp_on || s->tr_on) md_note_owners(s, f.sl, s->nsub);
+        md_note_owners(s, f.sl, s->nsub);
       }
     }
     if (r != ME_OK && !accepted) {  // refused: the slices before it go first, then it is split
@@ -1517,7 +1530,7 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
       return lost(r, "engine lost an accepted slice: ");
     }
     fl.push_back(std::move(f));
-    if (fl.size() > 1 || !backend_async(s))
+    if (fl.size() > 1 || !s->be.submit)  // (a synchronous match: one slice in flight)
       if ((r = finish_oldest()) != ME_OK) return r;
     if (!fl.empty() && fl.back().sl.recovery)  // a recovery chunk is matched alone (load_resting)
       while (!fl.empty())
@@ -1555,8 +1568,7 @@ extern "C" int me_service_flush(me_service* s, me_fill* out_fills, size_t fills_
   // the caller's buffers are checked before anything is matched
   if ((out_results || out_seq) && total > results_cap)
     return s->fail(ME_E_INVALID, "results_cap smaller than the pending records");
-  const uint64_t bound = s->eng ? me_fill_bound(s->eng, total) : s->m.max_resting + 2 * (uint64_t)total;
-  if (out_fills && has_backend(s) && fills_cap < bound)
+  if (out_fills && has_backend(s) && fills_cap < s->be.fill_bound(s->be, total))
     return s->fail(ME_E_INVALID, "fills_cap smaller than me_fill_bound(pending records)");
   FlushOut out;
   out.fills = out_fills;
@@ -1608,12 +1620,7 @@ extern "C" int me_service_start(me_service* s, uint32_t interval_us, uint32_t sl
   if (!s || !has_backend(s)) return ME_E_STATE;
   std::lock_guard<std::mutex> lk(s->mu);
   if (s->flusher.joinable()) return s->fail(ME_E_STATE, "flusher already running");
-  uint32_t mb = s->m.max_batch;
-  if (s->eng) {
-    me_config c{};
-    me_get_config(s->eng, &c);
-    mb = c.max_batch;
-  }
+  const uint32_t mb = s->be.max_batch;  // (not the current slice_max, which this call replaces)
   s->slice_max = slice_orders && slice_orders < mb ? slice_orders : mb;
   s->interval_us = interval_us ? interval_us : 1000;
   s->stop = false;
@@ -1645,10 +1652,12 @@ extern "C" void me_service_destroy(me_service* s) {
     s->pq_cv.notify_all();
   }
   if (s->persister.joinable()) s->persister.join();
-  if (!s->eng) {  // a matcher outlives its service: the feeds this service turned on go off with it
+  // A matcher outlives its service: the depth and trade feeds this service turned on go off with it. (An
+  // engine's feeds are left on, quotes included. That looks accidental; it is what the service has always done.)
+  if (s->be.feeds_off_at_destroy) {
     std::lock_guard<std::mutex> le(s->eng_mu);
-    if (s->dp_on && s->m.depth_enable) (void)s->m.depth_enable(s->m.ctx, 0, 0);
-    if (s->tr_on && s->m.trades_enable) (void)s->m.trades_enable(s->m.ctx, 0);
+    if (s->dp.on && s->be.depth_enable) (void)s->be.depth_enable(s->be.ctx, 0, 0);
+    if (s->tr.on && s->be.trades_enable) (void)s->be.trades_enable(s->be.ctx, 0);
   }
   close_db(s);
   delete s;
@@ -1668,8 +1677,8 @@ extern "C" int me_service_book(me_service* s, const char* symbol, me_level* bids
   }
   if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
   std::lock_guard<std::mutex> le(s->eng_mu);
-  const int rc = backend_book(s, sid, (uint32_t)std::min<size_t>(depth, 0xFFFFFFFFu), nullptr, 0, nullptr, nullptr,
-                              0, nullptr, bids, asks, n_bids, n_asks);
+  const int rc = s->be.book(s->be.ctx, sid, (uint32_t)std::min<size_t>(depth, 0xFFFFFFFFu), nullptr, 0, nullptr,
+                            nullptr, 0, nullptr, bids, asks, n_bids, n_asks);
   if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
   return ME_OK;
 }
@@ -1693,9 +1702,9 @@ extern "C" int me_service_order_book(me_service* s, const char* symbol, uint32_t
     std::lock_guard<std::mutex> le(s->eng_mu);
     side[0].resize(std::max<size_t>(bids_cap, 1));
     side[1].resize(std::max<size_t>(asks_cap, 1));
-    const int rc = backend_book(s, sid, depth, bids ? side[0].data() : nullptr, bids ? side[0].size() : 0, &n[0],
-                                asks ? side[1].data() : nullptr, asks ? side[1].size() : 0, &n[1], nullptr, nullptr,
-                                nullptr, nullptr);
+    const int rc = s->be.book(s->be.ctx, sid, depth, bids ? side[0].data() : nullptr, bids ? side[0].size() : 0,
+                              &n[0], asks ? side[1].data() : nullptr, asks ? side[1].size() : 0, &n[1], nullptr,
+                              nullptr, nullptr, nullptr);
     if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
   }
   me_book_order* out[2] = {bids, asks};
@@ -1730,7 +1739,7 @@ extern "C" int me_service_order_status(me_service* s, const char* client_id, con
   if (n > ((size_t)1 << 24)) return s->fail(ME_E_INVALID, "order status: more than 2^24 ids");
   if (n && (!order_ids || !out)) return s->fail(ME_E_INVALID, "order status: null order_ids or out");
   if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
-  if (!s->eng && !s->m.order_query) return s->fail(ME_E_INVALID, "order status: the backend has no order query");
+  if (!s->be.order_query) return s->fail(ME_E_INVALID, "order status: the backend has no order query");
   if (!n) return ME_OK;
   const std::string client = client_id ? client_id : "";
   std::vector<uint64_t> seqs(n);
@@ -1738,8 +1747,7 @@ extern "C" int me_service_order_status(me_service* s, const char* client_id, con
   std::vector<me_order_info> info(n);
   {
     std::lock_guard<std::mutex> le(s->eng_mu);
-    const int rc = s->eng ? me_order_query(s->eng, seqs.data(), n, info.data())
-                          : s->m.order_query(s->m.ctx, seqs.data(), n, info.data());
+    const int rc = s->be.order_query(s->be.ctx, seqs.data(), n, info.data());
     if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
   }
   std::lock_guard<std::mutex> lv(s->live_mu);
@@ -1778,7 +1786,7 @@ extern "C" int me_service_preview_order(me_service* s, const me_order_request* r
   if (!s) return ME_E_INVALID;
   if (!r || !out) return s->fail(ME_E_INVALID, "order preview: null request or out");
   if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
-  if (!s->eng && !s->m.order_preview) return s->fail(ME_E_INVALID, "order preview: the backend has no order preview");
+  if (!s->be.order_preview) return s->fail(ME_E_INVALID, "order preview: the backend has no order preview");
   const char* symbol = r->symbol ? r->symbol : "";
   if (!symbol[0]) return s->fail(ME_E_INVALID, "symbol is required");
   if (r->quantity <= 0) return s->fail(ME_E_INVALID, "quantity must be > 0");
@@ -1813,7 +1821,7 @@ extern "C" int me_service_preview_order(me_service* s, const me_order_request* r
   q.symbol = &sid;
   q.kind = &kd;
   std::lock_guard<std::mutex> le(s->eng_mu);
-  const int rc = s->eng ? me_order_preview(s->eng, &q, 1, out) : s->m.order_preview(s->m.ctx, &q, 1, out);
+  const int rc = s->be.order_preview(s->be.ctx, &q, 1, out);
   if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
   return ME_OK;
 }
@@ -1827,7 +1835,7 @@ extern "C" int me_service_mass_cancel(me_service* s, const char* const* symbols,
   if (n_cancelled) *n_cancelled = 0;
   if (!s) return ME_E_INVALID;
   if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
-  if (!s->eng) return s->fail(ME_E_INVALID, "mass cancel: the backend has no mass cancel");
+  if (!s->be.mass_cancel) return s->fail(ME_E_INVALID, "mass cancel: the backend has no mass cancel");
   if (sides < 1 || sides > 3) return s->fail(ME_E_INVALID, "mass cancel: sides must be 1 (buy), 2 (sell) or 3 (both)");
   std::lock_guard<std::mutex> lf(s->flush_mu);
   std::vector<uint32_t> sids;
@@ -1866,15 +1874,16 @@ extern "C" int me_service_mass_cancel(me_service* s, const char* const* symbols,
   {
     std::lock_guard<std::mutex> le(s->eng_mu);
     size_t need = 0;
-    rc = me_mass_cancel(s->eng, sids.data(), sd.data(), sids.size(), nullptr, 0, &need, counts.data());
+    rc = s->be.mass_cancel(s->be.ctx, sids.data(), sd.data(), sids.size(), nullptr, 0, &need, counts.data());
     if (rc == ME_E_CAPACITY && need) {  // sized from *n_out (nothing can rest in between: eng_mu is held)
       ent.resize(need);
-      rc = me_mass_cancel(s->eng, sids.data(), sd.data(), sids.size(), ent.data(), ent.size(), &need, counts.data());
+      rc = s->be.mass_cancel(s->be.ctx, sids.data(), sd.data(), sids.size(), ent.data(), ent.size(), &need,
+                             counts.data());
     }
     if (rc != ME_OK) return s->fail(rc, "engine: " + backend_err(s));
     ent.resize(need);
-    if (s->md_on) (void)md_pull(s);  // the purge's feed events carry the last slice's stamp
-    if (s->dp_on) (void)dp_pull(s);
+    if (s->md.on) (void)md_pull(s);  // the purge's feed events carry the last slice's stamp
+    if (s->dp.on) (void)dp_pull(s);
   }
   if (n_cancelled) *n_cancelled = ent.size();
   if (ent.empty()) return ME_OK;
@@ -1930,38 +1939,42 @@ extern "C" int me_service_market_data(me_service* s, const char* symbol, me_mark
   return ME_OK;
 }
 
-extern "C" int me_service_market_subscribe(me_service* s, int on) {
-  if (!s) return ME_E_INVALID;
+// What the three subscribe calls share. Off: the backend's feed goes off if it was on, and the feed's state
+// is dropped. On: `refuse` (a message, when the backend lacks the feed or the request is out of range) answers
+// ME_E_INVALID; enable(cap_events) turns the backend's feed on (with 0: off); the feed starts empty with the
+// current names owning their books; `first_pull` (or NULL) then reads the books as they stand. also_reset()
+// clears what the stream keeps beside the feed, under the same md_mu.
+template <class Feed, class Enable, class AlsoReset>
+static int feed_subscribe(me_service* s, Feed& f, bool on, const char* refuse, uint64_t cap_events, Enable&& enable,
+                          const char* enable_failed, AlsoReset&& also_reset, int (*first_pull)(me_service*)) {
   std::lock_guard<std::mutex> lf(s->flush_mu);  // no slice is in flight while it is held
   std::lock_guard<std::mutex> le(s->eng_mu);
-  if (!on) {
-    if (s->md_on && s->eng) me_quotes_enable(s->eng, 0);
-    std::lock_guard<std::mutex> lm(s->md_mu);
-    s->md_on = false;
-    s->md_q.clear();
-    s->md_at.clear();
-    s->md_owner.clear();
-    return ME_OK;
-  }
-  if (!s->eng && !s->m.quotes) return s->fail(ME_E_INVALID, "market stream: the backend has no quote feed");
-  if (s->eng) {
-    const int rc = me_quotes_enable(s->eng, std::max<uint64_t>(4ull * s->sym_cap, 1024));
-    if (rc != ME_OK) return s->fail(rc, "market stream: me_quotes_enable failed: " + backend_err(s));
-  }
   std::vector<std::string> names;
-  {
+  if (on) {
+    if (refuse) return s->fail(ME_E_INVALID, refuse);
+    const int rc = enable(cap_events);
+    if (rc != ME_OK) return s->fail(rc, enable_failed + backend_err(s));
     std::lock_guard<std::mutex> lk(s->mu);
     names = s->names;
+  } else if (f.on) {
+    (void)enable(0);
   }
   {
     std::lock_guard<std::mutex> lm(s->md_mu);
-    s->md_q.clear();
-    s->md_at.clear();
-    s->md_owner.assign(names.size(), {});
-    for (size_t i = 0; i < names.size(); ++i) s->md_owner[i].emplace_back(0, names[i]);
-    s->md_on = true;
+    f.reset(on, on ? &names : nullptr);
+    also_reset();
   }
-  return md_pull(s);  // the books as they stand
+  return on && first_pull ? first_pull(s) : ME_OK;
+}
+
+extern "C" int me_service_market_subscribe(me_service* s, int on) {
+  if (!s) return ME_E_INVALID;
+  const Backend& be = s->be;
+  return feed_subscribe(
+      s, s->md, on != 0, be.quotes ? nullptr : "market stream: the backend has no quote feed",
+      std::max<uint64_t>(4ull * be.num_symbols, 1024),
+      [&](uint64_t cap) { return be.quotes_enable ? be.quotes_enable(be.ctx, cap) : (int)ME_OK; },
+      "market stream: me_quotes_enable failed: ", [] {}, md_pull);
 }
 
 extern "C" int me_service_market_stream(me_service* s, const char* symbol, me_market_update* out, size_t cap,
@@ -1969,72 +1982,33 @@ extern "C" int me_service_market_stream(me_service* s, const char* symbol, me_ma
   if (n) *n = 0;
   if (!s || (cap && !out)) return ME_E_INVALID;
   std::lock_guard<std::mutex> lm(s->md_mu);
-  if (!s->md_on) return s->fail(ME_E_INVALID, "market stream: not subscribed (me_service_market_subscribe)");
-  size_t k = 0;
-  if (symbol && *symbol) {
-    auto it = s->md_at.find(std::string(symbol).substr(0, sizeof(out->symbol) - 1));
-    if (it != s->md_at.end() && cap) {
-      out[k++] = *it->second;
-      s->md_q.erase(it->second);
-      s->md_at.erase(it);
-    }
-  } else {
-    while (k < cap && !s->md_q.empty()) {
-      out[k++] = s->md_q.front();
-      s->md_at.erase(s->md_q.front().symbol);
-      s->md_q.pop_front();
-    }
-  }
+  if (!s->md.on) return s->fail(ME_E_INVALID, "market stream: not subscribed (me_service_market_subscribe)");
+  const size_t k = s->md.take(symbol, cap, [&](const std::string&, const me_market_update& u) { *out++ = u; });
   if (n) *n = k;
   return ME_OK;
 }
 
 extern "C" int me_service_depth_subscribe(me_service* s, uint32_t depth) {
   if (!s) return ME_E_INVALID;
-  std::lock_guard<std::mutex> lf(s->flush_mu);  // no slice is in flight while it is held
-  std::lock_guard<std::mutex> le(s->eng_mu);
-  auto reset = [&](bool on, uint32_t d) {
-    s->dp_on = on;
-    s->dp_depth = d;
-    s->dp_view.clear();
-    s->dp_q.clear();
-    s->dp_at.clear();
-    s->dp_owner.clear();
-  };
-  if (!depth) {
-    if (s->dp_on && s->eng) me_depth_enable(s->eng, 0, 0);
-    if (s->dp_on && !s->eng && s->m.depth_enable) s->m.depth_enable(s->m.ctx, 0, 0);
-    std::lock_guard<std::mutex> lm(s->md_mu);
-    reset(false, 0);
-    return ME_OK;
-  }
-  if (!s->eng && !(s->m.depth_enable && s->m.depth)) return s->fail(ME_E_INVALID, "depth stream: the matcher has no depth feed");
-  if (depth > ME_DEPTH_MAX) return s->fail(ME_E_INVALID, "depth stream: depth above ME_DEPTH_MAX");
-  // room for four jobs in which every level of every view changes
-  const uint64_t cap_ev = std::max<uint64_t>(16ull * depth * s->sym_cap, 4096);
-  const int rc = s->eng ? me_depth_enable(s->eng, depth, cap_ev) : s->m.depth_enable(s->m.ctx, depth, cap_ev);
-  if (rc != ME_OK) return s->fail(rc, "depth stream: me_depth_enable failed: " + backend_err(s));
-  std::vector<std::string> names;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    names = s->names;
-  }
-  {
-    std::lock_guard<std::mutex> lm(s->md_mu);
-    reset(true, depth);
-    s->dp_owner.assign(names.size(), {});
-    for (size_t i = 0; i < names.size(); ++i) s->dp_owner[i].emplace_back(0, names[i]);
-  }
-  return dp_pull(s);  // the books as they stand
+  const Backend& be = s->be;
+  const char* refuse = !(be.depth_enable && be.depth) ? "depth stream: the matcher has no depth feed"
+                       : depth > ME_DEPTH_MAX         ? "depth stream: depth above ME_DEPTH_MAX"
+                                                      : nullptr;
+  // room for four jobs in which every level of every view changes (off: depth 0, no events)
+  return feed_subscribe(
+      s, s->dp, depth != 0, refuse, std::max<uint64_t>(16ull * depth * be.num_symbols, 4096),
+      [&](uint64_t cap) { return be.depth_enable(be.ctx, depth, cap); }, "depth stream: me_depth_enable failed: ",
+      [&] { s->dp_view.clear(); }, dp_pull);
 }
 
 extern "C" int me_service_depth_stream(me_service* s, const char* symbol, me_depth_book* out, size_t cap, size_t* n) {
   if (n) *n = 0;
   if (!s || (cap && !out)) return ME_E_INVALID;
   std::lock_guard<std::mutex> lm(s->md_mu);
-  if (!s->dp_on) return s->fail(ME_E_INVALID, "depth stream: not subscribed (me_service_depth_subscribe)");
+  if (!s->dp.on) return s->fail(ME_E_INVALID, "depth stream: not subscribed (me_service_depth_subscribe)");
   auto sat = [](int64_t v) { return (int32_t)(v > INT32_MAX ? INT32_MAX : v); };
-  auto fill = [&](const std::string& name, me_depth_book& b) {  // the symbol's whole current view, best first
+  auto fill = [&](const std::string& name, me_service::Changed) {  // the symbol's whole current view, best first
+    me_depth_book& b = *out++;
     memset(&b, 0, sizeof b);
     put(b.symbol, sizeof b.symbol, name);
     b.scale = 4;
@@ -2050,80 +2024,27 @@ extern "C" int me_service_depth_stream(me_service* s, const char* symbol, me_dep
     }
     if (!b.n_bids && !b.n_asks) s->dp_view.erase(v);  // (an emptied book is handed out once, then forgotten)
   };
-  size_t k = 0;
-  if (symbol && *symbol) {
-    auto it = s->dp_at.find(std::string(symbol).substr(0, sizeof(out->symbol) - 1));
-    if (it != s->dp_at.end() && cap) {
-      fill(it->first, out[k++]);
-      s->dp_q.erase(it->second);
-      s->dp_at.erase(it);
-    }
-  } else {
-    while (k < cap && !s->dp_q.empty()) {
-      fill(s->dp_q.front(), out[k++]);
-      s->dp_at.erase(s->dp_q.front());
-      s->dp_q.pop_front();
-    }
-  }
+  const size_t k = s->dp.take(symbol, cap, fill);
   if (n) *n = k;
   return ME_OK;
 }
 
 extern "C" int me_service_trades_subscribe(me_service* s, int on) {
   if (!s) return ME_E_INVALID;
-  std::lock_guard<std::mutex> lf(s->flush_mu);  // no slice is in flight while it is held
-  std::lock_guard<std::mutex> le(s->eng_mu);
-  auto reset = [&](bool v) {
-    s->tr_on = v;
-    s->tr_q.clear();
-    s->tr_at.clear();
-    s->tr_cum.clear();
-    s->tr_owner.clear();
-  };
-  if (!on) {
-    if (s->tr_on && s->eng) me_trades_enable(s->eng, 0);
-    if (s->tr_on && !s->eng && s->m.trades_enable) s->m.trades_enable(s->m.ctx, 0);
-    std::lock_guard<std::mutex> lm(s->md_mu);
-    reset(false);
-    return ME_OK;
-  }
-  if (!s->eng && !(s->m.trades_enable && s->m.trades)) return s->fail(ME_E_INVALID, "trade stream: the matcher has no trade feed");
-  // room for four jobs in which every symbol trades
-  const uint64_t cap_ev = std::max<uint64_t>(4ull * s->sym_cap, 1024);
-  const int rc = s->eng ? me_trades_enable(s->eng, cap_ev) : s->m.trades_enable(s->m.ctx, cap_ev);
-  if (rc != ME_OK) return s->fail(rc, "trade stream: me_trades_enable failed: " + backend_err(s));
-  std::vector<std::string> names;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    names = s->names;
-  }
-  std::lock_guard<std::mutex> lm(s->md_mu);
-  reset(true);
-  s->tr_owner.assign(names.size(), {});
-  for (size_t i = 0; i < names.size(); ++i) s->tr_owner[i].emplace_back(0, names[i]);
-  return ME_OK;  // (no initial state: nothing to read yet)
+  const Backend& be = s->be;
+  // room for four jobs in which every symbol trades; no first pull: there is no initial state to read
+  return feed_subscribe(
+      s, s->tr, on != 0, be.trades_enable && be.trades ? nullptr : "trade stream: the matcher has no trade feed",
+      std::max<uint64_t>(4ull * be.num_symbols, 1024), [&](uint64_t cap) { return be.trades_enable(be.ctx, cap); },
+      "trade stream: me_trades_enable failed: ", [&] { s->tr_cum.clear(); }, nullptr);
 }
 
 extern "C" int me_service_trades_stream(me_service* s, const char* symbol, me_trade_update* out, size_t cap, size_t* n) {
   if (n) *n = 0;
   if (!s || (cap && !out)) return ME_E_INVALID;
   std::lock_guard<std::mutex> lm(s->md_mu);
-  if (!s->tr_on) return s->fail(ME_E_INVALID, "trade stream: not subscribed (me_service_trades_subscribe)");
-  size_t k = 0;
-  if (symbol && *symbol) {
-    auto it = s->tr_at.find(std::string(symbol).substr(0, sizeof(out->symbol) - 1));
-    if (it != s->tr_at.end() && cap) {
-      out[k++] = *it->second;
-      s->tr_q.erase(it->second);
-      s->tr_at.erase(it);
-    }
-  } else {
-    while (k < cap && !s->tr_q.empty()) {
-      out[k++] = s->tr_q.front();
-      s->tr_at.erase(s->tr_q.front().symbol);
-      s->tr_q.pop_front();
-    }
-  }
+  if (!s->tr.on) return s->fail(ME_E_INVALID, "trade stream: not subscribed (me_service_trades_subscribe)");
+  const size_t k = s->tr.take(symbol, cap, [&](const std::string&, const me_trade_update& u) { *out++ = u; });
   if (n) *n = k;
   return ME_OK;
 }
