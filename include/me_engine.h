@@ -579,6 +579,93 @@ int me_trades_read(me_engine* e, me_trade* out, size_t cap, size_t* n, size_t* l
  * may be NULL. ME_E_INVALID while the feed is off. */
 int me_trades_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* deferred);
 
+/* ---- stop and stop-limit orders: a trigger book on the device (no reference counterpart) --------------
+ * A STOP waits outside the book until its symbol trades through its stop price; it then leaves the trigger
+ * table and comes out as one me_stop_event, the NEW record it becomes (a MARKET: a stop; a LIMIT: a
+ * stop-limit) ready to be submitted. A stop never rests in a price level and no matching path knows it: the
+ * table is judged by a device job behind every match launch, like the feeds' jobs above.
+ *
+ * TRIGGER. A BUY stop triggers when a fill of its symbol has price_q4 >= stop_px_q4, a SELL stop when a fill
+ * has price_q4 <= stop_px_q4. The feed is conflated per launch group exactly like the trade feed: the job
+ * behind a match launch judges every live stop against its symbol's highest and lowest fill price of THAT
+ * launch; a symbol without a fill in the launch triggers nothing, whatever the stop price (INT64_MIN and
+ * INT64_MAX are stop prices like any other). Only fills of batches SUBMITTED AFTER THE ADD count:
+ * me_stops_add first enqueues everything already submitted (a partial group goes out as it is; nothing is
+ * waited for) and then copies the stops into the table in stream order. THERE IS NO "ALREADY THROUGH THE
+ * MARKET" CHECK: a stop whose price earlier trades have already passed waits for the next fill that
+ * satisfies it. A mass cancel produces no fills and triggers nothing; stops of a purged symbol stay until
+ * the caller cancels them.
+ *
+ * THE ENGINE DOES NOT INJECT THE ORDER. Seqs are the host's to allocate and must ascend, so the caller turns
+ * events into NEW records with fresh seqs in a later batch (kind, limit_px_q4, qty and symbol are the record's
+ * kind, price, quantity and symbol). A cascade — a triggered sell trades lower and triggers the next stop —
+ * therefore advances one job per step.
+ *
+ * Events of one job come in table order, which is ascending id (across symbols); jobs come in launch order.
+ * The event ring holds cap_stops events and never defers, by construction: me_stops_add keeps
+ * added - cancelled - events read + n <= cap_stops, so every live stop has a free slot waiting for its event.
+ * With the feature on, a job (its fold of the launch's fills included) is enqueued only while
+ * added - cancelled - events read > 0; an engine that never enables it launches exactly what it launched
+ * before. Job order with several feeds on: quote, depth, trade, stops; the other feeds' events, and every
+ * result, tape and book, are what they are without it.
+ * Out of scope here: the service RPC (me_stops_dump is its persistence hook), the cluster, trailing stops. */
+typedef struct me_stop { /* 40 B */
+  uint64_t id;          /* the caller's, non-zero, ascending over every add since me_stops_enable */
+  int64_t stop_px_q4;
+  int64_t limit_px_q4;  /* the price of the record it becomes; ignored for a MARKET and echoed as given */
+  int32_t qty;          /* > 0 */
+  uint32_t symbol;      /* LOCAL symbol id (< num_symbols), echoed as given */
+  uint8_t kind;         /* ME_KIND_TIF(side, type, ME_OP_NEW, tif) of the record it becomes */
+  uint8_t pad[7];       /* ignored; zero in dumps */
+} me_stop;
+typedef struct me_stop_event { /* 64 B */
+  uint64_t id;
+  int64_t stop_px_q4;
+  int64_t limit_px_q4;
+  int64_t trigger_px_q4; /* the launch's highest fill price of the symbol for a BUY stop, its lowest for a SELL */
+  uint64_t batches;      /* me_quote.batches' meaning */
+  int32_t qty;
+  uint32_t symbol;       /* the local id as given */
+  uint8_t kind;
+  uint8_t pad[15];       /* zero */
+} me_stop_event;
+/* cap_stops = 0 turns the feature off and drops everything (table, unread events, counts); else the most
+ * stops that may be live or triggered-and-unread at once: the table's and the event ring's size (48 B of HBM
+ * twice and 64 B of pinned host memory per stop). More than 2^22 is ME_E_INVALID. Enabling again starts
+ * afresh (ids may start over); a failing call leaves the feature off. No job runs at enable time. */
+int me_stops_enable(me_engine* e, uint64_t cap_stops);
+/* All or nothing, validated on the host before anything is enqueued. ME_E_INVALID, nothing added: stops
+ * NULL with n > 0; an id that is zero, not above the one before it in the call, or not above every id added
+ * since enable; symbol >= num_symbols; a side other than BUY / SELL; qty <= 0; the op bit (bit 3) set; MARKET
+ * together with POST_ONLY; the feature off. ME_E_CAPACITY, nothing added, NOT sticky (the engine stays
+ * usable): added - cancelled - events read + n > cap_stops; cancel stops or read events and try again.
+ * When the table's append end cannot take n more entries the call waits for the work in flight and compacts
+ * the table first (dead entries go, the order stays). The call returns once the copy into the table is done.
+ * n == 0: ME_OK. */
+int me_stops_add(me_engine* e, const me_stop* stops, size_t n);
+/* me_sync runs first, so a stop that the batches submitted so far trigger HAS triggered: it answers
+ * found[i] = 0 and its event is in the ring. found[i] = 1: the stop was live and is gone without an event.
+ * An id never added, already triggered or already cancelled answers 0. ids must be strictly ascending, else
+ * ME_E_INVALID and nothing changes (also: ids or found NULL with n > 0, n > 2^22, the feature off). One
+ * launch, one lane per id (k_stop_cancel: a binary search over the table, which ascends by id). */
+int me_stops_cancel(me_engine* e, const uint64_t* ids, size_t n, uint8_t* found);
+/* me_trades_read's contract without the catch-up clause (there is no deferral to catch up on): at most `cap`
+ * events in order (out may be NULL when cap is 0); *n = events copied, *left = events logged and still
+ * unread; launches no partial group, drains nothing and waits for no job in flight. After me_collect(t)
+ * returned, every event with batches <= t's ordinal is there; after me_sync, every event. *n and *left are
+ * written on every return. ME_E_INVALID while the feature is off. */
+int me_stops_read(me_engine* e, me_stop_event* out, size_t cap, size_t* n, size_t* left);
+/* jobs run and events logged since enable, as of the work the device has finished, and live = added -
+ * cancelled - events (all three exact after me_sync). Any pointer may be NULL. ME_E_INVALID while the
+ * feature is off; ME_E_STATE "stop job deferred" should a job ever have found the ring full (the bound above
+ * broken: not reachable). */
+int me_stops_stats(me_engine* e, uint64_t* jobs, uint64_t* events, uint64_t* live);
+/* The live stops in table order (ascending id) after me_sync: what a caller persists. *n is exact even when
+ * cap is short (entries past it are not written; out may be NULL when cap is 0). The pass is the table's
+ * compaction. ME_E_INVALID while the feature is off. */
+int me_stops_dump(me_engine* e, me_stop* out, size_t cap, size_t* n);
+/* Every me_stops_* call: argument checks come first; a failed engine then answers what me_sync answers. */
+
 /* Kernel timing. period >= 1: every period-th match-kernel launch records its own start and end
  * (hipExtLaunchKernelGGL events: no marker packets, though each timed launch still costs the
  * stream a few microseconds, hence the sampling); period <= 0: off. Resets the counters below. */

@@ -133,6 +133,17 @@ TRADE_DTYPE = np.dtype(
      ("cum_trades", "<u8"), ("batches", "<u8"), ("last_qty", "<i4"), ("symbol", "<u4")]
 )
 assert TRADE_DTYPE.itemsize == 96
+# me_stop: one stop / stop-limit order of the trigger book; me_stop_event: a triggered one, the NEW record it becomes
+STOP_DTYPE = np.dtype(
+    [("id", "<u8"), ("stop_px_q4", "<i8"), ("limit_px_q4", "<i8"), ("qty", "<i4"), ("symbol", "<u4"), ("kind", "u1"),
+     ("pad", "u1", (7,))]
+)
+STOP_EVENT_DTYPE = np.dtype(
+    [("id", "<u8"), ("stop_px_q4", "<i8"), ("limit_px_q4", "<i8"), ("trigger_px_q4", "<i8"), ("batches", "<u8"),
+     ("qty", "<i4"), ("symbol", "<u4"), ("kind", "u1"), ("pad", "u1", (15,))]
+)
+STOPS_CAP_MAX = 1 << 22
+assert STOP_DTYPE.itemsize == 40 and STOP_EVENT_DTYPE.itemsize == 64
 # me_order_info: one answer of me_order_query (found 0: every field but seq is 0)
 ORDER_INFO_DTYPE = np.dtype(
     [("seq", "<u8"), ("price_q4", "<i8"), ("qty_ahead", "<i8"), ("level_qty", "<i8"), ("qty_better", "<i8"),
@@ -264,6 +275,12 @@ PROTOTYPES = {
     "me_trades_enable": (C.c_int, [_P, C.c_uint64]),
     "me_trades_read": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "me_trades_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "me_stops_enable": (C.c_int, [_P, C.c_uint64]),
+    "me_stops_add": (C.c_int, [_P, _P, _SZ]),
+    "me_stops_cancel": (C.c_int, [_P, _P, _SZ, _P]),
+    "me_stops_read": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "me_stops_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "me_stops_dump": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "me_gen_create": (_P, [C.POINTER(MeGenParams)]),
     "me_gen_destroy": (None, [_P]),
     "me_gen_base_prices": (C.c_int, [_P, _P]),

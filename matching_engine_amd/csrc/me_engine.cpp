@@ -21,6 +21,7 @@
 #include "me_feed.hpp"
 #include "me_launch.hpp"
 #include "me_layout.hpp"
+#include "me_stops.hpp"
 
 static_assert(me::ME_C == ME_CHUNK_SLOTS, "chunk width mismatch");
 static_assert(sizeof(me_fill) == 32, "me_fill must be 32 B");
@@ -321,6 +322,20 @@ struct me_engine {
   // trade feed (me_trades_*): the same, allocated by me_trades_enable
   Feed<me_trade> trades;
   TradeDev td{};
+  // trigger book (me_stops_*), allocated by me_stops_enable: the event ring, the table's two buffers (sk.sd.tab
+  // is the current one, sk.sd.top its append end) and what the host counts (me_stops.hpp)
+  Feed<me_stop_event> stops;
+  struct StopBook {
+    StopDev sd{};
+    StopEnt* tab[2] = {nullptr, nullptr};
+    int cur = 0;
+    uint64_t cap = 0;
+    StopCounts c;  // (c.read is kept in stops.ring.consumed)
+    uint32_t* d_count = nullptr;  // the compaction's live count
+    uint64_t* d_ids = nullptr;    // a cancel's ids and answers, grown on demand
+    uint8_t* d_found = nullptr;
+    size_t q_cap = 0;
+  } sk;
   uint64_t nmatched = 0;    // batches matched (enqueued match launches), host and device: the events' stamp
   uint32_t last_n = 0;
   uint32_t sq_idx = 0;  // seq-ring state the next k_seq_sweep reads (it writes the other one)
@@ -412,6 +427,14 @@ static void trades_free(me_engine* e) {
   e->trades.free();
 }
 
+static void stops_free(me_engine* e) {
+  void* dp[] = {e->sk.tab[0], e->sk.tab[1], e->sk.sd.jw, e->sk.sd.mask, e->sk.sd.woff, e->sk.d_count, e->sk.d_ids, e->sk.d_found};
+  for (void* p : dp)
+    if (p) (void)hipFree(p);
+  e->sk = me_engine::StopBook{};
+  e->stops.free();
+}
+
 // Up to `cap` logged events in order to `out`; *n and *left (either may be null) are kept current before
 // anything that can fail, so an error still tells the caller what it holds.
 template <class Ev>
@@ -460,6 +483,7 @@ static void free_all(me_engine* e) {
   quotes_free(e);
   depth_free(e);
   trades_free(e);
+  stops_free(e);
   void* ptrs[] = {e->bk.levels,   e->bk.occ,      e->bk.sym,      e->bk.chunks,     e->bk.tend,
                   e->bk.loc,      e->bk.chunk_top, e->bk.err,       (void*)e->bk.gsym,
                   e->d_tape,      e->d_tape_count, e->d_fills_acc, e->bk.dbg,      e->bk.fcache,
@@ -1088,13 +1112,9 @@ static int depth_job(me_engine* e) {
   return ME_OK;
 }
 
-// The trade feed's job, wherever depth_job runs and directly behind it: the fold of the fills of the match
-// launch just enqueued (its nb batches bt, in launch order; bucketed: a pipelined launch, whose run starts
-// are still in the results), then every symbol's pending summary against the log (me_snapshot.hip k_trade_fold / k_trade_scan / k_trade_emit). nb = 0 (enable, catch-up): no fold.
-static int trades_job(me_engine* e, const BatchDev* bt, uint32_t nb, bool bucketed) {
-  TradeDev t = e->td;
-  t.ring = e->trades.ring;
-  t.ring.batches = e->nmatched;
+// What k_trade_fold reads of the match launch just enqueued: its nb batches bt in launch order (bucketed: a
+// pipelined launch, whose run starts are still in the results). The trade feed's job and the trigger book's.
+static TradeLaunch fold_launch(const me_engine* e, const BatchDev* bt, uint32_t nb, bool bucketed) {
   TradeLaunch tl{};
   tl.nb = nb;
   tl.scratch_cap = e->scratch_cap;
@@ -1106,10 +1126,37 @@ static int trades_job(me_engine* e, const BatchDev* bt, uint32_t nb, bool bucket
     tl.b[g].n = bt[g].n;
     tl.nmax = std::max(tl.nmax, bt[g].n);
   }
-  HIP_TRY(launch_trades(e->stream, e->bk, t, tl), "trade feed launch");
+  return tl;
+}
+// The trade feed's job, wherever depth_job runs and directly behind it: the fold of the fills of the match
+// launch just enqueued (its nb batches bt, in launch order; bucketed: a pipelined launch, whose run starts
+// are still in the results), then every symbol's pending summary against the log (me_snapshot.hip k_trade_fold / k_trade_scan / k_trade_emit). nb = 0 (enable, catch-up): no fold.
+static int trades_job(me_engine* e, const BatchDev* bt, uint32_t nb, bool bucketed) {
+  TradeDev t = e->td;
+  t.ring = e->trades.ring;
+  t.ring.batches = e->nmatched;
+  HIP_TRY(launch_trades(e->stream, e->bk, t, fold_launch(e, bt, nb, bucketed)), "trade feed launch");
   return ME_OK;
 }
 static int trades_job_idle(me_engine* e) { return trades_job(e, nullptr, 0, false); }
+
+// The trigger book's counts as they stand (the events read live in the ring).
+static StopCounts stop_counts(const me_engine* e) {
+  StopCounts c = e->sk.c;
+  c.read = e->stops.ring.consumed;
+  return c;
+}
+// The trigger book's job, wherever trades_job runs and directly behind it, and only while a stop may be live
+// (known on the host: me_stops.hpp stops_pending): its own fold of the launch's fills, then every entry of
+// [0, top) against its symbol's high / low of this launch (me_snapshot.hip k_stop_scan / k_stop_emit).
+static int stops_job(me_engine* e, const BatchDev* bt, uint32_t nb, bool bucketed) {
+  if (!stops_pending(stop_counts(e))) return ME_OK;
+  StopDev sd = e->sk.sd;
+  sd.ring = e->stops.ring;
+  sd.ring.batches = e->nmatched;
+  HIP_TRY(launch_stops(e->stream, sd, fold_launch(e, bt, nb, bucketed)), "stop job launch");
+  return ME_OK;
+}
 
 // One launch of the pipelined register-ladder path: match group g_match (if any), bucket group nb
 // (if any) and clear the counters its batches will use, compact g_tape's tapes (if any) — then the
@@ -1211,6 +1258,10 @@ static int pipe_launch(me_engine* e, const me_engine::Group* nb) {
     }
     if (e->trades.on) {  // the group's fills: in scratch until its tape job, one launch on
       int rc = trades_job(e, bt, gm.n, true);
+      if (rc) return rc;
+    }
+    if (e->stops.on) {
+      int rc = stops_job(e, bt, gm.n, true);
       if (rc) return rc;
     }
   }
@@ -1363,6 +1414,10 @@ static int enqueue_batch(me_engine* e, const uint64_t* seq, const int64_t* px, c
   }
   if (e->trades.on) {
     rc = trades_job(e, &bt, 1u, false);
+    if (rc) return rc;
+  }
+  if (e->stops.on) {
+    rc = stops_job(e, &bt, 1u, false);
     if (rc) return rc;
   }
   if (slot >= 0) {
@@ -1963,6 +2018,166 @@ extern "C" int me_trades_stats(me_engine* e, uint64_t* groups, uint64_t* events,
   if (!e) return ME_E_INVALID;
   if (!e->trades.on) return e->fail(ME_E_INVALID, "the trade feed is off (me_trades_enable)");
   e->trades.stats(groups, events, deferred);
+  return ME_OK;
+}
+
+// ---- trigger book: stop and stop-limit orders (me_snapshot.hip k_stop_*; the host's arithmetic: me_stops.hpp)
+extern "C" int me_stops_enable(me_engine* e, uint64_t cap_stops) {
+  if (!e) return ME_E_INVALID;
+  const bool too_many = cap_stops > STOPS_CAP_MAX;
+  if (e->failed) return too_many ? e->fail(ME_E_INVALID, "me_stops_enable: cap_stops above 2^22") : ME_E_STATE;
+  HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
+  if (e->stops.on) {  // jobs in flight write the log and the table: wait for them before they go
+    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    stops_free(e);
+  }
+  if (too_many) return e->fail(ME_E_INVALID, "me_stops_enable: cap_stops above 2^22");  // (a failing call leaves it off)
+  if (!cap_stops) return ME_OK;
+  const uint64_t S = e->bk.S;
+  auto& k = e->sk;
+  const size_t nw = (size_t)((cap_stops + 63) / 64);
+  // the job words at their identities, as the trade feed's: {~0, 0, 0, ~0, 0, 0, -, -} per symbol
+  std::vector<unsigned long long> jw0(S * TJ_N, 0ull);
+  for (uint64_t s = 0; s < S; ++s) jw0[s * TJ_N + TJ_FIRST] = jw0[s * TJ_N + TJ_LOW] = ~0ull;
+  hipError_t he;
+  if ((he = dalloc(&k.tab[0], cap_stops)) != hipSuccess || (he = dalloc(&k.tab[1], cap_stops)) != hipSuccess ||
+      (he = dalloc(&k.sd.jw, S * TJ_N)) != hipSuccess || (he = dalloc(&k.sd.mask, nw)) != hipSuccess ||
+      (he = dalloc(&k.sd.woff, nw)) != hipSuccess || (he = dalloc(&k.d_count, 1)) != hipSuccess ||
+      (he = e->stops.alloc(e->stream, cap_stops)) != hipSuccess ||
+      (he = hipMemcpyAsync(k.sd.jw, jw0.data(), jw0.size() * sizeof jw0[0], hipMemcpyHostToDevice, e->stream)) != hipSuccess ||
+      (he = hipStreamSynchronize(e->stream)) != hipSuccess) {  // (jw0 is pageable and goes out of scope)
+    stops_free(e);
+    return e->hip_fail(he, "me_stops_enable");
+  }
+  k.cap = cap_stops;
+  k.sd.tab = k.tab[0];
+  k.sd.S = (uint32_t)S;
+  e->stops.on = true;
+  return ME_OK;
+}
+
+// The live entries into the table's other buffer, in order, which then becomes the table: top is the exact
+// live count afterwards. The caller has brought the stream to rest (no job in flight reads the old buffer).
+static int stops_compact(me_engine* e) {
+  auto& k = e->sk;
+  StopEnt* dst = k.tab[k.cur ^ 1];
+  HIP_TRY(launch_stop_compact(e->stream, k.sd, dst, k.d_count), "stop compaction launch");
+  uint32_t live = 0;
+  HIP_TRY(hipMemcpyAsync(&live, k.d_count, 4, hipMemcpyDeviceToHost, e->stream), "D2H live stops");
+  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+  if (live > k.sd.top) return e->fail(ME_E_STATE, "stop compaction: more live entries than entries");
+  k.cur ^= 1;
+  k.sd.tab = dst;
+  k.sd.top = live;
+  return ME_OK;
+}
+
+extern "C" int me_stops_add(me_engine* e, const me_stop* stops, size_t n) {
+  if (!e) return ME_E_INVALID;
+  if (!e->stops.on) return e->fail(ME_E_INVALID, "the trigger book is off (me_stops_enable)");
+  auto& k = e->sk;
+  if (const char* why = stops_validate(stops, n, e->bk.S, k.c.last_id))
+    return e->fail(ME_E_INVALID, std::string("me_stops_add: ") + why);
+  if (e->failed) return me_sync(e);
+  if (!n) return ME_OK;
+  const StopCounts c = stop_counts(e);
+  if (!stops_room(c, n, k.cap)) {  // not sticky (e->fail would make it so)
+    e->err = "stops refused: " + std::to_string(stops_pending(c)) + " live or unread + " + std::to_string(n) +
+             " would exceed cap_stops (" + std::to_string(k.cap) + "); nothing was added";
+    return ME_E_CAPACITY;
+  }
+  HIP_TRY(hipSetDevice(e->dev), "hipSetDevice");
+  // everything submitted so far goes out first: its jobs carry the table as it stands, without these stops
+  int rc = flush_pipeline(e);
+  if (rc) return rc;
+  if ((uint64_t)k.sd.top + n > k.cap) {  // the append end: drop the dead entries
+    HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    if ((rc = stops_compact(e))) return rc;
+    if ((uint64_t)k.sd.top + n > k.cap) return e->fail(ME_E_STATE, "me_stops_add: the table holds more live stops than the host counted");
+  }
+  std::vector<StopEnt> stage(n);
+  memset(stage.data(), 0, n * sizeof(StopEnt));
+  for (size_t i = 0; i < n; ++i) {
+    stage[i].s = stops[i];
+    memset(stage[i].s.pad, 0, sizeof stage[i].s.pad);
+    stage[i].live = 1;
+  }
+  HIP_TRY(hipMemcpyAsync(k.sd.tab + k.sd.top, stage.data(), n * sizeof(StopEnt), hipMemcpyHostToDevice, e->stream), "H2D stops");
+  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");  // (stage is pageable and goes out of scope)
+  k.sd.top += (uint32_t)n;
+  k.c.added += n;
+  k.c.last_id = stops[n - 1].id;
+  return ME_OK;
+}
+
+extern "C" int me_stops_cancel(me_engine* e, const uint64_t* ids, size_t n, uint8_t* found) {
+  if (!e) return ME_E_INVALID;
+  if (!e->stops.on) return e->fail(ME_E_INVALID, "the trigger book is off (me_stops_enable)");
+  if (n > STOPS_CAP_MAX) return e->fail(ME_E_INVALID, "me_stops_cancel: more than 2^22 ids");
+  if (n && (!ids || !found)) return e->fail(ME_E_INVALID, "me_stops_cancel: null ids or found");
+  if (!stops_ids_ascend(ids, n)) return e->fail(ME_E_INVALID, "me_stops_cancel: ids not strictly ascending");
+  int rc = me_sync(e);
+  if (rc) return rc;
+  if (!n) return ME_OK;
+  auto& k = e->sk;
+  if (n > k.q_cap) {
+    if (k.d_ids) HIP_TRY(hipFree(k.d_ids), "hipFree");
+    k.d_ids = nullptr;
+    if (k.d_found) HIP_TRY(hipFree(k.d_found), "hipFree");
+    k.d_found = nullptr;
+    k.q_cap = 0;
+    HIP_TRY(hipMalloc((void**)&k.d_ids, n * sizeof(uint64_t)), "hipMalloc stop cancel");
+    HIP_TRY(hipMalloc((void**)&k.d_found, n), "hipMalloc stop cancel");
+    k.q_cap = n;
+  }
+  HIP_TRY(hipMemcpyAsync(k.d_ids, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream), "H2D stop ids");
+  HIP_TRY(launch_stop_cancel(e->stream, k.sd, k.d_ids, (uint32_t)n, k.d_found), "stop cancel launch");
+  HIP_TRY(hipMemcpyAsync(found, k.d_found, n, hipMemcpyDeviceToHost, e->stream), "D2H stop cancel answers");
+  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+  for (size_t i = 0; i < n; ++i) k.c.cancelled += found[i] ? 1u : 0u;
+  return ME_OK;
+}
+
+static int stops_no_catch_up(me_engine*) { return ME_OK; }  // (no job ever defers: Feed::read never asks)
+
+extern "C" int me_stops_read(me_engine* e, me_stop_event* out, size_t cap, size_t* n, size_t* left) {
+  if (n) *n = 0;
+  if (left) *left = 0;
+  if (!e) return ME_E_INVALID;
+  if (!e->stops.on) return e->fail(ME_E_INVALID, "the trigger book is off (me_stops_enable)");
+  if (cap && !out) return e->fail(ME_E_INVALID, "null output");
+  if (e->failed) return me_sync(e);
+  return e->stops.read(e, out, cap, n, left, stops_no_catch_up);
+}
+
+extern "C" int me_stops_stats(me_engine* e, uint64_t* jobs, uint64_t* events, uint64_t* live) {
+  if (!e) return ME_E_INVALID;
+  if (!e->stops.on) return e->fail(ME_E_INVALID, "the trigger book is off (me_stops_enable)");
+  if (e->failed) return me_sync(e);
+  uint64_t ev = 0, deferred = 0;
+  e->stops.stats(jobs, &ev, &deferred);
+  if (deferred) return e->fail(ME_E_STATE, "stop job deferred: the event ring was full (internal bound broken)");
+  if (events) *events = ev;
+  if (live) *live = e->sk.c.added - e->sk.c.cancelled - ev;
+  return ME_OK;
+}
+
+extern "C" int me_stops_dump(me_engine* e, me_stop* out, size_t cap, size_t* n) {
+  if (n) *n = 0;
+  if (!e) return ME_E_INVALID;
+  if (!e->stops.on) return e->fail(ME_E_INVALID, "the trigger book is off (me_stops_enable)");
+  if (cap && !out) return e->fail(ME_E_INVALID, "null output");
+  int rc = me_sync(e);
+  if (rc) return rc;
+  if ((rc = stops_compact(e))) return rc;
+  auto& k = e->sk;
+  const size_t live = k.sd.top, take = std::min(live, cap);
+  if (n) *n = live;
+  if (!take) return ME_OK;
+  std::vector<StopEnt> stage(take);
+  HIP_TRY(hipMemcpyAsync(stage.data(), k.sd.tab, take * sizeof(StopEnt), hipMemcpyDeviceToHost, e->stream), "D2H stops");
+  HIP_TRY(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+  for (size_t i = 0; i < take; ++i) out[i] = stage[i].s;
   return ME_OK;
 }
 

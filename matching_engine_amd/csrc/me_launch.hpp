@@ -43,6 +43,11 @@ hipError_t launch_book_snapshot(hipStream_t st, const BookDev& bk, const SnapReq
 hipError_t launch_quotes(hipStream_t st, const BookDev& bk, const QuoteDev& q);
 hipError_t launch_depth(hipStream_t st, const BookDev& bk, const DepthDev& d);
 hipError_t launch_trades(hipStream_t st, const BookDev& bk, const TradeDev& t, const TradeLaunch& tl);
+// the trigger book: its job behind a match launch; a cancel by id (found [n]); the stable compaction of the
+// table's live entries into dst (count [1] receives how many)
+hipError_t launch_stops(hipStream_t st, const StopDev& sd, const TradeLaunch& tl);
+hipError_t launch_stop_cancel(hipStream_t st, const StopDev& sd, const uint64_t* ids, uint32_t n, uint8_t* found);
+hipError_t launch_stop_compact(hipStream_t st, const StopDev& sd, StopEnt* dst, uint32_t* count);
 hipError_t launch_order_query(hipStream_t st, const BookDev& bk, const OrderQueryReq& rq);
 hipError_t launch_order_preview(hipStream_t st, const BookDev& bk, const PreviewReq& rq);
 // the mass cancel's passes: remove = false counts (read-only), true removes

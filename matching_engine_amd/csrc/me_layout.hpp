@@ -666,6 +666,29 @@ struct TradeDev {
                              // reduces first, bit 1 updates go through the workgroup's LDS table
 };
 
+// ---- trigger book: stop and stop-limit orders (me_snapshot.hip k_stop_*) --------------
+// Everything below is allocated by me_stops_enable and nothing before it. The TABLE is append-only in
+// [0, top): entries ascend by id, a triggered or cancelled entry stays where it is with its state cleared,
+// and a stable compaction into the other buffer (k_stop_live + k_stop_compact) drops the dead ones when the
+// append end is reached. The host owns `top` and which buffer is current; both travel by value with every
+// launch. The job's fold is the trade feed's (k_trade_fold through a TradeDev view whose jw is the one here).
+struct alignas(8) StopEnt {
+  me_stop s;
+  uint8_t live;  // 1: waiting for its trigger; 0: triggered or cancelled
+  uint8_t pad[7];
+};
+static_assert(sizeof(me_stop) == 40 && sizeof(StopEnt) == 48, "a table entry is the stop plus a state byte: 48 B");
+static_assert(sizeof(me_stop_event) == 64, "me_stop_event is 64 B");
+struct StopDev {
+  FeedRing<me_stop_event> ring;
+  StopEnt* tab;              // [cap] the current buffer
+  unsigned long long* jw;    // [S][TJ_N] the job's raw words (TJ_*: the trade fold's)
+  unsigned long long* mask;  // [ceil(cap / 64)] one ballot word per 64 entries
+  uint32_t* woff;            // [ceil(cap / 64)] set bits before each word
+  uint32_t top;              // entries in use: [0, top)
+  uint32_t S;
+};
+
 constexpr int BK_CAP = 128;          // records per bucket (two 64-record blocks)
 constexpr int BK_KIND_SHIFT = 26;    // BkRec::ok: six kind bits (side, type, op, time in force) above the batch index
 constexpr uint32_t BK_KIND_BITS = 63u;

@@ -850,6 +850,174 @@ hipError_t launch_trades(hipStream_t st, const BookDev& bk, const TradeDev& t, c
   return hipGetLastError();
 }
 
+// ---- trigger book: stop and stop-limit orders (me_stops_*, include/me_engine.h) -----------------------
+// Three launches behind every match launch of an engine with live stops (none otherwise: the host knows).
+//
+// The fold is k_trade_fold as it is, through a TradeDev view whose jw words are the trigger book's own: after
+// it, a symbol's TJ_COUNT says whether it traded in this launch and TJ_HIGH / TJ_LOW hold its biased extremes.
+//
+// k_stop_scan: one lane per table entry of [0, top). A live entry reads its symbol's count (a symbol without
+// a fill triggers nothing: the count decides, not the min / max identities) and compares its biased stop
+// price with the high (BUY: high >= stop) or the low (SELL: low <= stop). Every wave ballots into its mask
+// word. 48 B per entry plus the symbol's 64-B line, which the entries of a symbol share in L2.
+//
+// k_stop_emit: k_trade_emit's shape — prefix the popcounts, feed_fits (always true: the host keeps a ring
+// slot for every live stop, me_stops.hpp), write the events at tail + pos in table order and clear the
+// entries' state; every writer fences at system scope, and after the barrier the job words of every symbol
+// that traded go back to their identities and thread 0 runs feed_publish.
+__global__ __launch_bounds__(256) void k_stop_scan(StopDev sd) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool trig = false;
+  if (i < sd.top) {
+    const StopEnt& e = sd.tab[i];
+    const uint32_t s = e.s.symbol;
+    if (e.live && s < sd.S) {
+      const unsigned long long* w = sd.jw + (size_t)s * TJ_N;
+      if (w[TJ_COUNT]) {
+        const unsigned long long p = trade_bias(e.s.stop_px_q4);
+        trig = (e.s.kind & 3u) == ME_SIDE_BUY ? w[TJ_HIGH] >= p : w[TJ_LOW] <= p;
+      }
+    }
+  }
+  const unsigned long long m = __ballot(trig);
+  if ((threadIdx.x & 63u) == 0u && i < sd.top) sd.mask[i >> 6] = m;  // (i: the word's first entry)
+}
+
+__global__ __launch_bounds__(SNAP_T) void k_stop_emit(StopDev sd) {
+  __shared__ uint32_t wsum[SNAP_T / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  const uint32_t nw = (sd.top + 63u) / 64u;
+  uint32_t run = 0;
+  for (uint32_t base = 0; base < nw; base += SNAP_T) {
+    const uint32_t w = base + tid;
+    const uint32_t pc = w < nw ? (uint32_t)__popcll(sd.mask[w]) : 0u;
+    uint32_t tot = 0;
+    const uint32_t ex = snap_block_excl_scan(pc, wsum, tot);
+    if (w < nw) sd.woff[w] = run + ex;
+    run += tot;
+  }
+  const FeedRing<me_stop_event>& r = sd.ring;
+  const unsigned long long tail = r.ctl[FR_TAIL];
+  const bool fit = feed_fits(r, tail, run);
+  __syncthreads();  // the offsets are written, the tail is read
+  if (fit && run) {
+    for (uint32_t w = wv; w < nw; w += SNAP_T / 64) {
+      const unsigned long long m = sd.mask[w];
+      if (!((m >> lane) & 1ull)) continue;
+      const uint32_t i = w * 64u + lane;
+      const uint32_t pos = sd.woff[w] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      const me_stop s = sd.tab[i].s;
+      const unsigned long long* jw = sd.jw + (size_t)s.symbol * TJ_N;
+      me_stop_event ev;
+      ev.id = s.id;
+      ev.stop_px_q4 = s.stop_px_q4;
+      ev.limit_px_q4 = s.limit_px_q4;
+      ev.trigger_px_q4 = trade_unbias((s.kind & 3u) == ME_SIDE_BUY ? jw[TJ_HIGH] : jw[TJ_LOW]);
+      ev.batches = r.batches;
+      ev.qty = s.qty;
+      ev.symbol = s.symbol;
+      ev.kind = s.kind;
+      for (int k = 0; k < 15; ++k) ev.pad[k] = 0;
+      r.log[(tail + pos) % r.cap] = ev;
+      sd.tab[i].live = 0;
+    }
+    __threadfence_system();
+  }
+  __syncthreads();  // every writer has fenced and has read its symbol's words
+  for (uint32_t s = tid; s < sd.S; s += SNAP_T) {
+    unsigned long long* w = sd.jw + (size_t)s * TJ_N;
+    if (!w[TJ_COUNT]) continue;  // (the count rises with every other word: untouched words are identities)
+    w[TJ_FIRST] = ~0ull;
+    w[TJ_LAST] = 0ull;
+    w[TJ_HIGH] = 0ull;
+    w[TJ_LOW] = ~0ull;
+    w[TJ_VOLUME] = 0ull;
+    w[TJ_COUNT] = 0ull;
+  }
+  if (tid == 0) feed_publish(r, tail, run, fit);
+}
+
+// The trigger book's job on st, behind the match launch whose nb batches tl names.
+hipError_t launch_stops(hipStream_t st, const StopDev& sd, const TradeLaunch& tl) {
+  if (tl.nb && tl.nmax) {
+    TradeDev t{};  // the fold reads jw and wave_reduce alone
+    t.jw = sd.jw;
+    t.wave_reduce = TF_WAVE | TF_TABLE;
+    hipLaunchKernelGGL(k_trade_fold, dim3((tl.nmax + TF_T * TF_ITERS - 1u) / (TF_T * TF_ITERS), tl.nb), dim3(TF_T), 0,
+                       st, t, tl, sd.S);
+  }
+  if (sd.top) hipLaunchKernelGGL(k_stop_scan, dim3((sd.top + 255u) / 256u), dim3(256), 0, st, sd);
+  hipLaunchKernelGGL(k_stop_emit, dim3(1), dim3(SNAP_T), 0, st, sd);
+  return hipGetLastError();
+}
+
+// k_stop_cancel: one lane per id. The table ascends by id over [0, top), dead entries included, so a binary
+// search finds the one entry that can hold the id; a live one is cleared and answers 1. The ids of a call are
+// distinct (the host checks that they ascend): no two lanes touch one entry.
+__global__ __launch_bounds__(256) void k_stop_cancel(StopDev sd, const uint64_t* ids, uint32_t n, uint8_t* found) {
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= n) return;
+  const uint64_t id = ids[q];
+  uint32_t lo = 0, hi = sd.top;  // the first entry with an id >= id lies in [lo, hi]
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (sd.tab[mid].s.id < id) lo = mid + 1u;
+    else hi = mid;
+  }
+  uint8_t f = 0;
+  if (lo < sd.top && sd.tab[lo].s.id == id && sd.tab[lo].live) {
+    sd.tab[lo].live = 0;
+    f = 1;
+  }
+  found[q] = f;
+}
+
+hipError_t launch_stop_cancel(hipStream_t st, const StopDev& sd, const uint64_t* ids, uint32_t n, uint8_t* found) {
+  if (n) hipLaunchKernelGGL(k_stop_cancel, dim3((n + 255u) / 256u), dim3(256), 0, st, sd, ids, n, found);
+  return hipGetLastError();
+}
+
+// The stable compaction of the table (an add that reaches the append end, and me_stops_dump): k_stop_live
+// ballots "live" per entry, k_stop_compact — one workgroup, k_stop_emit's prefix — scatters the live entries
+// to dst in table order and writes their number to *count. dst is the table's other buffer: never sd.tab.
+__global__ __launch_bounds__(256) void k_stop_live(StopDev sd) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const unsigned long long m = __ballot(i < sd.top && sd.tab[i].live);
+  if ((threadIdx.x & 63u) == 0u && i < sd.top) sd.mask[i >> 6] = m;
+}
+
+__global__ __launch_bounds__(SNAP_T) void k_stop_compact(StopDev sd, StopEnt* dst, uint32_t* count) {
+  __shared__ uint32_t wsum[SNAP_T / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  const uint32_t nw = (sd.top + 63u) / 64u;
+  uint32_t run = 0;
+  for (uint32_t base = 0; base < nw; base += SNAP_T) {
+    const uint32_t w = base + tid;
+    const uint32_t pc = w < nw ? (uint32_t)__popcll(sd.mask[w]) : 0u;
+    uint32_t tot = 0;
+    const uint32_t ex = snap_block_excl_scan(pc, wsum, tot);
+    if (w < nw) sd.woff[w] = run + ex;
+    run += tot;
+  }
+  __syncthreads();  // the offsets are written
+  for (uint32_t w = wv; w < nw; w += SNAP_T / 64) {
+    const unsigned long long m = sd.mask[w];
+    if (!((m >> lane) & 1ull)) continue;
+    // (pos <= the entry's own index < top <= cap: inside dst)
+    const uint32_t pos = sd.woff[w] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    StopEnt e = sd.tab[w * 64u + lane];
+    for (int k = 0; k < 7; ++k) e.s.pad[k] = 0;
+    dst[pos] = e;
+  }
+  if (tid == 0) *count = run;
+}
+
+hipError_t launch_stop_compact(hipStream_t st, const StopDev& sd, StopEnt* dst, uint32_t* count) {
+  if (sd.top) hipLaunchKernelGGL(k_stop_live, dim3((sd.top + 255u) / 256u), dim3(256), 0, st, sd);
+  hipLaunchKernelGGL(k_stop_compact, dim3(1), dim3(SNAP_T), 0, st, sd, dst, count);
+  return hipGetLastError();
+}
+
 // ---- order query (me_order_query, include/me_engine.h) -----------------------------------------------
 // k_order_query: one wave per queried seq, four per workgroup, read-only. The wave
 //   1. finds the order's slot as cancel_order does (me_kernels.hip): the seq ring's entry, verified (chunk id

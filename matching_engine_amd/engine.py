@@ -145,6 +145,7 @@ class Engine:
         )
         self.max_batch = int(max_batch)
         self._depth = 0  # levels per side of the depth feed (depth_enable), 0 while it is off
+        self._stops_cap = 0  # the trigger book's capacity (stops_enable), 0 while it is off
         h = self.lib.me_create(C.byref(cfg))
         if not h:
             buf = C.create_string_buffer(1024)
@@ -493,6 +494,52 @@ class Engine:
     def trades_stats(self) -> dict:
         return self._feed_stats(self.lib.me_trades_stats)
 
+    # -- trigger book: stop and stop-limit orders (me_stops_*)
+    def stops_enable(self, cap_stops: int):
+        """Turn the trigger book on for at most cap_stops stops live or triggered-and-unread (<= 2^22), or off with
+        0 (everything is dropped). Enabling again starts afresh."""
+        _check(self.lib, self.h, self.lib.me_stops_enable(self.h, int(cap_stops)))
+        self._stops_cap = int(cap_stops)
+
+    def stops_add(self, stops):
+        """me_stops_add: STOP_DTYPE records (id ascending, local symbol ids), all or nothing. Fills of batches
+        submitted before this call never trigger them."""
+        a = np.ascontiguousarray(stops, dtype=_abi.STOP_DTYPE).reshape(-1)
+        _check(self.lib, self.h, self.lib.me_stops_add(self.h, ptr(a), len(a)))
+
+    def stops_cancel(self, ids) -> np.ndarray:
+        """me_stops_cancel: found (uint8) per id, strictly ascending ids; syncs first, so a stop the submitted
+        batches trigger answers 0 and its event is readable."""
+        q = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        found = np.zeros(len(q), dtype=np.uint8)
+        _check(self.lib, self.h, self.lib.me_stops_cancel(self.h, ptr(q), len(q), ptr(found)))
+        return found
+
+    def stops_read(self, cap: int = 0):
+        """(events STOP_EVENT_DTYPE, left): up to `cap` logged events in order (0 = a buffer of cap_stops, at most
+        65,536) and how many stay unread. Launches no partial group and waits for nothing."""
+        cap = int(cap) or max(1, min(self._stops_cap, 1 << 16))
+        return self._feed_read(self.lib.me_stops_read, _abi.STOP_EVENT_DTYPE, cap)
+
+    def stops_drain(self) -> np.ndarray:
+        """Every logged event: reads until none is left."""
+        return self._feed_drain(self.stops_read)
+
+    def stops_stats(self) -> dict:
+        """jobs run, events logged, stops live (exact after sync). Raises if a job ever found the ring full."""
+        j, ev, lv = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib, self.h, self.lib.me_stops_stats(self.h, C.byref(j), C.byref(ev), C.byref(lv)))
+        return {"jobs": j.value, "events": ev.value, "live": lv.value}
+
+    def stops_dump(self) -> np.ndarray:
+        """me_stops_dump: the live stops (STOP_DTYPE) in table order, after a sync: what a caller persists."""
+        n = C.c_size_t(0)
+        _check(self.lib, self.h, self.lib.me_stops_dump(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=_abi.STOP_DTYPE)
+        if n.value:
+            _check(self.lib, self.h, self.lib.me_stops_dump(self.h, ptr(out), len(out), C.byref(n)))
+        return out[: n.value]
+
     # -- timing
     def timing_enable(self, period: int = 1):
         """HIP events on every `period`-th match launch (True = every launch, 0/False = off)."""
@@ -591,6 +638,14 @@ class Stream:
             parts.append(Batch(a[0], a[1], a[2], np.full(m, s, dtype=np.uint32), a[3]))
         return Batch(*[np.concatenate([getattr(p, f) for p in parts]) for f in
                        ("seq", "price_q4", "qty", "symbol", "kind")])
+
+
+def stop_records(events, seq0: int) -> Batch:
+    """The NEW records triggered stops become (STOP_EVENT_DTYPE events, in event order): seqs seq0, seq0 + 1, ...;
+    price (limit_px_q4), qty, symbol and kind are the events'. The caller submits them in a later batch."""
+    ev = np.asarray(events, dtype=_abi.STOP_EVENT_DTYPE).reshape(-1)
+    seq = np.uint64(seq0) + np.arange(len(ev), dtype=np.uint64)
+    return Batch(seq, ev["limit_px_q4"], ev["qty"], ev["symbol"], ev["kind"])
 
 
 def shard_of(symbol: int, shards: int) -> int:
