@@ -608,7 +608,8 @@ int me_trades_stats(me_engine* e, uint64_t* groups, uint64_t* events, uint64_t* 
  * added - cancelled - events read > 0; an engine that never enables it launches exactly what it launched
  * before. Job order with several feeds on: quote, depth, trade, stops; the other feeds' events, and every
  * result, tape and book, are what they are without it.
- * Out of scope here: the service RPC (me_stops_dump is its persistence hook), the cluster, trailing stops. */
+ * The service carries stops to its clients (me_service.h: me_service_stops_enable, _submit_stop, _cancel_stop):
+ * ids of their own, a `stops` table and restart recovery. Out of scope: the cluster, trailing stops. */
 typedef struct me_stop { /* 40 B */
   uint64_t id;          /* the caller's, non-zero, ascending over every add since me_stops_enable */
   int64_t stop_px_q4;

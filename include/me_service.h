@@ -28,6 +28,9 @@
  *   me_service_market_data    StreamMarketData's MarketDataUpdate (proto:60-67) from the GPU book.
  *   me_service_updates        StreamOrderUpdates (proto/matching_engine.proto:34,71-91): drains the
  *                             OrderUpdate events the flushes produced, optionally for one client_id.
+ *   me_service_submit_stop    stop and stop-limit orders — a build extension (the trigger book of me_engine.h
+ *                             behind me_service_stops_enable): ids "SID-<n>", me_service_cancel_stop,
+ *                             me_service_stop_updates, a `stops` table and restart recovery (further down).
  *
  * Restart: the reference resumes only its OID counter from the DB (matching_engine_service.cpp:18-22,
  * storage.cpp:254-267). me_service_create does that and also rebuilds the books: every order the DB
@@ -126,11 +129,19 @@ typedef struct me_matcher {
   int (*trades)(void* ctx, me_trade* out, size_t cap, size_t* n, size_t* left);
   int (*order_query)(void* ctx, const uint64_t* seqs, size_t n, me_order_info* out);
   int (*order_preview)(void* ctx, const me_order_soa* q, size_t n, me_preview* out);
+  /* Optional, all four or none (else the matcher has no stop orders: me_service_stops_enable answers
+   * ME_E_INVALID): me_stops_enable's / me_stops_add's / me_stops_cancel's / me_stops_read's contracts over the
+   * matcher's books. me_stop.symbol is in the id space of `match`; me_stop_event.batches counts slices, as
+   * `quotes` documents. A matcher built by older code must be zero-initialised up to sizeof(me_matcher). */
+  int (*stops_enable)(void* ctx, uint64_t cap_stops);
+  int (*stops_add)(void* ctx, const me_stop* stops, size_t n);
+  int (*stops_cancel)(void* ctx, const uint64_t* ids, size_t n, uint8_t* found);
+  int (*stops_read)(void* ctx, me_stop_event* out, size_t cap, size_t* n, size_t* left);
 } me_matcher;
 
 /* The service over a matcher instead of an engine (same contract otherwise). NULL on a bad matcher. The
  * matcher must outlive the service: me_service_destroy (like an unsubscribe) turns the depth and trade feeds
- * it enabled off through depth_enable / trades_enable. */
+ * it enabled off through depth_enable / trades_enable, and stop orders off through stops_enable(ctx, 0). */
 me_service* me_service_create_matcher(const me_matcher* m, const char* const* symbols, uint32_t num_symbols,
                                       const char* db_path);
 
@@ -288,7 +299,9 @@ int me_service_preview_order(me_service* s, const me_order_request* req, int32_t
  * the orders back; me_service_order_status then answers ME_OS_NOT_RESTING for them, and a book left empty
  * counts as idle: a new symbol may take it (me_service_stats: reclaimed_books). *n_cancelled (or NULL)
  * receives the number of orders removed. ME_E_INVALID with nothing changed: a name that has no book, a name
- * given twice, a NULL name, sides outside 1..3, and a service over a me_matcher (it has no mass cancel). */
+ * given twice, a NULL name, sides outside 1..3, and a service over a me_matcher (it has no mass cancel).
+ * Stop orders are left alone, as me_mass_cancel leaves them: a purge produces no fill and triggers nothing, and
+ * the stops of a purged symbol stay armed (and keep its book) until their owners cancel them. */
 int me_service_mass_cancel(me_service* s, const char* const* symbols, size_t n, int32_t sides, uint64_t* n_cancelled);
 
 /* OrderUpdate (proto:71-91). Events per flushed record, in slice order: for each fill the maker's
@@ -312,7 +325,8 @@ typedef struct me_order_update {
  * leaving the others queued). *n = updates written; returns ME_OK. */
 int me_service_updates(me_service* s, const char* client_id, me_order_update* out, size_t cap, size_t* n);
 /* Events dropped because the queue held 2^24 undrained updates (the oldest go first; each drop also
- * sets me_service_last_error). */
+ * sets me_service_last_error). One count for the OrderUpdate queue and the stop update queue
+ * (me_service_stop_updates), which has the same bound. */
 uint64_t me_service_updates_dropped(const me_service* s);
 /* Books handed from an idle symbol to a new one since create, and resting orders replayed into the
  * books from the DB at create (restart recovery). */
@@ -418,6 +432,120 @@ int me_service_trades_subscribe(me_service* s, int on);
  * idle symbol to a new one reports each name's own totals, not the book's. *n = updates written;
  * ME_E_INVALID when not subscribed. */
 int me_service_trades_stream(me_service* s, const char* symbol, me_trade_update* out, size_t cap, size_t* n);
+
+/* ---- stop and stop-limit orders (build extension; the trigger book of me_engine.h, me_stops_*) --------------
+ * A stop waits outside the book until its symbol trades through its stop price (BUY: a fill at or above it,
+ * SELL: at or below it) and then becomes an ordinary order of its owner: a MARKET (a stop) or a LIMIT (a
+ * stop-limit). The backend judges the stops in the job behind every match launch; what the service adds per
+ * slice is one read of its event ring.
+ *
+ * IDS. Stops have their own id space, "SID-<n>", counted from 1 (after a restart: from the highest id the
+ * `stops` table holds, plus 1); n is the backend's me_stop.id. The order a stop becomes takes the next OID when
+ * its event is processed, not before: seqs ascend along the stream, and OIDs stay gap-free.
+ *
+ * STREAM POSITION. A stop operation (SubmitStop, CancelStop) closes the open slice if it holds records and
+ * attaches to the boundary in front of the next slice; consecutive operations share one boundary. The flush
+ * path applies a boundary's operations in submission order right before it submits the slice behind it — runs
+ * of adds as one stops_add, runs of cancels as one stops_cancel (ids sorted; an id named twice in a run is
+ * answered CANCEL_REJECTED the second time) — so a stop sees the fills of every order submitted after it and
+ * of none submitted before it (me_stops_add's rule). A boundary with no slice behind it is applied by
+ * me_service_flush and, on its interval, by the background flusher. A slice split after a capacity refusal has
+ * the boundary in front of its first part only. Slices already in flight are collected before a boundary that
+ * holds a cancel is applied. me_service_pending counts records only.
+ *
+ * TRIGGER. After every collected slice, and after every stops_cancel, the backend's events are read until none
+ * is left; an event is processed once the slice it is stamped with has been collected (two slices are in
+ * flight, and a later slice's events may already be readable: the outcome does not depend on that). The stamps
+ * are matched as me_service_market_subscribe matches them: the engine must have been fresh when the service was
+ * created, and recovery slices count. For each event, in ring order: the next OID is allocated, the NEW record
+ * (the event's kind, limit price, quantity and symbol) joins the open slice under the stop's client, and a
+ * TRIGGERED update is queued. From then on the order is an ordinary order: its OrderUpdates go to the stop's
+ * owner, it can be cancelled and reduced while it rests. me_service_flush does not chase a cascade: the
+ * injected orders stay pending (me_service_pending() > 0) for the next flush or the background flusher — one
+ * step per flush, as in the engine. With batches_per_launch > 1 the engine judges the stops once per launch
+ * group: slices of one flush that share a group share a job, so trigger_price is the group's extreme and the
+ * events of the group come in stop id order.
+ * THERE IS NO "ALREADY THROUGH THE MARKET" CHECK (me_engine.h): a stop waits for the next qualifying fill.
+ *
+ * PERSISTENCE. me_service_stops_enable creates the table `stops` (stop_id INTEGER PRIMARY KEY — the n of
+ * "SID-n" —, client_id, symbol, side, order_type, tif, stop_price and limit_price (Q4), quantity, status
+ * (ME_SS_ARMED / _TRIGGERED / _CANCELED), order_id, trigger_price, updated_ts); a database that never enables
+ * stops keeps the reference's schema. Rows go through the persister in order with the matched slices: the ARMED
+ * insert and the CANCELED update in the transaction of the slice behind their boundary, TRIGGERED (with
+ * order_id and trigger_price) in the transaction that carries the triggered order's `orders` row. A crash
+ * between the trigger and that commit therefore leaves the stop ARMED and no order: it is re-armed at the
+ * restart and, there being no already-through-the-market check, waits for the next qualifying fill. A failed
+ * transaction is kept and retried like a slice's. Without a database everything works, in memory only. */
+
+/* cap_stops > 0: turn stop orders on — the backend's stops_enable(cap_stops) (an engine, or a matcher's four
+ * hooks; a matcher without them: ME_E_INVALID; more than 2^22: ME_E_INVALID) — create the table, seed the SID
+ * counter from MAX(stop_id) + 1 over all rows (never backwards within one service: a SID handed out before an
+ * off / on is not issued again), and re-add the rows the database shows ARMED in ascending id
+ * through stops_add (the books were rebuilt at create): they count into me_service_stop_stats' `recovered` and
+ * keep their symbols' books. More ARMED rows than cap_stops, or more symbols than books: ME_E_CAPACITY and
+ * stop orders stay off. Already on: ME_E_STATE. cap_stops == 0: off — the backend's table and events are
+ * dropped, queued stop updates too; the rows stay (a later enable re-arms them). It waits for a running flush. */
+int me_service_stops_enable(me_service* s, uint64_t cap_stops);
+
+typedef struct me_stop_request {
+  const char* client_id;
+  const char* symbol;
+  int32_t order_type, side; /* of the order the stop becomes */
+  int64_t price;            /* its limit price; ignored for a MARKET */
+  int64_t stop_price;       /* same scale */
+  int32_t scale, quantity, tif; /* ME_TIF_* */
+} me_stop_request;
+/* Always returns 0; the first failing check wins, answered in-band, and a refused request takes no SID and no
+ * OID: (1) "stop orders are not enabled"; (2) SubmitOrder's checks, its strings and order ("symbol is
+ * required", "quantity must be > 0", "price must be > 0 for LIMIT"); (3) "invalid time in force" as
+ * me_service_submit_order_tif gives it; (4) normalize_to_q4 of price (LIMIT only) and of stop_price with
+ * `scale`: grpc_status 2 and SubmitOrder's text ("scale out of range", "overflow", "underflow"); then a side
+ * other than BUY / SELL: "DB insert failed" (SubmitOrder's answer to it; here before any id exists); (5)
+ * "stop capacity exhausted", grpc_status 8, when the stops accepted and not yet cancel-confirmed or
+ * trigger-processed, plus this one, exceed cap_stops — the service mirrors the engine's bound on the host, so
+ * the backend's add is never refused (should it be, the service fails: ME_E_* from the flush, not an answer);
+ * (6) the book claim as SubmitOrder does it: "symbol capacity exhausted", grpc_status 8. Accepted: success = 1,
+ * order_id = "SID-<n>"; the stop is QUEUED until its boundary is applied, then ARMED (one ARMED update). A book
+ * with a QUEUED or ARMED stop is not idle: no other symbol takes it over. */
+int me_service_submit_stop(me_service* s, const me_stop_request* req, me_order_response* resp);
+
+typedef struct me_stop_cancel_request {
+  const char* client_id;
+  const char* stop_id; /* "SID-<n>" */
+} me_stop_cancel_request;
+/* Always returns 0. In-band, first failing check wins: "stop orders are not enabled", "stop_id is invalid" (not
+ * "SID-<n>", n >= 1), "stop belongs to another client" (a QUEUED or ARMED stop of a different client_id). An
+ * accepted cancel consumes no id and answers success = 1 with order_id = the TARGET's id; its outcome arrives as
+ * a stop update once its boundary is applied: CANCELED when the backend found the stop live (found = 1), else
+ * CANCEL_REJECTED (already triggered, already cancelled, or an id nobody owns, which is queued like any other).
+ * The backend's events are read and processed before the outcomes are queued: the owner of a stop that had
+ * triggered sees TRIGGERED before the rejection. */
+int me_service_cancel_stop(me_service* s, const me_stop_cancel_request* req, me_order_response* resp);
+
+enum { ME_SS_ARMED = 0, ME_SS_TRIGGERED = 1, ME_SS_CANCELED = 2, ME_SS_CANCEL_REJECTED = 3, ME_SS_QUEUED = 4 };
+typedef struct me_stop_update { /* 200 B */
+  char stop_id[32];   /* "SID-<n>" */
+  char order_id[32];  /* "OID-<n>" once TRIGGERED, else "" */
+  char client_id[64]; /* the stop's owner; of a CANCEL_REJECTED: the requester */
+  char symbol[32];    /* "" in a CANCEL_REJECTED of a stop the service no longer holds */
+  int32_t state;      /* ME_SS_* */
+  int32_t scale;      /* 4 */
+  int64_t stop_price, limit_price, trigger_price; /* Q4; trigger_price 0 until TRIGGERED */
+  int32_t quantity;
+  uint8_t kind;       /* ME_KIND_TIF of the order the stop becomes */
+  uint8_t pad[3];
+} me_stop_update;
+/* me_service_updates' contract for the stop updates: drain up to cap of them (client_id NULL or "": every
+ * client's; else only that client's, the others stay queued). *n = updates written; returns ME_OK. The queue
+ * holds 2^24 undrained updates; beyond that the oldest go first, each drop counted by
+ * me_service_updates_dropped and the first one reported in me_service_last_error. */
+int me_service_stop_updates(me_service* s, const char* client_id, me_stop_update* out, size_t cap, size_t* n);
+/* The caller's stops that are QUEUED or ARMED, in ascending stop id (client_id NULL or "": every client's).
+ * *n is exact even when cap is short (entries past it are not written; out may be NULL when cap is 0). */
+int me_service_stops(me_service* s, const char* client_id, me_stop_update* out, size_t cap, size_t* n);
+/* live: stops QUEUED or ARMED now; triggered: events processed since the enable; recovered: ARMED rows re-added
+ * from the database by the enable. Any pointer may be NULL. All 0 while stop orders are off. */
+int me_service_stop_stats(const me_service* s, uint64_t* live, uint64_t* triggered, uint64_t* recovered);
 
 int me_service_last_error(const me_service* s, char* buf, size_t cap);
 

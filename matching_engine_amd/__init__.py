@@ -11,7 +11,7 @@ from ._abi import (  # noqa: F401
     RJ_CAPACITY, RJ_WOULD_CROSS, RJ_BAD_TIF, TIF_GTC, TIF_IOC, TIF_FOK, TIF_POST_ONLY,
     ME_OK, ME_E_INVALID, ME_E_HIP, ME_E_CAPACITY, ME_E_STATE, ME_E_SQLITE,
     QUOTE_DTYPE, QUOTE_HAS_BID, QUOTE_HAS_ASK, DEPTH_DTYPE, DEPTH_MAX, TRADE_DTYPE,
-    STOP_DTYPE, STOP_EVENT_DTYPE, STOPS_CAP_MAX,
+    STOP_DTYPE, STOP_EVENT_DTYPE, STOPS_CAP_MAX, SS_ARMED, SS_TRIGGERED, SS_CANCELED, SS_CANCEL_REJECTED, SS_QUEUED,
     ORDER_INFO_DTYPE, OS_NOT_RESTING, OS_PENDING, OS_RESTING,
     PREVIEW_DTYPE, PV_HAS_OPP, PV_CROSSES, PV_RESTS, preview_notional,
 )

@@ -380,6 +380,52 @@ class MeOrderUpdate(C.Structure):
 assert C.sizeof(MeOrderUpdate) == 152, "me_order_update layout"
 
 
+# stop orders through the service (me_service_stops_enable / _submit_stop / _cancel_stop / _stop_updates / _stops)
+SS_ARMED, SS_TRIGGERED, SS_CANCELED, SS_CANCEL_REJECTED, SS_QUEUED = 0, 1, 2, 3, 4
+
+
+class MeStopRequest(C.Structure):
+    _fields_ = [
+        ("client_id", C.c_char_p),
+        ("symbol", C.c_char_p),
+        ("order_type", C.c_int32),
+        ("side", C.c_int32),
+        ("price", C.c_int64),
+        ("stop_price", C.c_int64),
+        ("scale", C.c_int32),
+        ("quantity", C.c_int32),
+        ("tif", C.c_int32),
+    ]
+
+
+class MeStopCancelRequest(C.Structure):
+    _fields_ = [
+        ("client_id", C.c_char_p),
+        ("stop_id", C.c_char_p),
+    ]
+
+
+class MeStopUpdate(C.Structure):
+    _fields_ = [
+        ("stop_id", C.c_char * 32),
+        ("order_id", C.c_char * 32),
+        ("client_id", C.c_char * 64),
+        ("symbol", C.c_char * 32),
+        ("state", C.c_int32),
+        ("scale", C.c_int32),
+        ("stop_price", C.c_int64),
+        ("limit_price", C.c_int64),
+        ("trigger_price", C.c_int64),
+        ("quantity", C.c_int32),
+        ("kind", C.c_uint8),
+        ("pad", C.c_uint8 * 3),
+    ]
+
+
+assert C.sizeof(MeStopRequest) == 56 and C.sizeof(MeStopCancelRequest) == 16, "me_stop_request layout"
+assert C.sizeof(MeStopUpdate) == 200, "me_stop_update layout"
+
+
 class MeMarketData(C.Structure):
     _fields_ = [
         ("best_bid", C.c_int64),
@@ -497,7 +543,22 @@ PARITY_HOOKS = [
 ]
 
 
+# me_matcher's stop hooks (all four or none; me_shard_ops has none: the cluster carries no stop orders)
+STOPS_ENABLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64)
+STOPS_ADD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
+STOPS_CANCEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_uint8))
+STOP_HOOKS = [
+    ("stops_enable", STOPS_ENABLE_FN),
+    ("stops_add", STOPS_ADD_FN),
+    ("stops_cancel", STOPS_CANCEL_FN),
+    ("stops_read", QUOTES_FN),
+]
+
+
 class MeMatcher(C.Structure):
+    """The HEAD of me_matcher: its members up to order_preview, the ones me_shard_ops shares. NEVER ALLOCATE IT:
+    it is 32 bytes shorter than the C struct, which me_service_create_matcher reads and me_cluster_matcher clears
+    in full. MeMatcherStops below is the whole struct; the prototypes take only that one."""
     _fields_ = [
         ("ctx", C.c_void_p),
         ("num_symbols", C.c_uint32),
@@ -509,6 +570,13 @@ class MeMatcher(C.Structure):
         ("collect", COLLECT_FN),
         ("quotes", QUOTES_FN),
     ] + PARITY_HOOKS
+
+
+class MeMatcherStops(MeMatcher):
+    """me_matcher as include/me_service.h declares it: MeMatcher's members (the struct up to order_preview, the
+    members me_shard_ops shares), then the four stop hooks. ALLOCATE THIS ONE: me_cluster_matcher clears, and
+    me_service_create_matcher reads, sizeof(me_matcher) bytes. A fresh instance is all zero: no stop orders."""
+    _fields_ = STOP_HOOKS
 
 
 # ---- include/me_cluster.h ---------------------------------------------------------------------
@@ -546,7 +614,7 @@ class MeShardOps(C.Structure):
 
 
 PROTOTYPES.update({
-    "me_service_create_matcher": (_P, [C.POINTER(MeMatcher), C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p]),
+    "me_service_create_matcher": (_P, [C.POINTER(MeMatcherStops), C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p]),
     "me_service_order_book": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ),
                                         C.POINTER(MeBookOrder), _SZ, C.POINTER(_SZ)]),
     "me_service_order_status": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_char_p), _SZ, C.POINTER(MeOrderStatus)]),
@@ -561,6 +629,12 @@ PROTOTYPES.update({
     "me_service_depth_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeDepthBook), _SZ, C.POINTER(_SZ)]),
     "me_service_trades_subscribe": (C.c_int, [_P, C.c_int]),
     "me_service_trades_stream": (C.c_int, [_P, C.c_char_p, C.POINTER(MeTradeUpdate), _SZ, C.POINTER(_SZ)]),
+    "me_service_stops_enable": (C.c_int, [_P, C.c_uint64]),
+    "me_service_submit_stop": (C.c_int, [_P, C.POINTER(MeStopRequest), C.POINTER(MeOrderResponse)]),
+    "me_service_cancel_stop": (C.c_int, [_P, C.POINTER(MeStopCancelRequest), C.POINTER(MeOrderResponse)]),
+    "me_service_stop_updates": (C.c_int, [_P, C.c_char_p, C.POINTER(MeStopUpdate), _SZ, C.POINTER(_SZ)]),
+    "me_service_stops": (C.c_int, [_P, C.c_char_p, C.POINTER(MeStopUpdate), _SZ, C.POINTER(_SZ)]),
+    "me_service_stop_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_cluster_quotes_enable": (C.c_int, [_P, C.c_uint64]),
     "me_cluster_quotes": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "me_cluster_depth_enable": (C.c_int, [_P, C.c_uint32, C.c_uint64]),
@@ -596,7 +670,7 @@ PROTOTYPES.update({
     "me_cluster_book": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _SZ, C.POINTER(_SZ), _P, _SZ, C.POINTER(_SZ),
                                   _P, _P, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "me_cluster_snapshot": (C.c_int, [_P, C.c_uint32, _P, _P]),
-    "me_cluster_matcher": (C.c_int, [_P, C.POINTER(MeMatcher)]),
+    "me_cluster_matcher": (C.c_int, [_P, C.POINTER(MeMatcherStops)]),
     "me_cluster_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "me_cluster_phases": (C.c_int, [_P, C.POINTER(C.c_double), _SZ]),
     "me_cluster_last_error": (C.c_int, [_P, C.c_char_p, _SZ]),

@@ -156,9 +156,53 @@ def _set_parity_hooks(struct, obj):
     return tuple(keep)
 
 
+def _set_stop_hooks(m, obj):
+    """me_matcher's four stop hooks over stops_enable(cap), stops_add(recs STOP_DTYPE), stops_cancel(ids uint64[n])
+    -> found uint8[n] and stops_read(cap) -> (events STOP_EVENT_DTYPE, left) — set when obj has all four, else
+    all NULL (the matcher has no stop orders). ValueError is me's ME_E_INVALID, SliceRefused its ME_E_CAPACITY.
+    Returns the callbacks, which must live as long as the struct."""
+    names = ("stops_enable", "stops_add", "stops_cancel", "stops_read")
+    if not all(hasattr(obj, n) for n in names):
+        return ()
+
+    def guard(fn):
+        def cb(ctx, *a):
+            try:
+                fn(*a)
+                return 0
+            except ValueError:
+                return _abi.ME_E_INVALID
+            except SliceRefused:
+                return _abi.ME_E_CAPACITY
+            except Exception:
+                return _abi.ME_E_STATE
+
+        return cb
+
+    def add(recs, n):
+        a = np.zeros(n, dtype=_abi.STOP_DTYPE)
+        if n:
+            C.memmove(a.ctypes.data, recs, a.nbytes)
+        obj.stops_add(a)
+
+    def cancel(ids, n, found):
+        q = np.ctypeslib.as_array(ids, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+        got = np.ascontiguousarray(obj.stops_cancel(q), dtype=np.uint8)
+        assert len(got) == n
+        for i in range(n):
+            found[i] = int(got[i])
+
+    m.stops_enable = _abi.STOPS_ENABLE_FN(guard(lambda cap: obj.stops_enable(int(cap))))
+    m.stops_add = _abi.STOPS_ADD_FN(guard(add))
+    m.stops_cancel = _abi.STOPS_CANCEL_FN(guard(cancel))
+    m.stops_read = _abi.QUOTES_FN(_events_cb(obj.stops_read, _abi.STOP_EVENT_DTYPE))
+    return (m.stops_enable, m.stops_add, m.stops_cancel, m.stops_read)
+
+
 def python_matcher(obj) -> MeMatcher:
     """me_matcher over a Python object with match(batch) -> (results, tape), book_orders(symbol, depth)
-    -> (bid entries, ask entries, bid levels, ask levels), num_symbols, max_batch, max_resting. Test
+    -> (bid entries, ask entries, bid levels, ask levels), num_symbols, max_batch, max_resting, and the optional
+    hooks: quotes, _set_parity_hooks' six, and the four stop hooks (_set_stop_hooks: all four or none). Test
     infrastructure (a single book standing in for a backend); the callbacks run on the flushing thread."""
     keep = {}
 
@@ -183,7 +227,7 @@ def python_matcher(obj) -> MeMatcher:
         except Exception:
             return _abi.ME_E_STATE
 
-    m = MeMatcher()
+    m = _abi.MeMatcherStops()
     m.ctx = None
     m.num_symbols, m.max_batch, m.max_resting = obj.num_symbols, obj.max_batch, obj.max_resting
     m.match = _abi.MATCH_FN(match_cb)
@@ -193,6 +237,7 @@ def python_matcher(obj) -> MeMatcher:
         m.quotes = _abi.QUOTES_FN(_quotes_cb(obj))
         m._keep += (m.quotes,)
     m._keep += _set_parity_hooks(m, obj)
+    m._keep += _set_stop_hooks(m, obj)
     return m
 
 
@@ -436,7 +481,7 @@ class Cluster:
     def c_matcher(self) -> MeMatcher:
         """me_cluster_matcher: the service on rank 0 is created over it (two slices in flight)."""
         if self._cm is None:
-            m = MeMatcher()
+            m = _abi.MeMatcherStops()  # the whole struct: me_cluster_matcher clears it all and leaves the stop hooks NULL
             self._check(self.lib.me_cluster_matcher(self.h, C.byref(m)))
             self._cm = m
         return self._cm

@@ -19,7 +19,9 @@
 // Locks (always taken in this order, never the other way round):
 //   flush_mu  one flusher at a time: slices are matched in stream order
 //   eng_mu    every engine call (the engine is single-threaded): flush matching, book reads
-//   mu        the open slice, the closed-slice queue, the symbol table, the OID counter
+//   mu        the open slice, the closed-slice queue, the symbol table, the OID counter; the stops held, the
+//             SID counter (the flush thread takes it after eng_mu, or without it, to turn stop events into
+//             orders: never the other way round)
 //   pq_mu     the matched-slice queue between the two stages
 //   live_mu   resting orders' owners and remainders (cancel ownership, OrderUpdate bookkeeping)
 //   upd_mu    the OrderUpdate queue
@@ -51,6 +53,8 @@
 #include "me_engine.h"
 #include "me_service.h"
 #include "me_service_feed.hpp"
+#include "me_service_stops.hpp"
+#include "me_stops.hpp"
 
 namespace {
 
@@ -151,6 +155,39 @@ struct Pending {
 // rejected (BAD_SYMBOL -> an OrderUpdate REJECTED) without taking a book for it.
 constexpr uint32_t kNoBook = 0xFFFFFFFFu;
 
+// A stop order the service holds: QUEUED (accepted, its boundary not applied yet) or ARMED (in the backend's
+// table). It leaves the table when its cancel is confirmed or its event is processed.
+struct Stop {
+  std::string client;
+  std::string symbol;
+  uint32_t sid = 0;  // its book (reference-counted like a live order's: a book with a stop is never handed over)
+  int32_t side = 0, type = 0, tif = 0;
+  int64_t stop_px = 0, limit_px = 0;
+  int32_t qty = 0;
+  uint8_t kind = 0;
+  bool armed = false;
+};
+
+// One stop operation at a slice boundary, in submission order. An add carries the stop as accepted; a cancel
+// the requester, and what the service knew of the target when it was asked (for the rejection's update).
+struct StopOp {
+  bool cancel = false;
+  bool unknown = false;  // a cancel of an id not issued yet when it was accepted: rejected without asking
+  uint64_t id = 0;
+  std::string client;  // add: the owner; cancel: the requester
+  Stop stop;           // add: the stop; cancel: the target as known at the request (symbol "" if unknown)
+};
+
+// A change to the `stops` table that commits with a slice's transaction.
+struct StopRow {
+  int32_t state = 0;  // ME_SS_ARMED: insert (from `stop`); ME_SS_CANCELED / ME_SS_TRIGGERED: update
+  uint64_t id = 0;
+  uint64_t oid = 0;   // TRIGGERED: the order the stop became (a record of the same slice)
+  int64_t trigger_px = 0;
+  std::string client;
+  Stop stop;
+};
+
 // One time slice: the SoA handed to the engine + the host-only fields persistence needs.
 struct Slice {
   std::vector<uint64_t> seq;
@@ -159,14 +196,23 @@ struct Slice {
   std::vector<uint32_t> sid;
   std::vector<uint8_t> kind;
   std::vector<Pending> meta;
+  std::vector<StopOp> pre;     // the boundary in front of the slice: applied right before it is submitted
+  std::vector<StopRow> srows;  // stop rows of its transaction: its boundary's, and its triggered orders'
   int64_t opened_us = 0;
   bool recovery = false;  // resting orders replayed from the DB at create: their rows already exist
   size_t size() const { return seq.size(); }
-  // The first k records become their own slice; this one keeps the rest.
+  // The first k records become their own slice; this one keeps the rest. The boundary (and its rows) stays in
+  // front of the first part; a triggered stop's row goes with its order's record.
   Slice take_prefix(size_t k) {
     Slice p;
     p.opened_us = opened_us;
     p.recovery = recovery;
+    p.pre = std::move(pre);
+    pre.clear();
+    const uint64_t last = k ? seq[k - 1] : 0;
+    std::vector<StopRow> rest;
+    for (auto& r : srows) (r.state != ME_SS_TRIGGERED || r.oid <= last ? p.srows : rest).push_back(std::move(r));
+    srows = std::move(rest);
     auto cut = [k](auto& src, auto& dst) {
       dst.assign(std::make_move_iterator(src.begin()), std::make_move_iterator(src.begin() + k));
       src.erase(src.begin(), src.begin() + k);
@@ -224,6 +270,10 @@ struct Backend {
   decltype(me_matcher::trades) trades = nullptr;
   decltype(me_matcher::order_query) order_query = nullptr;
   decltype(me_matcher::order_preview) order_preview = nullptr;
+  decltype(me_matcher::stops_enable) stops_enable = nullptr;  // the four together, or no stop orders
+  decltype(me_matcher::stops_add) stops_add = nullptr;
+  decltype(me_matcher::stops_cancel) stops_cancel = nullptr;
+  decltype(me_matcher::stops_read) stops_read = nullptr;
   int (*mass_cancel)(void*, const uint32_t* symbols, const uint8_t* sides, size_t n, me_book_entry* out, size_t cap,
                      size_t* n_out, uint64_t* counts) = nullptr;
   std::string (*last_error)(void*) = nullptr;
@@ -235,7 +285,8 @@ struct Backend {
   // A failed submit other than ME_E_CAPACITY: the slice was taken and is lost (the service fails). Else only
   // ME_OK is "accepted" and every failure is a refusal that applied nothing.
   bool failure_loses_slice = false;
-  // The depth and trade feeds the service turned on go off when it is destroyed (the backend outlives it).
+  // The depth and trade feeds and the stop orders the service turned on go off when it is destroyed (the
+  // backend outlives it).
   bool feeds_off_at_destroy = false;
 };
 
@@ -268,6 +319,10 @@ Backend backend_of(me_engine* e) {
   b.trades = eng_call<me_trades_read>;
   b.order_query = eng_call<me_order_query>;
   b.order_preview = eng_call<me_order_preview>;
+  b.stops_enable = eng_call<me_stops_enable>;
+  b.stops_add = eng_call<me_stops_add>;
+  b.stops_cancel = eng_call<me_stops_cancel>;
+  b.stops_read = eng_call<me_stops_read>;
   b.mass_cancel = eng_call<me_mass_cancel>;
   b.last_error = [](void* e) {
     char t[512];
@@ -304,6 +359,12 @@ Backend backend_of(const me_matcher* m) {
   b.trades = m->trades;
   b.order_query = m->order_query;
   b.order_preview = m->order_preview;
+  if (m->stops_enable && m->stops_add && m->stops_cancel && m->stops_read) {
+    b.stops_enable = m->stops_enable;
+    b.stops_add = m->stops_add;
+    b.stops_cancel = m->stops_cancel;
+    b.stops_read = m->stops_read;
+  }
   b.last_error = [](void*) { return std::string("matcher failed"); };
   b.fill_bound = [](const Backend& b, uint64_t n) { return b.max_resting + 2 * n; };
   b.num_symbols = m->num_symbols;
@@ -373,6 +434,17 @@ struct me_service {
   me::ServiceFeed<me_trade_update, sizeof(me_trade_update::symbol) - 1> tr;
   std::unordered_map<std::string, std::pair<int64_t, uint64_t>> tr_cum;
   uint64_t nsub = 0;  // slices the backend accepted since create (eng_mu): slice k's events are stamped k
+  // --- stop orders (me_service_stops.hpp). mu: whether they are on, the SID counter, the stops held, the
+  // capacity mirror. flush_mu: the events read and held back, the slices collected. upd_mu: the stop updates.
+  uint64_t stops_cap = 0;  // 0: off
+  uint64_t next_sid = 1;
+  std::map<uint64_t, Stop> stops;  // QUEUED and ARMED, ascending id
+  me::StopLedger stop_ledger;
+  uint64_t stops_triggered = 0;
+  uint64_t stops_recovered = 0;
+  me::StopHold stop_hold;
+  uint64_t ncol = 0;  // slices collected since create: an event is due once its stamp is <= ncol
+  std::deque<me_stop_update> stop_updates;
   // --- background flusher
   std::thread flusher;
   std::condition_variable cv;  // with mu
@@ -387,6 +459,8 @@ struct me_service {
   sqlite3_stmt* st_reduce = nullptr;  // an earlier slice's order, reduced in place: remaining only
   sqlite3_stmt* st_ins_k = nullptr;   // kRows-row INSERT INTO orders
   sqlite3_stmt* st_fill_k = nullptr;  // kRows-row INSERT INTO fills
+  sqlite3_stmt* st_stop_ins = nullptr;  // the `stops` table (me_service_stops_enable prepares them)
+  sqlite3_stmt* st_stop_upd = nullptr;
   bool failed = false;  // the engine lost a slice it had accepted: nothing more can be matched
   // --- err_mu
   mutable std::mutex err_mu;
@@ -401,9 +475,11 @@ struct me_service {
 };
 
 static void close_db(me_service* s) {
-  for (sqlite3_stmt* st : {s->st_ins, s->st_upd, s->st_fill, s->st_maker, s->st_reduce, s->st_ins_k, s->st_fill_k})
+  for (sqlite3_stmt* st : {s->st_ins, s->st_upd, s->st_fill, s->st_maker, s->st_reduce, s->st_ins_k, s->st_fill_k,
+                           s->st_stop_ins, s->st_stop_upd})
     if (st) g_sql.finalize(st);
   s->st_ins = s->st_upd = s->st_fill = s->st_maker = s->st_reduce = s->st_ins_k = s->st_fill_k = nullptr;
+  s->st_stop_ins = s->st_stop_upd = nullptr;
   if (s->db) g_sql.close(s->db);
   s->db = nullptr;
 }
@@ -653,6 +729,10 @@ struct Inflight {
   bool done = false;  // outputs already here (a matcher without submit / collect matches at once)
   std::vector<me_order_result> res;
   std::vector<me_fill> tape;
+  // Stop updates of a boundary applied while this slice was in flight: queued once the slice is collected and
+  // its events processed, where a backend with one slice in flight queues them (the stream's order, not the
+  // pipeline's).
+  std::vector<me_stop_update> post;
 };
 
 // Hand one slice to the backend (eng_mu held). accepted = the backend took it (a later failure loses
@@ -826,9 +906,10 @@ static int tr_pull(me_service* s) {
       });
 }
 
-// Close the open slice (mu held).
+// Close the open slice (mu held). One without records but with a boundary in front of it closes too: a
+// boundary-only slice, which the flush path applies and never submits.
 static void close_open(me_service* s) {
-  if (!s->open.size()) return;
+  if (!s->open.size() && s->open.pre.empty()) return;
   s->closed_records += s->open.size();
   s->closed.push_back(std::move(s->open));
   s->open = Slice{};
@@ -838,7 +919,7 @@ static void close_open(me_service* s) {
 // Append a record to the open slice (mu held); a full slice is closed and handed to the flusher.
 static void append(me_service* s, uint64_t seq, int64_t px, int32_t qty, uint32_t sid, uint8_t kind, Pending&& m) {
   Slice& o = s->open;
-  if (!o.size()) o.opened_us = mono_us();
+  if (!o.size() && o.pre.empty()) o.opened_us = mono_us();  // (a boundary started the clock already)
   o.seq.push_back(seq);
   o.px.push_back(px);
   o.qty.push_back(qty);
@@ -982,6 +1063,162 @@ extern "C" int me_service_cancel_order(me_service* s, const me_cancel_request* r
 
 extern "C" int me_service_reduce_order(me_service* s, const me_reduce_request* r, me_order_response* resp) {
   return cancel_or_reduce(s, r->client_id, r->symbol, r->order_id, true, r->quantity, resp);
+}
+
+// ---- stop orders: the request path (the flush path's half is further down) ------------------------------
+static_assert(sizeof(me_stop_update) == 200, "me_stop_update layout");
+
+static me_stop_update stop_update(uint64_t id, const std::string& client, const Stop& st, int32_t state,
+                                  uint64_t oid = 0, int64_t trigger_px = 0) {
+  me_stop_update u;
+  memset(&u, 0, sizeof u);
+  put(u.stop_id, sizeof u.stop_id, me::print_sid(id));
+  if (oid) put(u.order_id, sizeof u.order_id, "OID-" + std::to_string(oid));
+  put(u.client_id, sizeof u.client_id, client);
+  put(u.symbol, sizeof u.symbol, st.symbol);
+  u.state = state;
+  u.scale = 4;
+  u.stop_price = st.stop_px;
+  u.limit_price = st.limit_px;
+  u.trigger_price = trigger_px;
+  u.quantity = st.qty;
+  u.kind = st.kind;
+  return u;
+}
+
+// A stop operation takes its place in the stream (mu held): behind every record submitted so far, in the
+// boundary in front of the next slice.
+static void boundary_add(me_service* s, StopOp&& op) {
+  if (s->open.size()) close_open(s);
+  if (s->open.pre.empty()) s->open.opened_us = mono_us();
+  s->open.pre.push_back(std::move(op));
+  s->cv.notify_all();
+}
+
+extern "C" int me_service_submit_stop(me_service* s, const me_stop_request* r, me_order_response* resp) {
+  if (!resp) return 0;
+  memset(resp, 0, sizeof(*resp));
+  if (!s || !r) {
+    put(resp->error_message, sizeof resp->error_message, "stop orders are not enabled");
+    return 0;
+  }
+  auto refuse = [&](const char* why, int32_t grpc = 0) {
+    resp->grpc_status = grpc;
+    put(resp->error_message, sizeof resp->error_message, why);
+    return 0;
+  };
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (!s->stops_cap) return refuse("stop orders are not enabled");
+  const char* symbol = r->symbol ? r->symbol : "";
+  if (!symbol[0]) return refuse("symbol is required");
+  if (r->quantity <= 0) return refuse("quantity must be > 0");
+  const bool limit = r->order_type == ME_TYPE_LIMIT;
+  if (limit && r->price <= 0) return refuse("price must be > 0 for LIMIT");
+  if (r->tif < ME_TIF_GTC || r->tif > ME_TIF_POST_ONLY || (r->tif == ME_TIF_POST_ONLY && !limit))
+    return refuse("invalid time in force");
+  int64_t q4 = 0, stop_q4 = 0;
+  int nr = limit ? me_normalize_to_q4(r->price, r->scale, &q4) : 0;
+  if (nr == 0) nr = me_normalize_to_q4(r->stop_price, r->scale, &stop_q4);
+  if (nr != 0) return refuse(nr == 1 ? "scale out of range" : (nr == 2 ? "overflow" : "underflow"), 2);
+  if (r->side != ME_SIDE_BUY && r->side != ME_SIDE_SELL) return refuse("DB insert failed");
+  if (!s->stop_ledger.room(1, s->stops_cap)) return refuse("stop capacity exhausted", 8);
+  const std::string sym(symbol);
+  uint32_t sid = 0;
+  if (!intern(s, sym, sid)) return refuse("symbol capacity exhausted", 8);
+  const uint64_t id = s->next_sid++;
+  StopOp op;
+  op.id = id;
+  op.client = r->client_id ? r->client_id : "";
+  Stop& st = op.stop;
+  st.client = op.client;
+  st.symbol = sym;
+  st.sid = sid;
+  st.side = r->side;
+  st.type = limit ? ME_TYPE_LIMIT : ME_TYPE_MARKET;
+  st.tif = r->tif;
+  st.stop_px = stop_q4;
+  st.limit_px = q4;
+  st.qty = r->quantity;
+  st.kind = ME_KIND_TIF(r->side, st.type, ME_OP_NEW, r->tif);
+  s->stops.emplace(id, st);
+  s->stop_ledger.accepted++;
+  ref_add(s, sid, 1);  // the stop's own count, until its cancel is confirmed or its event processed
+  put(resp->order_id, sizeof resp->order_id, me::print_sid(id));
+  resp->success = 1;
+  boundary_add(s, std::move(op));
+  return 0;
+}
+
+extern "C" int me_service_cancel_stop(me_service* s, const me_stop_cancel_request* r, me_order_response* resp) {
+  if (!resp) return 0;
+  memset(resp, 0, sizeof(*resp));
+  auto refuse = [&](const char* why) {
+    put(resp->error_message, sizeof resp->error_message, why);
+    return 0;
+  };
+  if (!s || !r) return refuse("stop orders are not enabled");
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (!s->stops_cap) return refuse("stop orders are not enabled");
+  const uint64_t target = me::parse_sid(r->stop_id);
+  if (!target) return refuse("stop_id is invalid");
+  StopOp op;
+  op.cancel = true;
+  op.id = target;
+  op.client = r->client_id ? r->client_id : "";
+  op.unknown = target >= s->next_sid;
+  auto it = s->stops.find(target);
+  if (it != s->stops.end()) {
+    if (it->second.client != op.client) return refuse("stop belongs to another client");
+    op.stop = it->second;
+  }
+  put(resp->order_id, sizeof resp->order_id, me::print_sid(target));
+  resp->success = 1;
+  boundary_add(s, std::move(op));
+  return 0;
+}
+
+extern "C" int me_service_stop_updates(me_service* s, const char* client_id, me_stop_update* out, size_t cap,
+                                       size_t* n) {
+  if (n) *n = 0;
+  if (!s || (cap && !out)) return ME_E_INVALID;
+  std::lock_guard<std::mutex> lk(s->upd_mu);
+  size_t k = 0;
+  const bool all = !client_id || !client_id[0];
+  std::deque<me_stop_update> keep;
+  for (auto& u : s->stop_updates) {
+    if (k < cap && (all || strncmp(u.client_id, client_id, sizeof u.client_id) == 0))
+      out[k++] = u;
+    else
+      keep.push_back(u);
+  }
+  s->stop_updates.swap(keep);
+  if (n) *n = k;
+  return ME_OK;
+}
+
+extern "C" int me_service_stops(me_service* s, const char* client_id, me_stop_update* out, size_t cap, size_t* n) {
+  if (n) *n = 0;
+  if (!s || (cap && !out)) return ME_E_INVALID;
+  const bool all = !client_id || !client_id[0];
+  std::lock_guard<std::mutex> lk(s->mu);
+  size_t k = 0;
+  for (const auto& kv : s->stops) {
+    if (!all && kv.second.client != client_id) continue;
+    if (k < cap) out[k] = stop_update(kv.first, kv.second.client, kv.second, kv.second.armed ? ME_SS_ARMED : ME_SS_QUEUED);
+    ++k;
+  }
+  if (n) *n = k;
+  return ME_OK;
+}
+
+extern "C" int me_service_stop_stats(const me_service* s, uint64_t* live, uint64_t* triggered, uint64_t* recovered) {
+  if (!s) return ME_E_INVALID;
+  me_service* m = const_cast<me_service*>(s);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (live) *live = m->stops.size();
+  if (triggered) *triggered = m->stops_triggered;
+  if (recovered) *recovered = m->stops_recovered;
+  return ME_OK;
 }
 
 extern "C" size_t me_service_pending(const me_service* s) {
@@ -1309,6 +1546,35 @@ static bool persist(me_service* s, const Slice& sl, const me_order_result* res, 
       step(s->st_fill, "insert fill");
     }
   }
+  // ---- stop rows: the boundary's ARMED inserts and CANCELED updates, and TRIGGERED for the stops whose orders
+  // this slice carries (their `orders` rows went in above: one transaction)
+  for (size_t k = 0; ok && k < sl.srows.size() && s->st_stop_ins && s->st_stop_upd; ++k) {
+    const StopRow& r = sl.srows[k];
+    if (r.state == ME_SS_ARMED) {
+      sqlite3_stmt* st = s->st_stop_ins;
+      g_sql.bind_int64(st, 1, (long long)r.id);
+      g_sql.bind_text(st, 2, r.client.c_str(), -1, SQLITE_TRANSIENT);
+      g_sql.bind_text(st, 3, r.stop.symbol.c_str(), -1, SQLITE_TRANSIENT);
+      g_sql.bind_int64(st, 4, r.stop.side);
+      g_sql.bind_int64(st, 5, r.stop.type);
+      g_sql.bind_int64(st, 6, r.stop.tif);
+      g_sql.bind_int64(st, 7, r.stop.stop_px);
+      g_sql.bind_int64(st, 8, r.stop.limit_px);
+      g_sql.bind_int64(st, 9, r.stop.qty);
+      g_sql.bind_int64(st, 10, ME_SS_ARMED);
+      g_sql.bind_int64(st, 11, ts);
+      step(st, "insert stop");
+    } else {
+      sqlite3_stmt* st = s->st_stop_upd;
+      const std::string soid = r.oid ? "OID-" + std::to_string(r.oid) : "";
+      g_sql.bind_int64(st, 1, r.state);
+      g_sql.bind_text(st, 2, soid.c_str(), -1, SQLITE_TRANSIENT);
+      g_sql.bind_int64(st, 3, r.trigger_px);
+      g_sql.bind_int64(st, 4, ts);
+      g_sql.bind_int64(st, 5, (long long)r.id);
+      step(st, "update stop");
+    }
+  }
   if (!ok) {
     g_sql.exec(s->db, "ROLLBACK", nullptr, nullptr, nullptr);
     return false;
@@ -1446,6 +1712,165 @@ static int on_refused(me_service* s, Slice&& sl, FlushOut* out, size_t& taken) {
   return ME_OK;
 }
 
+// ---- stop orders: the flush path's half (flush_mu held throughout) --------------------------------------
+static void push_stop_updates(me_service* s, const std::vector<me_stop_update>& ups) {
+  if (ups.empty()) return;
+  std::lock_guard<std::mutex> lu(s->upd_mu);
+  for (const me_stop_update& u : ups) {
+    if (s->stop_updates.size() >= kMaxQueuedUpdates) {  // nobody drains the stream: drop the oldest, loudly
+      s->stop_updates.pop_front();
+      if (s->updates_dropped++ == 0)  // (one count for both streams: me_service_updates_dropped)
+        s->fail(ME_OK, "stop update queue full (2^24 undrained events): dropping the oldest; drain with "
+                       "me_service_stop_updates");
+    }
+    s->stop_updates.push_back(u);
+  }
+}
+
+// Read the backend's stop events until none is left (eng_mu held) into the hold-back buffer.
+static int stops_pull(me_service* s) {
+  me_stop_event buf[128];
+  for (;;) {
+    size_t n = 0, left = 0;
+    const int rc = s->be.stops_read(s->be.ctx, buf, sizeof buf / sizeof buf[0], &n, &left);
+    if (rc != ME_OK) return s->fail(rc, "stop orders: reading the backend's events failed: " + backend_err(s));
+    s->stop_hold.push(buf, n);
+    if (!left) return ME_OK;
+  }
+}
+
+// Process the events whose slice has been collected, in ring order, under the submit lock (lock order:
+// flush_mu, eng_mu, mu; eng_mu is not needed here): each becomes the next order of the stream.
+static void stops_process(me_service* s, std::vector<me_stop_update>& ups) {
+  const std::vector<me_stop_event> due = s->stop_hold.take_due(s->ncol);
+  if (due.empty()) return;
+  std::lock_guard<std::mutex> lk(s->mu);
+  for (const me_stop_event& ev : due) {
+    auto it = s->stops.find(ev.id);
+    if (it == s->stops.end()) continue;  // (not reachable: every stop of the backend's table is in this one)
+    const Stop st = it->second;
+    const uint64_t oid = s->next_id++;
+    const bool never_rests = ((ev.kind >> 2) & 1u) != 0 || (((ev.kind >> 4) ^ (ev.kind >> 5)) & 1u) != 0;
+    if (!never_rests) {
+      std::lock_guard<std::mutex> lv(s->live_mu);
+      s->live[oid] = Live{st.client, st.symbol, ev.qty, ev.symbol};
+    }
+    ref_add(s, ev.symbol, 1);  // the order's count (SubmitOrder's), before the stop's goes
+    StopRow row;
+    row.state = ME_SS_TRIGGERED;
+    row.id = ev.id;
+    row.oid = oid;
+    row.trigger_px = ev.trigger_px_q4;
+    s->open.srows.push_back(std::move(row));  // commits with the slice that carries the order's row
+    append(s, oid, ev.limit_px_q4, ev.qty, ev.symbol, ev.kind, Pending{st.client, st.symbol, st.side, false, 0});
+    ref_add(s, st.sid, -1);
+    s->stops.erase(it);
+    s->stop_ledger.closed++;
+    s->stops_triggered++;
+    ups.push_back(stop_update(ev.id, st.client, st, ME_SS_TRIGGERED, oid, ev.trigger_px_q4));
+  }
+}
+
+// Apply the boundary in front of a slice, in submission order: runs of adds as one stops_add, runs of cancels as
+// one stops_cancel (no slice is in flight then: the caller collected them). The boundary's rows join the
+// slice's transaction, its updates go to `ups`.
+static int apply_boundary(me_service* s, Slice& sl, std::vector<me_stop_update>& ups) {
+  const std::vector<StopOp> ops = std::move(sl.pre);
+  sl.pre.clear();
+  std::vector<uint8_t> is_cancel(ops.size());
+  for (size_t i = 0; i < ops.size(); ++i) is_cancel[i] = ops[i].cancel;
+  for (const me::StopRun& run : me::stop_runs(is_cancel)) {
+    const size_t n = run.end - run.begin;
+    if (!run.cancel) {
+      std::vector<me_stop> recs(n);
+      memset(recs.data(), 0, n * sizeof(me_stop));
+      for (size_t i = 0; i < n; ++i) {
+        const StopOp& op = ops[run.begin + i];
+        recs[i].id = op.id;
+        recs[i].stop_px_q4 = op.stop.stop_px;
+        recs[i].limit_px_q4 = op.stop.limit_px;
+        recs[i].qty = op.stop.qty;
+        recs[i].symbol = op.stop.sid;
+        recs[i].kind = op.stop.kind;
+      }
+      int rc;
+      {
+        std::lock_guard<std::mutex> le(s->eng_mu);
+        rc = s->be.stops_add(s->be.ctx, recs.data(), n);
+      }
+      if (rc != ME_OK) {  // the host's mirror of the bound admitted them: the backend's table is not the service's
+        s->failed = true;
+        return s->fail(rc, "stop orders: the backend refused stops the service had admitted: " + backend_err(s));
+      }
+      {
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (size_t i = 0; i < n; ++i) {
+          auto it = s->stops.find(ops[run.begin + i].id);
+          if (it != s->stops.end()) it->second.armed = true;
+        }
+      }
+      for (size_t i = 0; i < n; ++i) {
+        const StopOp& op = ops[run.begin + i];
+        ups.push_back(stop_update(op.id, op.client, op.stop, ME_SS_ARMED));
+        StopRow row;
+        row.state = ME_SS_ARMED;
+        row.id = op.id;
+        row.client = op.client;
+        row.stop = op.stop;
+        sl.srows.push_back(std::move(row));
+      }
+      continue;
+    }
+    // cancels: the ids the backend may know, sorted, each once; an id from the future (never issued when the
+    // cancel was accepted) is not asked about — it may name somebody's stop by now
+    std::vector<uint64_t> ids;
+    std::vector<size_t> at(n, SIZE_MAX);  // operation -> its index among the asked ones
+    for (size_t i = 0; i < n; ++i) {
+      if (ops[run.begin + i].unknown) continue;
+      at[i] = ids.size();
+      ids.push_back(ops[run.begin + i].id);
+    }
+    const me::CancelRun cr = me::cancel_run(ids.data(), ids.size());
+    std::vector<uint8_t> found(cr.ids.size() + 1, 0);
+    int rc;
+    {
+      std::lock_guard<std::mutex> le(s->eng_mu);
+      rc = s->be.stops_cancel(s->be.ctx, cr.ids.data(), cr.ids.size(), found.data());
+      if (rc != ME_OK) {
+        s->failed = true;
+        return s->fail(rc, "stop orders: the backend's stops_cancel failed: " + backend_err(s));
+      }
+      rc = stops_pull(s);
+    }
+    if (rc != ME_OK) {
+      s->failed = true;  // the cancels are applied and their answers lost
+      return rc;
+    }
+    stops_process(s, ups);  // TRIGGERED first: the owner of a stop that had triggered sees it before the rejection
+    std::lock_guard<std::mutex> lk(s->mu);
+    for (size_t i = 0; i < n; ++i) {
+      const StopOp& op = ops[run.begin + i];
+      const bool hit = at[i] != SIZE_MAX && cr.first[at[i]] && found[cr.slot[at[i]]];
+      if (!hit) {
+        ups.push_back(stop_update(op.id, op.client, op.stop, ME_SS_CANCEL_REJECTED));
+        continue;
+      }
+      auto it = s->stops.find(op.id);
+      if (it != s->stops.end()) {
+        ref_add(s, it->second.sid, -1);
+        s->stops.erase(it);
+      }
+      s->stop_ledger.closed++;
+      ups.push_back(stop_update(op.id, op.client, op.stop, ME_SS_CANCELED));
+      StopRow row;
+      row.state = ME_SS_CANCELED;
+      row.id = op.id;
+      sl.srows.push_back(std::move(row));
+    }
+  }
+  return ME_OK;
+}
+
 // Flush the closed slices (and the open one when take_open), oldest first, two in flight: slice k+1 is
 // submitted before slice k is collected. `rec_limit` bounds the records taken (those present when the
 // caller checked its output capacity). With `wait`, returns once the persister has emitted every
@@ -1478,6 +1903,14 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
     s->inflight_records -= n;
     return s->fail(r, what + backend_err(s));
   };
+  // A failure before a taken slice was handed to the backend: it goes back to the head of the queue.
+  auto lost_one = [&](int r, Inflight& f) {
+    std::lock_guard<std::mutex> lk(s->mu);
+    s->inflight_records -= f.sl.size();
+    s->closed_records += f.sl.size();
+    s->closed.push_front(std::move(f.sl));
+    return r;
+  };
   auto finish_oldest = [&]() -> int {
     int r;
     {
@@ -1486,19 +1919,29 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
       each_feed(s, [&](auto& f, auto pull) {
         if (r == ME_OK && f.on) (void)pull(s);  // (a failed read is in last_error; the slice is matched)
       });
+      if (r == ME_OK && s->stops_cap) (void)stops_pull(s);
     }
     if (r != ME_OK) return lost(r, "engine lost an accepted slice: ");
+    ++s->ncol;
     Inflight& f = fl.front();
+    const std::vector<me_stop_update> post = std::move(f.post);
     deliver(s, std::move(f.sl), std::move(f.res), std::move(f.tape), out);
     fl.pop_front();
+    if (s->stops_cap) {  // the events this slice was waited for: each becomes an order of the open slice
+      std::vector<me_stop_update> ups;
+      stops_process(s, ups);
+      push_stop_updates(s, ups);
+    }
+    push_stop_updates(s, post);
     return ME_OK;
   };
   size_t taken = 0;
-  while (taken < rec_limit) {
+  for (;;) {
     Inflight f;
     {
       std::lock_guard<std::mutex> lk(s->mu);
       if (s->closed.empty()) break;
+      if (taken >= rec_limit && s->closed.front().size()) break;  // (a boundary-only slice holds no record)
       f.sl = std::move(s->closed.front());
       s->closed.pop_front();
       s->closed_records -= f.sl.size();
@@ -1511,6 +1954,25 @@ static int flush_closed(me_service* s, bool take_open, size_t rec_limit, FlushOu
     }
     bool accepted = false;
     int r;
+    if (!f.sl.pre.empty()) {  // the boundary in front of the slice (a slice split later keeps none: applied once)
+      bool any_cancel = false;
+      for (const StopOp& op : f.sl.pre) any_cancel |= op.cancel;
+      // a cancel's answer depends on what the slices before it triggered: they are collected first
+      while (any_cancel && !fl.empty())
+        if ((r = finish_oldest()) != ME_OK) return lost_one(r, f);
+      std::vector<me_stop_update> ups;
+      if ((r = apply_boundary(s, f.sl, ups)) != ME_OK) return lost_one(r, f);
+      if (fl.empty())
+        push_stop_updates(s, ups);
+      else
+        fl.back().post.insert(fl.back().post.end(), ups.begin(), ups.end());
+    }
+    if (!f.sl.size()) {  // a boundary with no slice behind it: its rows go to the persister in stream order
+      while (!fl.empty())
+        if ((r = finish_oldest()) != ME_OK) return r;
+      if (!f.sl.srows.empty()) deliver(s, std::move(f.sl), {}, {}, out);
+      continue;
+    }
     {
       std::lock_guard<std::mutex> le(s->eng_mu);
       r = backend_submit(s, f, accepted);
@@ -1590,11 +2052,12 @@ static void flusher_main(me_service* s) {
   int64_t backoff_us = 0, retry_at = 0;
   while (!s->stop) {
     const int64_t now = mono_us();
-    const bool due = s->open.size() && now - s->open.opened_us >= s->interval_us;
+    const bool opened = s->open.size() || !s->open.pre.empty();  // records, or a boundary waiting to be applied
+    const bool due = opened && now - s->open.opened_us >= s->interval_us;
     if (due) close_open(s);
     const bool blocked = backoff_us && now < retry_at;
     if (s->closed.empty() || blocked) {
-      int64_t wait = s->open.size() ? s->open.opened_us + s->interval_us - now : s->interval_us;
+      int64_t wait = opened && !due ? s->open.opened_us + s->interval_us - now : s->interval_us;
       if (blocked) wait = std::min(wait, retry_at - now);
       s->cv.wait_for(lk, std::chrono::microseconds(wait > 0 ? wait : 1));
       continue;
@@ -1658,6 +2121,7 @@ extern "C" void me_service_destroy(me_service* s) {
     std::lock_guard<std::mutex> le(s->eng_mu);
     if (s->dp.on && s->be.depth_enable) (void)s->be.depth_enable(s->be.ctx, 0, 0);
     if (s->tr.on && s->be.trades_enable) (void)s->be.trades_enable(s->be.ctx, 0);
+    if (s->stops_cap && s->be.stops_enable) (void)s->be.stops_enable(s->be.ctx, 0);
   }
   close_db(s);
   delete s;
@@ -2046,6 +2510,179 @@ extern "C" int me_service_trades_stream(me_service* s, const char* symbol, me_tr
   if (!s->tr.on) return s->fail(ME_E_INVALID, "trade stream: not subscribed (me_service_trades_subscribe)");
   const size_t k = s->tr.take(symbol, cap, [&](const std::string&, const me_trade_update& u) { *out++ = u; });
   if (n) *n = k;
+  return ME_OK;
+}
+
+// The `stops` table (created at the first enable: a database that never enables stops keeps the reference's
+// schema) and its two statements.
+static bool open_stops_table(me_service* s, std::string& err) {
+  if (s->st_stop_ins && s->st_stop_upd) return true;
+  auto chk = [&](int rc, const char* what) {
+    if (sql_ok(rc)) return true;
+    err = s->sql_err(what);
+    return false;
+  };
+  auto drop = [&] {  // both statements or neither: persist() uses the pair
+    for (sqlite3_stmt** st : {&s->st_stop_ins, &s->st_stop_upd}) {
+      if (*st) g_sql.finalize(*st);
+      *st = nullptr;
+    }
+  };
+  drop();
+  const bool ok = chk(g_sql.exec(s->db,
+                        "CREATE TABLE IF NOT EXISTS stops ("
+                        "  stop_id INTEGER PRIMARY KEY, client_id TEXT NOT NULL, symbol TEXT NOT NULL,"
+                        "  side INTEGER NOT NULL CHECK (side IN (1,2)), order_type INTEGER NOT NULL, tif INTEGER NOT NULL,"
+                        "  stop_price INTEGER NOT NULL, limit_price INTEGER NOT NULL,"
+                        "  quantity INTEGER NOT NULL CHECK (quantity > 0), status INTEGER NOT NULL,"
+                        "  order_id TEXT NOT NULL DEFAULT '', trigger_price INTEGER NOT NULL DEFAULT 0,"
+                        "  updated_ts INTEGER NOT NULL);",
+                        nullptr, nullptr, nullptr),
+             "stops schema") &&
+         chk(g_sql.prepare_v2(s->db,
+                              "INSERT INTO stops(stop_id, client_id, symbol, side, order_type, tif, stop_price, "
+                              "limit_price, quantity, status, updated_ts) VALUES (?,?,?,?,?,?,?,?,?,?,?)",
+                              -1, &s->st_stop_ins, nullptr),
+             "prepare stop insert") &&
+         chk(g_sql.prepare_v2(s->db, "UPDATE stops SET status=?, order_id=?, trigger_price=?, updated_ts=? WHERE stop_id=?",
+                              -1, &s->st_stop_upd, nullptr),
+             "prepare stop update");
+  if (!ok) drop();
+  return ok;
+}
+
+extern "C" int me_service_stops_enable(me_service* s, uint64_t cap_stops) {
+  if (!s) return ME_E_INVALID;
+  if (!has_backend(s)) return s->fail(ME_E_STATE, "no engine");
+  const Backend& be = s->be;
+  if (!be.stops_enable) return s->fail(ME_E_INVALID, "stop orders: the matcher has no stop hooks");
+  if (cap_stops > me::STOPS_CAP_MAX) return s->fail(ME_E_INVALID, "stop orders: cap_stops above 2^22");
+  std::lock_guard<std::mutex> lf(s->flush_mu);  // no slice is in flight while it is held
+  if (s->failed) return s->fail(ME_E_STATE, "service failed: the engine lost an accepted slice");
+  auto backend_off = [&] {
+    std::lock_guard<std::mutex> le(s->eng_mu);
+    (void)be.stops_enable(be.ctx, 0);
+  };
+  if (!cap_stops) {  // off: the backend's table and events go, and what the service held of them
+    if (!s->stops_cap) return ME_OK;
+    backend_off();
+    {
+      std::lock_guard<std::mutex> lk(s->mu);
+      for (const auto& kv : s->stops) ref_add(s, kv.second.sid, -1);
+      s->stops.clear();
+      s->stop_ledger = me::StopLedger{};
+      s->stops_cap = 0;
+      s->stops_triggered = s->stops_recovered = 0;
+      s->open.pre.clear();  // operations not applied yet go with it
+      for (Slice& sl : s->closed) sl.pre.clear();
+    }
+    s->stop_hold = me::StopHold{};
+    std::lock_guard<std::mutex> lu(s->upd_mu);
+    s->stop_updates.clear();
+    return ME_OK;
+  }
+  if (s->stops_cap) return s->fail(ME_E_STATE, "stop orders are already enabled");
+  // the persister owns the DB while it has work: wait until it has none (or is stalled on a failed transaction)
+  std::vector<std::pair<uint64_t, Stop>> armed;
+  uint64_t next_sid = 1;
+  if (s->db) {
+    std::unique_lock<std::mutex> lq(s->pq_mu);
+    s->pq_cv.wait(lq, [&] { return s->pq_emitted == s->pq.size() && (s->pq.empty() || s->pq_stalled); });
+    std::string err;
+    if (!open_stops_table(s, err)) return s->fail(ME_E_SQLITE, "me_service_stops_enable: " + err);
+    sqlite3_stmt* q = nullptr;
+    if (!sql_ok(g_sql.prepare_v2(s->db, "SELECT COALESCE(MAX(stop_id), 0) + 1 FROM stops", -1, &q, nullptr)))
+      return s->fail(ME_E_SQLITE, "me_service_stops_enable: " + s->sql_err("prepare sid"));
+    if (g_sql.step(q) == SQLITE_ROW) next_sid = (uint64_t)g_sql.column_int64(q, 0);
+    g_sql.finalize(q);
+    q = nullptr;
+    if (!sql_ok(g_sql.prepare_v2(s->db,
+                                 "SELECT stop_id, client_id, symbol, side, order_type, tif, stop_price, limit_price, "
+                                 "quantity FROM stops WHERE status = 0 ORDER BY stop_id",
+                                 -1, &q, nullptr)))
+      return s->fail(ME_E_SQLITE, "me_service_stops_enable: " + s->sql_err("prepare stop recovery"));
+    while (g_sql.step(q) == SQLITE_ROW) {
+      Stop st;
+      const char* cl = (const char*)g_sql.column_text(q, 1);
+      const char* sy = (const char*)g_sql.column_text(q, 2);
+      st.client = cl ? cl : "";
+      st.symbol = sy ? sy : "";
+      st.side = (int32_t)g_sql.column_int64(q, 3);
+      st.type = g_sql.column_int64(q, 4) == ME_TYPE_LIMIT ? ME_TYPE_LIMIT : ME_TYPE_MARKET;
+      st.tif = (int32_t)g_sql.column_int64(q, 5);
+      st.stop_px = g_sql.column_int64(q, 6);
+      st.limit_px = g_sql.column_int64(q, 7);
+      const long long qty = g_sql.column_int64(q, 8);
+      const long long id = g_sql.column_int64(q, 0);
+      if (id <= 0 || qty <= 0 || qty > INT32_MAX || (st.side != ME_SIDE_BUY && st.side != ME_SIDE_SELL) ||
+          st.tif < ME_TIF_GTC || st.tif > ME_TIF_POST_ONLY || (st.tif == ME_TIF_POST_ONLY && st.type != ME_TYPE_LIMIT) ||
+          st.symbol.empty())
+        continue;  // (a row this service cannot have written)
+      st.qty = (int32_t)qty;
+      st.kind = ME_KIND_TIF(st.side, st.type, ME_OP_NEW, st.tif);
+      st.armed = true;
+      armed.emplace_back((uint64_t)id, std::move(st));
+    }
+    g_sql.finalize(q);
+  }
+  if (armed.size() > cap_stops)
+    return s->fail(ME_E_CAPACITY, "me_service_stops_enable: the DB holds " + std::to_string(armed.size()) +
+                                      " armed stops, more than cap_stops");
+  {
+    std::lock_guard<std::mutex> le(s->eng_mu);
+    const int rc = be.stops_enable(be.ctx, cap_stops);
+    if (rc != ME_OK) return s->fail(rc, "me_service_stops_enable: the backend's stops_enable failed: " + backend_err(s));
+  }
+  std::vector<me_stop> recs(armed.size());
+  if (!recs.empty()) memset(recs.data(), 0, recs.size() * sizeof(me_stop));
+  bool books = true;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    for (size_t i = 0; books && i < armed.size(); ++i) {
+      Stop& st = armed[i].second;
+      if (!intern(s, st.symbol, st.sid)) {
+        for (size_t j = 0; j < i; ++j) ref_add(s, armed[j].second.sid, -1);
+        books = false;
+        break;
+      }
+      ref_add(s, st.sid, 1);  // at once: the next name must not take this book over
+      recs[i].id = armed[i].first;
+      recs[i].stop_px_q4 = st.stop_px;
+      recs[i].limit_px_q4 = st.limit_px;
+      recs[i].qty = st.qty;
+      recs[i].symbol = st.sid;
+      recs[i].kind = st.kind;
+    }
+  }
+  if (!books) {
+    backend_off();
+    return s->fail(ME_E_CAPACITY, "me_service_stops_enable: the DB holds armed stops on more symbols than the "
+                                  "backend has books");
+  }
+  if (!recs.empty()) {
+    int rc;
+    {
+      std::lock_guard<std::mutex> le(s->eng_mu);
+      rc = be.stops_add(be.ctx, recs.data(), recs.size());
+    }
+    if (rc != ME_OK) {
+      const std::string why = backend_err(s);
+      for (auto& a : armed) ref_add(s, a.second.sid, -1);
+      backend_off();
+      return s->fail(rc, "me_service_stops_enable: re-adding the armed stops failed: " + why);
+    }
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  s->stops_cap = cap_stops;
+  // never backwards within one service: a SID handed out before an off / on is not issued again (the rows cover
+  // only stops whose boundary was applied, and an in-memory service has no rows at all)
+  s->next_sid = std::max(next_sid, s->next_sid);
+  s->stop_ledger = me::StopLedger{};
+  s->stop_ledger.accepted = armed.size();
+  s->stops_triggered = 0;
+  s->stops_recovered = armed.size();
+  s->stop_hold = me::StopHold{};
+  for (auto& a : armed) s->stops.emplace(a.first, std::move(a.second));
   return ME_OK;
 }
 

@@ -151,6 +151,79 @@ class MatchingEngineService:
                  "qty_better": o.qty_better, "orders_ahead": o.orders_ahead, "levels_better": o.levels_better}
                 for o in out[:n]]
 
+    # ---- stop orders (me_service.h "stop and stop-limit orders") ----
+    def _stop_call(self, what, rc):
+        if rc != 0:
+            e = ServiceError(f"{what} failed ({rc}): {self.last_error()}")
+            e.code = rc
+            raise e
+
+    def stops_enable(self, cap_stops: int):
+        """me_service_stops_enable: turn stop orders on with room for cap_stops stops (0: off), create the
+        `stops` table and re-arm the stops the database shows ARMED. ServiceError (code ME_E_INVALID) on a
+        matcher without the four stop hooks, ME_E_CAPACITY when the database holds more armed stops."""
+        self._stop_call("stops_enable", self.lib.me_service_stops_enable(self.h, int(cap_stops)))
+
+    def submit_stop(self, client_id, symbol, order_type, side, price, stop_price, scale, quantity, tif=0) -> dict:
+        """me_service_submit_stop: a stop (order_type MARKET) or stop-limit (LIMIT, `price` its limit) that
+        becomes an order of `side` once the symbol trades through stop_price. Answers like submit_order, with
+        order_id = "SID-<n>"; ARMED / TRIGGERED / CANCELED arrive through stop_updates()."""
+        req = _abi.MeStopRequest(client_id.encode(), symbol.encode(), order_type, side, price, stop_price, scale,
+                                 quantity, tif)
+        resp = MeOrderResponse()
+        self.lib.me_service_submit_stop(self.h, C.byref(req), C.byref(resp))
+        return {"order_id": resp.order_id.decode(), "success": bool(resp.success),
+                "error_message": resp.error_message.decode(), "grpc_status": resp.grpc_status}
+
+    def cancel_stop(self, client_id, stop_id) -> dict:
+        """me_service_cancel_stop: queue a cancel of a stop; CANCELED or CANCEL_REJECTED arrives as a stop
+        update once its boundary is applied."""
+        req = _abi.MeStopCancelRequest(client_id.encode(), stop_id.encode())
+        resp = MeOrderResponse()
+        self.lib.me_service_cancel_stop(self.h, C.byref(req), C.byref(resp))
+        return {"order_id": resp.order_id.decode(), "success": bool(resp.success),
+                "error_message": resp.error_message.decode(), "grpc_status": resp.grpc_status}
+
+    @staticmethod
+    def _stop_dict(u) -> dict:
+        return {"stop_id": u.stop_id.decode(), "order_id": u.order_id.decode(), "client_id": u.client_id.decode(),
+                "symbol": u.symbol.decode(), "state": u.state, "scale": u.scale, "stop_price": u.stop_price,
+                "limit_price": u.limit_price, "trigger_price": u.trigger_price, "quantity": u.quantity,
+                "kind": u.kind}
+
+    def stop_updates(self, client_id=None, cap=4096) -> list:
+        """me_service_stop_updates: drain the queued stop updates (one client's, or all) as dicts with stop_id,
+        order_id ("OID-<n>" once TRIGGERED), client_id, symbol, state (SS_*), scale, stop_price, limit_price,
+        trigger_price, quantity, kind."""
+        out = []
+        buf = (_abi.MeStopUpdate * cap)()
+        while True:
+            n = C.c_size_t(0)
+            self._stop_call("stop_updates", self.lib.me_service_stop_updates(
+                self.h, client_id.encode() if client_id else None, buf, cap, C.byref(n)))
+            out += [self._stop_dict(u) for u in buf[: n.value]]
+            if n.value < cap:
+                return out
+
+    def stops(self, client_id=None) -> list:
+        """me_service_stops: the client's (None: everybody's) QUEUED and ARMED stops in ascending stop id, as
+        stop_updates() shapes them."""
+        cid = client_id.encode() if client_id else None
+        n = C.c_size_t(0)
+        self._stop_call("stops", self.lib.me_service_stops(self.h, cid, None, 0, C.byref(n)))
+        while True:
+            cap = max(n.value, 1)
+            buf = (_abi.MeStopUpdate * cap)()
+            self._stop_call("stops", self.lib.me_service_stops(self.h, cid, buf, cap, C.byref(n)))
+            if n.value <= cap:
+                return [self._stop_dict(u) for u in buf[: n.value]]
+
+    def stop_stats(self) -> dict:
+        """me_service_stop_stats: stops QUEUED or ARMED now, events processed, stops re-armed from the database."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._stop_call("stop_stats", self.lib.me_service_stop_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"live": a.value, "triggered": b.value, "recovered": c.value}
+
     def order_updates(self, client_id=None, cap=1 << 16) -> list:
         """StreamOrderUpdates (proto:34,71-91): drain the queued OrderUpdate events (one client, or all)."""
         out = []

@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "matching_engine_amd", "csrc")
 FILES = [os.path.join(CSRC, f) for f in ("me_kernels.hip", "me_match_reg.hip", "me_side.hip", "me_snapshot.hip", "me_agg.hip",
                                          "me_engine.cpp", "me_gen.cpp", "me_service.cpp", "me_cluster.cpp", "me_bookread.hpp", "me_far.hpp",
-                                         "me_feed.hpp", "me_launch.hpp", "me_layout.hpp", "me_service_feed.hpp", "me_side.hpp", "me_stops.hpp",
+                                         "me_feed.hpp", "me_launch.hpp", "me_layout.hpp", "me_service_feed.hpp", "me_service_stops.hpp", "me_side.hpp", "me_stops.hpp",
                                          "me_wave.hpp")]
 FILES += [os.path.join(ROOT, "include", f) for f in ("me_engine.h", "me_service.h", "me_cluster.h")]
 FILES += [os.path.join(ROOT, "matching_engine_amd", "Makefile")]  # the compiler flags shape the kernels
