@@ -25,7 +25,7 @@ from tests.tif_model import Arrays, kind
 
 MAX = (1 << 31) - 1
 CHUNK = 16
-LS = (128, 256, 1024, 2048)  # the window depths of tests/test_reduce_gpu.PATHS
+LS = (128, 256, 1024, 2048)  # the window depths of tests/gpu_harness.PATHS
 
 
 def kd(side, market=False, tif=0, hi=0):

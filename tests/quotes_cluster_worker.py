@@ -1,4 +1,4 @@
-"""One rank of the quote-feed cluster check (launched by tests/test_quotes_service.py and
+"""One rank of the quote-feed cluster check (launched through tests/service_common.py by tests/test_quotes_service.py and
 tests/test_quotes_service_gpu.py). Rank 0 turns every shard's feed on (me_cluster_quotes_enable), sends a
 config-5-style stream through me_cluster_submit / collect and, after each collected slice, replays what
 me_cluster_quotes hands out into a table of quotes: it must equal the tops of ONE oracle book holding every

@@ -1,7 +1,7 @@
 """Stop orders through the service — TEST INFRASTRUCTURE ONLY (tests/test_stops_service.py on a CPU,
 tests/test_stops_service_gpu.py on the engine).
 
-`StopMatcher` is tests/test_quotes_service.py's FeedMatcher with me_matcher's four stop hooks over
+`StopMatcher` is tests/service_common.py's FeedMatcher with me_matcher's four stop hooks over
 tests/stops_model.StopModel: every matched slice's fills are fed to the model and one job runs behind each match,
 stamped with the slice number. `ServiceModel` replays the rules of include/me_service.h ("stop and stop-limit
 orders") in plain Python over an OracleBook and a StopModel. The scripts drive a service and return everything
@@ -12,7 +12,7 @@ from collections import deque
 import numpy as np
 
 from tests import stops_model as sm
-from tests.test_quotes_service import FeedMatcher
+from tests.service_common import FeedMatcher
 
 BUY, SELL = 1, 2
 LIMIT, MARKET = 0, 1

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
+from tests.gpu_harness import pipelined
 
 pytestmark = pytest.mark.gpu
 
@@ -55,18 +56,6 @@ def _sync(eng, ob, batches, ctx, symbols):
     assert eng.resting_count() == ob.resting() == eng.admission()["resting"], ctx
 
 
-def _pipelined(eng, batches, lag):
-    out, tickets = [None] * len(batches), []
-    for k, b in enumerate(batches):
-        tickets.append((k, eng.submit_host(b)))
-        while len(tickets) > lag:
-            j, t = tickets.pop(0)
-            out[j] = eng.collect(t)
-    for j, t in tickets:
-        out[j] = eng.collect(t)
-    return out
-
-
 def _check(eng, ob, batches, outs, ctx):
     for k, b in enumerate(batches):
         ro, fo = ob.submit(b)
@@ -91,7 +80,7 @@ def test_cx_config5_stream_every_batch(me, orc, cx_env, group, lag):
                    batches_per_launch=group) as eng:
         p = eng.paths()
         assert p["grouped_agg"] and p["grouped_cancels"], p
-        _check(eng, ob, batches, _pipelined(eng, batches, lag), f"cx config5 G={group}")
+        _check(eng, ob, batches, pipelined(eng, batches, lag), f"cx config5 G={group}")
         launches = -(-len(batches) // group)
         assert eng.stats()["handoffs"] * 16 <= launches * sc.num_symbols, eng.stats()
 
@@ -262,7 +251,7 @@ def test_cx_fuzz(me, orc, cx_env, seed):
                 for db in dbs:
                     db.free()
         elif path == "host":
-            outs = _pipelined(eng, batches, int(rng.integers(1, 2 * group + 2)))
+            outs = pipelined(eng, batches, int(rng.integers(1, 2 * group + 2)))
         else:
             outs = [eng.submit_batch(b) for b in batches]
         _check(eng, ob, batches, outs, ctx)

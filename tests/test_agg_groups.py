@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
+from tests.gpu_harness import env, pipelined
 
 pytestmark = pytest.mark.gpu
 
@@ -30,28 +31,9 @@ def orc(built):
 
 def _engine(me, sc, base, batches, **kw):
     total = sum(len(b) for b in batches)
-    old = os.environ.get("ME_REG_AGG")
-    os.environ["ME_REG_AGG"] = "1"
-    try:
+    with env({"ME_REG_AGG": "1"}):
         return me.Engine(sc.num_symbols, sc.levels, base, max_batch=max(len(b) for b in batches),
                          max_resting=total + 1024, max_chunks=total + 2 * sc.num_symbols, seq_ring=1 << 22, **kw)
-    finally:
-        if old is None:
-            del os.environ["ME_REG_AGG"]
-        else:
-            os.environ["ME_REG_AGG"] = old
-
-
-def _pipelined(eng, batches, lag):
-    out, tickets = [None] * len(batches), []
-    for k, b in enumerate(batches):
-        tickets.append((k, eng.submit_host(b)))
-        while len(tickets) > lag:
-            j, t = tickets.pop(0)
-            out[j] = eng.collect(t)
-    for j, t in tickets:
-        out[j] = eng.collect(t)
-    return out
 
 
 def _check(eng, ob, batches, outs, ctx):
@@ -76,7 +58,7 @@ def test_agg_groups_config2_every_batch(me, orc, group, lag):
     batches = [st.next(sc.batch) for _ in range(72)]
     ob = orc.OracleBook(sc.num_symbols)
     with _engine(me, sc, base, batches, batches_per_launch=group) as eng:
-        nf = _check(eng, ob, batches, _pipelined(eng, batches, lag), f"agg G={group}")
+        nf = _check(eng, ob, batches, pipelined(eng, batches, lag), f"agg G={group}")
         assert eng.stats()["handoffs"] == 0
     assert nf > 0
 
@@ -91,7 +73,7 @@ def test_agg_groups_long_fifos_and_sweeps(me, orc, spread):
     batches = [st.next(sc.batch) for _ in range(48)]
     ob = orc.OracleBook(sc.num_symbols)
     with _engine(me, sc, base, batches, batches_per_launch=16) as eng:
-        assert _check(eng, ob, batches, _pipelined(eng, batches, 20), f"agg spread={spread}") > 0
+        assert _check(eng, ob, batches, pipelined(eng, batches, 20), f"agg spread={spread}") > 0
 
 
 def test_agg_groups_handoffs(me, orc):
@@ -104,7 +86,7 @@ def test_agg_groups_handoffs(me, orc):
     batches = [st.next(sc.batch) for _ in range(80)]
     ob = orc.OracleBook(sc.num_symbols)
     with _engine(me, sc, base, batches, batches_per_launch=32) as eng:
-        _check(eng, ob, batches, _pipelined(eng, batches, 40), "agg handoffs")
+        _check(eng, ob, batches, pipelined(eng, batches, 40), "agg handoffs")
         assert eng.stats()["handoffs"] > 0
 
 
@@ -117,7 +99,7 @@ def test_agg_groups_large_quantities(me, orc):
     batches = [st.next(sc.batch) for _ in range(24)]
     ob = orc.OracleBook(sc.num_symbols)
     with _engine(me, sc, base, batches, batches_per_launch=8) as eng:
-        _check(eng, ob, batches, _pipelined(eng, batches, 10), "agg large qty")
+        _check(eng, ob, batches, pipelined(eng, batches, 10), "agg large qty")
         assert eng.stats()["handoffs"] > 0
 
 
@@ -130,7 +112,7 @@ def test_agg_groups_overfull_buckets(me, orc):
     batches = [st.next(sc.batch) for _ in range(24)]
     ob = orc.OracleBook(sc.num_symbols)
     with _engine(me, sc, base, batches, batches_per_launch=8) as eng:
-        _check(eng, ob, batches, _pipelined(eng, batches, 10), "agg overfull")
+        _check(eng, ob, batches, pipelined(eng, batches, 10), "agg overfull")
         assert eng.stats()["handoffs"] > 0
 
 
@@ -207,7 +189,7 @@ def test_agg_groups_side_jobs_in_line(me, orc, monkeypatch):
     ob = orc.OracleBook(sc.num_symbols)
     with _engine(me, sc, base, batches, batches_per_launch=3) as eng:
         assert eng.paths()["grouped_agg"]
-        assert _check(eng, ob, batches, _pipelined(eng, batches, 7), "side jobs in line") > 0
+        assert _check(eng, ob, batches, pipelined(eng, batches, 7), "side jobs in line") > 0
 
 
 def _peak_resting(orc, sc, batches):
@@ -252,7 +234,7 @@ def test_grouped_walk_symbols_stride_the_grid(me, orc, monkeypatch, cx):
     with _engine(me, sc, base, batches, batches_per_launch=4) as eng:
         p = eng.paths()
         assert p["grouped_agg"] and p["grouped_cancels"] == bool(cx), p
-        assert _check(eng, ob, batches, _pipelined(eng, batches, 9), f"grid stride cx={cx}") > 0
+        assert _check(eng, ob, batches, pipelined(eng, batches, 9), f"grid stride cx={cx}") > 0
         handoffs = eng.stats()["handoffs"]
         print(f"grid stride cx={cx}: handoffs {handoffs}")
         assert handoffs > 0
@@ -273,18 +255,11 @@ def test_agg_groups_cancels_tight_chunk_pool(me, orc, group):
     batches = [st.next(sc.batch) for _ in range(40)]
     peak = _peak_resting(orc, sc, batches)
     ob = orc.OracleBook(sc.num_symbols)
-    old = os.environ.get("ME_REG_AGG")
-    os.environ["ME_REG_AGG"] = "1"
-    try:
+    with env({"ME_REG_AGG": "1"}):
         eng = me.Engine(1, sc.levels, base, max_batch=sc.batch, max_resting=sum(len(b) for b in batches),
                         max_chunks=peak + 2 + 8, seq_ring=1 << 22, batches_per_launch=group)
-    finally:
-        if old is None:
-            del os.environ["ME_REG_AGG"]
-        else:
-            os.environ["ME_REG_AGG"] = old
     with eng:
-        _check(eng, ob, batches, _pipelined(eng, batches, 2 * group + 1), f"agg tight pool G={group}")
+        _check(eng, ob, batches, pipelined(eng, batches, 2 * group + 1), f"agg tight pool G={group}")
         assert eng.stats()["handoffs"] > 0
         assert eng.paths()["grouped_agg"]
 
@@ -311,11 +286,11 @@ def test_agg_auto_mode_turns_off_under_cancels(me, orc, monkeypatch, cx):
     ob = orc.OracleBook(sc.num_symbols)
     with me.Engine(sc.num_symbols, sc.levels, base, max_batch=sc.batch, max_resting=max_resting,
                    max_chunks=max_resting + 2 * sc.num_symbols, seq_ring=1 << 22, batches_per_launch=8) as eng:
-        outs = _pipelined(eng, batches[:16], 9)
+        outs = pipelined(eng, batches[:16], 9)
         assert eng.paths()["grouped_agg"], "phase 1 should run on the grouped aggregate path"
         assert eng.stats()["handoffs"] == 0
         assert not eng.paths()["grouped_cancels"]
-        outs += _pipelined(eng, batches[16:], 9)
+        outs += pipelined(eng, batches[16:], 9)
         p = eng.paths()
         if cx == "0":
             assert not p["grouped_agg"], "hand-offs should have turned the aggregate path off"
@@ -338,6 +313,6 @@ def test_agg_auto_choice_by_records_per_symbol(me, orc, symbols, agg):
     ob = orc.OracleBook(sc.num_symbols)
     with me.Engine(sc.num_symbols, sc.levels, base, max_batch=sc.batch, max_resting=total + 1024,
                    seq_ring=1 << 22) as eng:
-        outs = _pipelined(eng, batches, 70)
+        outs = pipelined(eng, batches, 70)
         assert eng.paths()["grouped_agg"] == agg
         _check(eng, ob, batches, outs, f"auto choice S={symbols}")

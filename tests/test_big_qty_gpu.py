@@ -13,9 +13,8 @@ from tests import depth_model as dm
 from tests import quote_model as qm
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
 from tests.book_audit import audit, names
+from tests.gpu_harness import PATHS, as_batch, engine_on, pipelined
 from tests.reduce_model import ReduceBook
-from tests.test_reduce_gpu import PATHS, _engine
-from tests.test_tif_gpu import _b, _pipelined
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +52,7 @@ def _run_groups(me, eng, model, groups, ctx, grouped):
     checked after each. Yields the group's index after its checks."""
     last = 0
     for g, arrays in enumerate(groups):
-        bs = [_b(me, a) for a in arrays]
+        bs = [as_batch(me, a) for a in arrays]
         if grouped:
             tickets = [eng.submit_host(b) for b in bs]
             outs = [eng.collect(t) for t in tickets]
@@ -73,7 +72,7 @@ def _run_case(me, path, case, ctx, group=1):
     grouped = PATHS[path][3]
     kw = {"batches_per_launch": group} if grouped else {}
     model = ReduceBook(case.S)
-    with _engine(me, path, case.S, case.base, case.batches, ring=RING, **kw) as eng:
+    with engine_on(me, path, case.S, case.base, case.batches, ring=RING, **kw) as eng:
         for _ in _run_groups(me, eng, model, [[a] for a in case.batches], ctx, grouped):
             pass
         return eng.stats()
@@ -96,9 +95,9 @@ def test_stream_parity(me, path, name, mode):
     ctx = f"{name} {path} {mode}"
     grouped = PATHS[path][3]
     if mode == "pipelined":
-        batches = [_b(me, a) for a in arrays]
-        with _engine(me, path, S, base, arrays, ring=RING, batches_per_launch=group) as eng:
-            outs = _pipelined(eng, batches, 2 * group + 1)
+        batches = [as_batch(me, a) for a in arrays]
+        with engine_on(me, path, S, base, arrays, ring=RING, batches_per_launch=group) as eng:
+            outs = pipelined(eng, batches, 2 * group + 1)
             for k, (ro, fo) in enumerate(exp):
                 assert_results_equal(outs[k][0], ro, f"{ctx} batch {k}")
                 assert_fills_equal(outs[k][1], fo, f"{ctx} batch {k}")
@@ -107,7 +106,7 @@ def test_stream_parity(me, path, name, mode):
     else:
         model = ReduceBook(S)
         ekw = {"batches_per_launch": 1} if grouped else {}
-        with _engine(me, path, S, base, arrays, ring=RING, **ekw) as eng:
+        with engine_on(me, path, S, base, arrays, ring=RING, **ekw) as eng:
             for _ in _run_groups(me, eng, model, [[a] for a in arrays], ctx, grouped):
                 pass
             stats = eng.stats()
@@ -129,7 +128,7 @@ def test_gwalk_handoffs_are_lw_caps(me):
     for tag, sub in runs.items():
         model = ReduceBook(S)
         groups = [sub[i:i + group] for i in range(0, len(sub), group)]
-        with _engine(me, "gwalk", S, base, sub, ring=RING, batches_per_launch=group) as eng:
+        with engine_on(me, "gwalk", S, base, sub, ring=RING, batches_per_launch=group) as eng:
             for _ in _run_groups(me, eng, model, groups, f"control {tag}", True):
                 pass
             hand[tag] = eng.stats()["handoffs"]
@@ -172,7 +171,7 @@ def test_lw_cap_edges(me, path):
         arrays = [a for g in groups for a in g[0]]
         kw = {"batches_per_launch": G} if PATHS[path][3] else {}
         model = ReduceBook(1)
-        with _engine(me, path, 1, base, arrays, ring=RING, **kw) as eng:
+        with engine_on(me, path, 1, base, arrays, ring=RING, **kw) as eng:
             seen = 0
             for g in _run_groups(me, eng, model, [x[0] for x in groups], f"LW_CAP {path} {name}", PATHS[path][3]):
                 now = eng.stats()[counter]
@@ -191,7 +190,7 @@ def test_fok_across_2_31(me, path):
     grouped = PATHS[path][3]
     kw = {"batches_per_launch": 1} if grouped else {}
     model = ReduceBook(case.S)
-    with _engine(me, path, case.S, case.base, case.batches, ring=RING, **kw) as eng:
+    with engine_on(me, path, case.S, case.base, case.batches, ring=RING, **kw) as eng:
         before = None
         for g in _run_groups(me, eng, model, [[a] for a in case.batches], f"FOK {path}", grouped):
             now = [eng.dump(s) for s in range(case.S)]
@@ -230,13 +229,13 @@ def test_feeds_at_width(me, path):
     model = ReduceBook(S)
     view = bq.Snap(model)
     ekw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, S, base, arrays, ring=RING, **ekw) as eng:
+    with engine_on(me, path, S, base, arrays, ring=RING, **ekw) as eng:
         eng.quotes_enable(4 * S * (len(arrays) + 2))
         eng.depth_enable(D, 8 * D * S * (len(arrays) + 2))
         table, maps = qm.tops(qm._Empty(), S), dm.empty_maps(S)
         big = 0
         for k, a in enumerate(arrays):
-            r, f = eng.submit_batch(_b(me, a))
+            r, f = eng.submit_batch(as_batch(me, a))
             ro, fo = model.submit(a)
             assert_results_equal(r, ro, f"feeds {path} batch {k}")
             assert_fills_equal(f, fo, f"feeds {path} batch {k}")

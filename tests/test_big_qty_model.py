@@ -29,8 +29,8 @@ import pytest
 
 from tests import big_qty as bq
 from tests.big_qty import CAP31, CAP32, MAX, Q28
+from tests.model_common import FIELDS_BOOK, FIELDS_FILL, FIELDS_RES, same
 from tests.reduce_model import ReduceBook, check_seq_rule, is_reduce
-from tests.test_pybook_cross import FIELDS_BOOK, FIELDS_FILL, FIELDS_RES, same
 from tests.tif_model import Arrays
 
 BUY, SELL = 1, 2

@@ -24,9 +24,9 @@ from tests import order_query_model as oq
 from tests import preview_cases as pc
 from tests import preview_model as pm
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal, side_levels
-from tests.feed_common import PATHS, _env, _same
+from tests.feed_common import _same
+from tests.gpu_harness import FEED_PATHS, as_batch, engine_on
 from tests.reduce_model import ReduceBook
-from tests.test_tif_gpu import _b
 
 pytestmark = pytest.mark.gpu
 
@@ -43,16 +43,8 @@ def me(built):
 
 
 def _engine(me, sn):
-    """The "reg" settings of feed_common.PATHS at L = 128, the "deep" ones above."""
-    _, env, expect, grouped = PATHS["reg" if sn.L <= 128 else "deep"]
-    n = sum(len(a) for a in sn.batches)
-    with _env(env):
-        eng = me.Engine(sn.S, sn.L, sn.base, max_batch=max(len(a) for a in sn.batches), max_resting=n + 1024,
-                        seq_ring=1 << 22, **({"batches_per_launch": 1} if grouped else {}))
-    p = eng.paths()
-    for k, v in expect.items():
-        assert p[k] == v, f"L={sn.L}: paths() {p}"
-    return eng
+    """The "reg" row at L = 128, the "deep" one above, at the scenario's own window size."""
+    return engine_on(me, "reg" if sn.L <= 128 else "deep", sn.S, sn.base, sn.batches, table=FEED_PATHS, levels=sn.L, group=1)
 
 
 def _sweeps(model, S):
@@ -83,7 +75,7 @@ def test_every_reader_over_one_book(me, L):
         _same(eng.depth_drain(), depth.expect(0), f"L={L} enable")
         for k, a in enumerate(sn.batches):
             ctx = f"L={L} batch {k}"
-            r, f = eng.submit_batch(_b(me, a))
+            r, f = eng.submit_batch(as_batch(me, a))
             ro, fo = ob.submit(a)
             rb.submit(a)
             assert_results_equal(r, ro, ctx)

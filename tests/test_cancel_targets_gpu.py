@@ -14,7 +14,7 @@ import pytest
 from tests import cancel_targets as ct
 from tests import tif_model as tm
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
-from tests.test_tif_gpu import PATHS, SMALL, _b, _env, _pipelined
+from tests.gpu_harness import FEED_PATHS as PATHS, SMALL, as_batch, engine_on, pipelined
 from tests.tif_model import TifBook, kind
 
 pytestmark = pytest.mark.gpu
@@ -38,18 +38,6 @@ def orc(built):
     return oracle
 
 
-def _engine(me, path, num_symbols, base, batches, ring, **kw):
-    L, env, expect, _ = PATHS[path]
-    total = sum(len(b) for b in batches)
-    kw.setdefault("max_resting", total + 1024)
-    with _env(env):
-        eng = me.Engine(num_symbols, L, base, max_batch=max(len(b) for b in batches), seq_ring=ring, **kw)
-    p = eng.paths()
-    for k, v in expect.items():
-        assert p[k] == v, f"{path}: paths() {p}"
-    return eng
-
-
 def _check(eng, model, outs, exp, ctx):
     for k, (ro, fo) in enumerate(exp):
         assert_results_equal(outs[k][0], ro, f"{ctx} batch {k}")
@@ -63,13 +51,13 @@ def _run_case(me, name, path, group, device=False):
     assert PATHS[path][0] == c.levels
     base, arrays, _, _ = ct.stream(name)
     exp, _, model = ct.expected(name)
-    batches = [_b(me, a) for a in arrays]
+    batches = [as_batch(me, a) for a in arrays]
     ctx = f"{name} {path} G={group}{' device' if device else ''}"
     grouped = PATHS[path][3]
     kw = {"batches_per_launch": group} if grouped else {}
     if device:  # (every record of a device batch counts as one that may rest)
         kw["max_resting"] = 2 * sum(len(b) for b in batches) + 1024
-    with _engine(me, path, S, base, batches, c.ring, **kw) as eng:
+    with engine_on(me, path, S, base, batches, table=PATHS, ring=c.ring, **kw) as eng:
         if device:
             dbs = [eng.upload(b) for b in batches]
             try:
@@ -82,7 +70,7 @@ def _run_case(me, name, path, group, device=False):
                 for db in dbs:
                     db.free()
         elif grouped:
-            outs = _pipelined(eng, batches, 2 * group + 1)
+            outs = pipelined(eng, batches, 2 * group + 1)
         else:
             outs = [eng.submit_batch(b) for b in batches]
         _check(eng, model, outs, exp, ctx)
@@ -204,9 +192,9 @@ def test_ring_slot_taken_by_a_later_record(me, path, sub):
     assert exp[-1][0]["remaining_qty"][second[1] - cut] == 9
     if sub == "resting_other_symbol":
         assert exp[-1][0]["status"][[i - cut for i in own]].tolist() == [ST_CANCELED, ST_CANCELED]
-    batches = [_b(me, a) for a in arrays]
+    batches = [as_batch(me, a) for a in arrays]
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, 2, base, batches, R, **kw) as eng:
+    with engine_on(me, path, 2, base, batches, table=PATHS, ring=R, **kw) as eng:
         outs = [eng.submit_batch(b) for b in batches]
         _check(eng, tb, outs, exp, f"ring slot {path} {sub}")
 

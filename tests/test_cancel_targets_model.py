@@ -18,11 +18,9 @@ import pytest
 from oracle.pybook import BUY, FILL_DTYPE, RESULT_DTYPE, RJ_UNKNOWN, ST_CANCELED, ST_REJECTED, PyBook
 from tests import cancel_targets as ct
 from tests import tif_model as tm
+from tests.model_common import FIELDS_BOOK, FIELDS_FILL, FIELDS_RES, same
 from tests.tif_model import Arrays, TifBook, kind
 
-FIELDS_RES = ("filled_qty", "remaining_qty", "fill_count", "tape_offset", "status", "reason")
-FIELDS_FILL = ("taker_seq", "maker_seq", "price_q4", "qty", "symbol")
-FIELDS_BOOK = ("seq", "price_q4", "qty", "side")
 S = ct.S_CX
 
 
@@ -31,14 +29,6 @@ def orc(built):
     from oracle import oracle
 
     return oracle
-
-
-def same(a, b, fields, ctx):
-    assert len(a) == len(b), f"{ctx}: {len(a)} vs {len(b)} entries"
-    for f in fields:
-        if not np.array_equal(np.asarray(a[f]), np.asarray(b[f])):
-            i = int(np.nonzero(np.asarray(a[f]) != np.asarray(b[f]))[0][0])
-            raise AssertionError(f"{ctx}: field {f} differs first at {i}: {a[i]} vs {b[i]}")
 
 
 def differ(a, b, fields):

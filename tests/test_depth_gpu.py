@@ -9,7 +9,8 @@ import pytest
 
 from tests import depth_model as dm
 from tests import quote_model as qm
-from tests.feed_common import BIG, BUY, PATHS, SELL, SMALL, Rows, _c5_stream, _engine, _env, _same
+from tests.feed_common import BIG, BUY, SELL, Rows, _c5_stream, _same
+from tests.gpu_harness import FEED_PATHS as PATHS, SMALL, env, feed_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +67,7 @@ def test_events_of_every_group_on_every_path(me, orc, path, group):
     both = path == "gwalk_cx"
     qmodel = qm.QuoteModel(ob, S) if both else None
     kw = {"batches_per_launch": group} if grouped else {}
-    with _engine(me, path, S, base, batch, 2 * total + 1024, **kw) as eng:
+    with feed_engine(me, path, S, base, batch, 2 * total + 1024, **kw) as eng:
         if both:
             eng.quotes_enable(64 * S * (nb + 1))
         eng.depth_enable(D, 4 * D * S * (nb + 2))
@@ -296,7 +297,7 @@ def test_sparse_deep_window(me, orc):
     base = np.array([1_000_000, 2_000_000, 3_000_000, 4_000_000], dtype=np.int64)
     ob = orc.OracleBook(S)
     model = dm.DepthModel(ob, S, D)
-    with _env({"ME_HOT_MIN": "0"}):
+    with env({"ME_HOT_MIN": "0"}):
         eng = me.Engine(S, L, base, max_batch=64, max_resting=1024, seq_ring=1 << 20)
     with eng:
         eng.depth_enable(D, 1024)
@@ -404,7 +405,7 @@ def test_host_pipeline_events_are_there_after_collect(me, orc, group):
         ob.submit(b)
         after.append(dm.views(ob, S, D))
     cap = 4 * D * S * (nb + 2)
-    with _engine(me, "reg", S, base, batch, nb * batch + 1024, batches_per_launch=group) as eng:
+    with feed_engine(me, "reg", S, base, batch, nb * batch + 1024, batches_per_launch=group) as eng:
         eng.depth_enable(D, cap)
         got = np.zeros(0, dtype=dm.DEPTH_DTYPE)
         tickets = []
@@ -496,7 +497,7 @@ def test_enable_mid_stream(me, orc, path):
     S, L, D = 65, PATHS[path][0], 4
     base, batches = _c5_stream(me, S, L, 3, 300)
     ob = orc.OracleBook(S)
-    with _engine(me, path, S, base, 300, 2048) as eng:
+    with feed_engine(me, path, S, base, 300, 2048) as eng:
         for b in batches[:2]:
             eng.submit_batch(b)
             ob.submit(b)

@@ -3,7 +3,7 @@ book handed out equals the CPU oracle's top-D snapshot of the same orders. Needs
 import numpy as np
 import pytest
 
-from tests.test_quotes_service import FeedMatcher
+from tests.service_common import FeedMatcher
 
 pytestmark = pytest.mark.gpu
 

@@ -9,7 +9,8 @@ import pytest
 
 from tests import depth_model as dm
 from tests import quote_model as qm
-from tests.feed_common import BUY, PATHS, SELL, Rows, _c5_stream, _engine, _same
+from tests.feed_common import BUY, SELL, Rows, _c5_stream, _same
+from tests.gpu_harness import FEED_PATHS as PATHS, feed_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -146,7 +147,7 @@ def test_both_feeds_wrap_defer_and_catch_up(me, planned, path):
     launches conflated into their catch-up jobs; the counters agree with the plan."""
     batches, reads, rings = planned
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, S, BASE, max(len(b) for b in batches), 64 * S, **kw) as eng:
+    with feed_engine(me, path, S, BASE, max(len(b) for b in batches), 64 * S, **kw) as eng:
         eng.quotes_enable(QCAP)
         eng.depth_enable(D, DCAP)
         read = {"quotes": eng.quotes_read, "depth": eng.depth_read}
@@ -180,7 +181,7 @@ def test_reenable_one_feed_beside_the_other(me, orc, path):
     S, L, D = 65, PATHS[path][0], 3
     base, batches = _c5_stream(me, S, L, 5, 300)
     ob = orc.OracleBook(S)
-    with _engine(me, path, S, base, 300, 4096) as eng:
+    with feed_engine(me, path, S, base, 300, 4096) as eng:
         def step(k):
             eng.submit_batch(batches[k])
             ob.submit(batches[k])

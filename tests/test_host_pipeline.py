@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
+from tests.gpu_harness import pipelined
 
 pytestmark = pytest.mark.gpu
 
@@ -36,24 +37,18 @@ def _engine(me, sc, base, batches, **kw):
                      max_resting=total + 1024, max_chunks=total + 2 * sc.num_symbols, seq_ring=1 << 22, **kw)
 
 
-def _pipelined(me, eng, batches, lag, zero_copy_every=0):
-    """Submit every batch through me_submit_host, collecting each `lag` submissions later (in order);
-    returns the outputs per batch. zero_copy_every = k: every k-th batch is written straight into the
-    pinned slot (me_host_inputs) instead of being staged by the engine."""
-    out, tickets = [None] * len(batches), []
-    for k, b in enumerate(batches):
-        if zero_copy_every and k % zero_copy_every == 0:
-            w = eng.host_inputs(len(b))
-            for f in ("seq", "price_q4", "qty", "symbol", "kind"):
-                getattr(w, f)[:] = getattr(b, f)
-            b = w
-        tickets.append((k, eng.submit_host(b)))
-        while len(tickets) > lag:
-            j, t = tickets.pop(0)
-            out[j] = eng.collect(t)
-    for j, t in tickets:
-        out[j] = eng.collect(t)
-    return out
+def _zero_copy(eng, every):
+    """For pipelined's `stage`: every `every`-th batch is written straight into the pinned slot (me_host_inputs)
+    instead of being staged by the engine."""
+    def stage(k, b):
+        if k % every:
+            return b
+        w = eng.host_inputs(len(b))
+        for f in ("seq", "price_q4", "qty", "symbol", "kind"):
+            getattr(w, f)[:] = getattr(b, f)
+        return w
+
+    return stage
 
 
 @pytest.mark.parametrize("levels,group,lag", [(128, 4, 1), (128, 4, 12), (128, 32, 96), (128, 8, 32), (512, 1, 3)])
@@ -62,7 +57,7 @@ def test_host_pipeline_every_batch(me, orc, levels, group, lag):
     ob = orc.OracleBook(sc.num_symbols)
     with _engine(me, sc, base, batches, batches_per_launch=group) as eng:
         assert eng.config()["host_slots"] == 4 * eng.config()["batches_per_launch"] + 1
-        outs = _pipelined(me, eng, batches, lag, zero_copy_every=3)
+        outs = pipelined(eng, batches, lag, _zero_copy(eng, 3))
         for k, b in enumerate(batches):
             ro, fo = ob.submit(b)
             assert_results_equal(outs[k][0], ro, f"L={levels} G={group} lag={lag} batch {k}")
@@ -77,7 +72,7 @@ def test_host_tape_longer_than_slot(me, orc, levels):
     ob = orc.OracleBook(sc.num_symbols)
     spilled = 0
     with _engine(me, sc, base, batches, batches_per_launch=2, host_tape_cap=64) as eng:
-        for k, (r, f) in enumerate(_pipelined(me, eng, batches, lag=2)):
+        for k, (r, f) in enumerate(pipelined(eng, batches, lag=2)):
             ro, fo = ob.submit(batches[k])
             assert_results_equal(r, ro, f"spill L={levels} batch {k}")
             assert_fills_equal(f, fo, f"spill L={levels} batch {k}")
@@ -113,7 +108,7 @@ def test_host_tape_longer_than_batch(me, orc):
     ob = orc.OracleBook(sc.num_symbols)
     longer = 0
     with _engine(me, sc, base, batches, batches_per_launch=4) as eng:
-        for k, (r, f) in enumerate(_pipelined(me, eng, batches, lag=3)):
+        for k, (r, f) in enumerate(pipelined(eng, batches, lag=3)):
             ro, fo = ob.submit(batches[k])
             assert_results_equal(r, ro, f"long tape batch {k}")
             assert_fills_equal(f, fo, f"long tape batch {k}")
@@ -133,7 +128,7 @@ def test_host_pipeline_drifting_handoffs(me, orc):
     batches = [st.next(sc.batch) for _ in range(96)]
     ob = orc.OracleBook(sc.num_symbols)
     with _engine(me, sc, base, batches, batches_per_launch=32) as eng:
-        for k, (r, f) in enumerate(_pipelined(me, eng, batches, lag=40)):
+        for k, (r, f) in enumerate(pipelined(eng, batches, lag=40)):
             ro, fo = ob.submit(batches[k])
             assert_results_equal(r, ro, f"drift host batch {k}")
             assert_fills_equal(f, fo, f"drift host batch {k}")

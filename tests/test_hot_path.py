@@ -4,12 +4,11 @@
 ME_HOT_MIN (read at me_create) sets the records per batch that make a symbol hot; 1 sends every symbol
 through the hot path, so the generic fallbacks (cancels, prices outside the window, far levels,
 re-centring: k_match_hot_cont) run behind it too."""
-import os
-
 import numpy as np
 import pytest
 
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
+from tests.gpu_harness import env
 
 
 def run_both(eng, ob, batches, ctx=""):
@@ -46,22 +45,14 @@ def orc(built):
 
 
 def _engine(me, hot_min, *a, agg=1, ladder=None, occ=None, **kw):
-    env = {"ME_HOT_MIN": str(hot_min), "ME_HOT_AGG": str(agg)}
+    hot = {"ME_HOT_MIN": str(hot_min), "ME_HOT_AGG": str(agg)}
     if ladder is not None:  # ME_AGG_LADDER: the largest window k_agg_walk's ladder walk takes (0: lists)
-        env["ME_AGG_LADDER"] = str(ladder)
+        hot["ME_AGG_LADDER"] = str(ladder)
     if occ is not None:  # ME_LW_OCC: ladders deeper than this search through the LDS occupancy bitmap (0: off)
-        env["ME_LW_OCC"] = str(occ)
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        kw.setdefault("seq_ring", 1 << 22)
+        hot["ME_LW_OCC"] = str(occ)
+    kw.setdefault("seq_ring", 1 << 22)
+    with env(hot):
         return me.Engine(*a, **kw)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
 
 
 def _drift(me, levels, num_symbols, batch, nbatches, **over):

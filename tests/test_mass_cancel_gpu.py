@@ -16,8 +16,7 @@ from tests import mass_cancel_model as mc
 from tests import tif_model as tm
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
 from tests.big_qty import Script
-from tests.test_reduce_gpu import PATHS, _engine
-from tests.test_tif_gpu import _b
+from tests.gpu_harness import PATHS, as_batch, engine_on
 
 pytestmark = pytest.mark.gpu
 
@@ -52,7 +51,7 @@ class Run:
         self.purged = set()
 
     def step(self, a, ctx, check=True):
-        r, f = self.eng.submit_batch(_b(self.me, a))
+        r, f = self.eng.submit_batch(as_batch(self.me, a))
         ro, fo = self.orc.submit(a)
         assert_results_equal(r, ro, ctx)
         assert_fills_equal(f, fo, ctx)
@@ -132,7 +131,7 @@ def test_book_shapes_sides_and_symbol_lists(me, path):
     sc.new(4, BUY, m4 - 2, 5)
     sc.cancel(0, a1)
     after = sc.take()
-    with _engine(me, path, S, base, [build, cancels, after], ring=1 << 16, **_kw(path)) as eng:
+    with engine_on(me, path, S, base, [build, cancels, after], ring=1 << 16, **_kw(path)) as eng:
         run = Run(me, eng, S)
         run.step(build, f"shapes {path} build")
         run.step(cancels, f"shapes {path} cancels")
@@ -209,7 +208,7 @@ def test_far_side_moved_into_the_arena(me, path):
         sc.new(0, BUY, b0 - 15 * (k + 1), 9)
     sc.new(0, SELL, b0 - 100, 25)  # takes the window bid, then far bids
     after = sc.take()
-    with _engine(me, path, S, base, [build, after], ring=1 << 16, far_levels=4, **_kw(path)) as eng:
+    with engine_on(me, path, S, base, [build, after], ring=1 << 16, far_levels=4, **_kw(path)) as eng:
         run = Run(me, eng, S)
         run.step(build, f"arena {path} build")
         assert eng.far_stats()["moves"] > 0
@@ -229,7 +228,7 @@ def test_the_stream_goes_on(me, path):
     symbol 0's), purges after the third: the same symbols trade on, cancels of purged orders are rejected."""
     L, S = PATHS[path][0], 4
     base, arrays = tm.tif_stream(4200 + L, S, L, 6, 1024, far_pct=2, skew=path in ("hot", "hot_agg"), **PLAIN)
-    with _engine(me, path, S, base, arrays, ring=1 << 16, **_kw(path)) as eng:
+    with engine_on(me, path, S, base, arrays, ring=1 << 16, **_kw(path)) as eng:
         run = Run(me, eng, S)
         for k in range(3):
             run.step(arrays[k], f"goes on {path} batch {k}", check=k == 2)
@@ -296,15 +295,15 @@ def test_a_refused_batch_is_admitted_after_the_purge(me):
         run = Run(me, eng, S)
         run.step(fill, "admission fill")
         assert eng.admission()["resting"] == R
-        assert not eng.admits(_b(me, more))
+        assert not eng.admits(as_batch(me, more))
         with pytest.raises(me.EngineError) as ei:
-            eng.submit_batch(_b(me, more))
+            eng.submit_batch(as_batch(me, more))
         assert ei.value.code == me.ME_E_CAPACITY
         e, c = run.purge([3, 1], [BOTH, BUY], "admission purge")
         assert len(e) == R // 4 + R // 8
         adm = eng.admission()
         assert adm["resting"] == adm["bound"] == R - len(e)
-        assert eng.admits(_b(me, more))
+        assert eng.admits(as_batch(me, more))
         run.step(more, "admission admitted")
 
 
@@ -314,7 +313,7 @@ def test_host_tickets_held_across_a_purge(me):
     base, arrays = tm.tif_stream(977, S, L, 4, 512, **PLAIN)
     with me.Engine(S, L, base, max_batch=512, max_resting=4096, seq_ring=1 << 16, batches_per_launch=4) as eng:
         run = Run(me, eng, S)
-        tickets = [eng.submit_host(_b(me, a)) for a in arrays[:3]]
+        tickets = [eng.submit_host(as_batch(me, a)) for a in arrays[:3]]
         exp = [run.orc.submit(a) for a in arrays[:3]]
         run.last = max(int(a.seq.max()) for a in arrays[:3])
         assert run.orc.resting() > 100
@@ -393,7 +392,7 @@ def _replay_depth(state, ev):
 def test_quote_and_depth_feeds_follow_a_purge(me, path):
     L, S, D = PATHS[path][0], 4, 4
     base, arrays = tm.tif_stream(555, S, L, 3, 512, far_pct=2, **PLAIN)
-    with _engine(me, path, S, base, arrays, ring=1 << 16, **_kw(path)) as eng:
+    with engine_on(me, path, S, base, arrays, ring=1 << 16, **_kw(path)) as eng:
         run = Run(me, eng, S)
         eng.quotes_enable(1 << 12)
         eng.depth_enable(D, 1 << 13)

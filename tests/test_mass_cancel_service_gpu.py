@@ -6,7 +6,7 @@ import sqlite3
 import numpy as np
 import pytest
 
-from tests.test_quotes_service import FeedMatcher
+from tests.service_common import FeedMatcher
 
 pytestmark = pytest.mark.gpu
 

@@ -7,6 +7,7 @@ import re
 import subprocess
 
 from tests import order_query_model as oq
+from tests.abi_layout import c_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INFO_FIELDS = ("seq", "price_q4", "qty_ahead", "level_qty", "qty_better", "qty", "orders_ahead", "levels_better",
@@ -40,22 +41,10 @@ def test_declared_exported_and_prototyped(built):
     assert lib.me_service_order_status(None, None, None, 0, None) == _abi.ME_E_INVALID
 
 
-def _c_layout(tmp_path, header, struct, fields):
-    """sizeof and every offsetof of `struct`, as the C compiler sees the header."""
-    src = tmp_path / f"{struct}_layout.c"
-    lines = "\n".join(f'  printf("{f} %zu\\n", offsetof({struct}, {f}));' for f in fields)
-    src.write_text(f'#include <stddef.h>\n#include <stdio.h>\n#include "{header}"\nint main(void) {{\n'
-                   f'  printf("sizeof %zu\\n", sizeof({struct}));\n{lines}\n  return 0;\n}}\n')
-    exe = tmp_path / f"{struct}_layout"
-    subprocess.run(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    return {k: int(v) for k, v in (ln.split() for ln in out.splitlines())}
-
-
 def test_order_info_dtype_matches_the_header(built, tmp_path):
     from matching_engine_amd import _abi
 
-    c = _c_layout(tmp_path, "me_engine.h", "me_order_info", INFO_FIELDS)
+    c = c_layout(tmp_path, "me_engine.h", "me_order_info", INFO_FIELDS)
     dt = _abi.ORDER_INFO_DTYPE
     assert dt.itemsize == 64 == c["sizeof"]
     assert dt.names == INFO_FIELDS
@@ -70,7 +59,7 @@ def test_order_info_dtype_matches_the_header(built, tmp_path):
 def test_order_status_struct_matches_the_header(built, tmp_path):
     from matching_engine_amd import _abi
 
-    c = _c_layout(tmp_path, "me_service.h", "me_order_status", STATUS_FIELDS)
+    c = c_layout(tmp_path, "me_service.h", "me_order_status", STATUS_FIELDS)
     assert C.sizeof(_abi.MeOrderStatus) == c["sizeof"] == 88
     assert tuple(n for n, _ in _abi.MeOrderStatus._fields_) == STATUS_FIELDS
     for f in STATUS_FIELDS:

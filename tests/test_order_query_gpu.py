@@ -18,9 +18,8 @@ from tests import reduce_model as rm
 from tests import tif_model as tm
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
 from tests.big_qty import Script
+from tests.gpu_harness import PATHS, as_batch, engine_on
 from tests.reduce_model import INT32_MAX, ReduceBook
-from tests.test_reduce_gpu import PATHS, _engine
-from tests.test_tif_gpu import _b
 from tests.tif_model import TIF_IOC, kind
 
 pytestmark = pytest.mark.gpu
@@ -68,7 +67,7 @@ class Run:
         self.used = set()
 
     def step(self, a, ctx, extra=()):
-        r, f = self.eng.submit_batch(_b(self.me, a))
+        r, f = self.eng.submit_batch(as_batch(self.me, a))
         ro, fo = self.model.submit(a)
         assert_results_equal(r, ro, ctx)
         assert_fills_equal(f, fo, ctx)
@@ -126,7 +125,7 @@ def test_chunks_and_dead_seqs(me, path):
     script.append(sc.take())
     sc.reduce(0, o[6], 100)                            # reduced to nothing
     script.append(sc.take())
-    with _engine(me, path, S, base, script, **_kw(path)) as eng:
+    with engine_on(me, path, S, base, script, **_kw(path)) as eng:
         run = Run(me, eng, S)
         _, a0 = run.step(script[0], f"chunks {path} build")
         assert [_pos(a0[o[j]]) for j in (1, 16, 17, 33, 40)] == [
@@ -160,9 +159,9 @@ def test_query_counts_and_arguments(me, path):
     L, S = PATHS[path][0], 8
     base, arrays = rm.reduce_stream(777, S, L, 3, 512, far_pct=3, skew=True, **DEEP_BOOKS)
     model = ReduceBook(S)
-    with _engine(me, path, S, base, arrays, **_kw(path)) as eng:
+    with engine_on(me, path, S, base, arrays, **_kw(path)) as eng:
         for a in arrays:
-            eng.submit_batch(_b(me, a))
+            eng.submit_batch(as_batch(me, a))
             model.submit(a)
         used = sorted({int(x) for a in arrays for x in a.seq})
         pool = np.array(used + _dead(used[-1]) + [used[-1] + 2 + 3 * i for i in range(32)], dtype=np.uint64)
@@ -211,7 +210,7 @@ def test_far_levels_and_a_recentre(me, path):
     # the window re-centres around it; the old window's bids become far levels, far asks come into the window
     mover = sc.new(0, BUY, b0 + L + 5, 20)
     move = sc.take()
-    with _engine(me, path, S, base, [build, move], far_levels=4, **_kw(path)) as eng:
+    with engine_on(me, path, S, base, [build, move], far_levels=4, **_kw(path)) as eng:
         run = Run(me, eng, S)
         _, a0 = run.step(build, f"far {path} build")
         assert eng.far_stats()["moves"] > 0  # ten levels in regions of four: the sides moved to the arena
@@ -276,7 +275,7 @@ def test_ring_and_old_table(me, path):
     sc.reduce(0, A, 4)
     sc.reduce(0, A2, 11)
     script.append(sc.take())
-    with _engine(me, path, S, base, script, ring=R, **_kw(path)) as eng:
+    with engine_on(me, path, S, base, script, ring=R, **_kw(path)) as eng:
         run = Run(me, eng, S)
         for k, a in enumerate(script):
             _, ans = run.step(a, f"ring {path} batch {k}", extra=[P + R, P + 2 * R, A + 7 * R])
@@ -308,7 +307,7 @@ def test_int64_quantities_and_symbol_ids(me, path):
     sc.new(0, SELL, int(base[0]) + 9, 1)
     sc.new(1, BUY, int(base[1]) + 9, 2)
     a = sc.take()
-    with _engine(me, path, S, base, [a], max_resting=4096, symbol_ids=ids, **_kw(path)) as eng:
+    with engine_on(me, path, S, base, [a], max_resting=4096, symbol_ids=ids, **_kw(path)) as eng:
         run = Run(me, eng, S, symbol_ids=ids)
         _, ans = run.step(a, f"int64 {path}")
         assert int(ans[hi[2]]["qty_ahead"]) == 4_294_967_294
@@ -364,10 +363,10 @@ def _books_equal(eng, dumps, ctx):
 def test_random_streams(me, path, draw):
     L = PATHS[path][0]
     base, arrays, cps, dumps = _draw(L, draw, RN)
-    with _engine(me, path, RS, base, arrays, **_kw(path)) as eng:
+    with engine_on(me, path, RS, base, arrays, **_kw(path)) as eng:
         for k, (a, (ro, fo, q, want)) in enumerate(zip(arrays, cps)):
             ctx = f"random L={L} #{draw} {path} batch {k}"
-            r, f = eng.submit_batch(_b(me, a))
+            r, f = eng.submit_batch(as_batch(me, a))
             assert_results_equal(r, ro, ctx)
             assert_fills_equal(f, fo, ctx)
             oq.assert_answers_equal(eng.order_query(q), want, ctx)
@@ -385,8 +384,8 @@ def test_random_streams_in_device_groups(me, path, group, draw):
     L = PATHS[path][0]
     base, arrays, cps, dumps = _draw(L, draw, RSUB)
     total = sum(len(a) for a in arrays)
-    with _engine(me, path, RS, base, arrays, max_resting=2 * total + 1024, batches_per_launch=group) as eng:
-        dbs = [eng.upload(_b(me, a)) for a in arrays]
+    with engine_on(me, path, RS, base, arrays, max_resting=2 * total + 1024, batches_per_launch=group) as eng:
+        dbs = [eng.upload(as_batch(me, a)) for a in arrays]
         try:
             for g0 in range(0, len(dbs), group):
                 g1 = min(g0 + group, len(dbs))
@@ -413,9 +412,9 @@ def _feeds_run(me, path, draw, queries):
     events, final dumps, the engine's last export)."""
     L = PATHS[path][0]
     base, arrays, cps, _ = _draw(L, draw, RN)
-    batches = [_b(me, a) for a in arrays]
+    batches = [as_batch(me, a) for a in arrays]
     quotes, depth, outs = [], [], [None] * len(batches)
-    with _engine(me, path, RS, base, arrays, **_kw(path, 1)) as eng:
+    with engine_on(me, path, RS, base, arrays, **_kw(path, 1)) as eng:
         eng.quotes_enable(1 << 14)
         eng.depth_enable(5, 1 << 15)
         quotes.append(eng.quotes_drain())

@@ -3,7 +3,7 @@ fill and cancel, and what the call keeps to itself. Needs an MI355X."""
 import numpy as np
 import pytest
 
-from tests.test_quotes_service import FeedMatcher
+from tests.service_common import FeedMatcher
 
 pytestmark = pytest.mark.gpu
 

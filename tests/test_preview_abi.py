@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 
 from tests import preview_model as pm
-from tests.test_order_query_abi import _c_layout
+from tests.abi_layout import c_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("first_price_q4", "last_price_q4", "opp_price_q4", "notional_hi", "notional_lo", "filled_qty", "remaining_qty",
@@ -45,7 +45,7 @@ def test_declared_exported_and_prototyped(built):
 def test_preview_dtype_matches_the_header(built, tmp_path):
     from matching_engine_amd import _abi
 
-    c = _c_layout(tmp_path, "me_engine.h", "me_preview", FIELDS)
+    c = c_layout(tmp_path, "me_engine.h", "me_preview", FIELDS)
     dt = _abi.PREVIEW_DTYPE
     assert dt.itemsize == 64 == c["sizeof"]
     assert dt.names == FIELDS

@@ -16,9 +16,8 @@ from tests import book_audit
 from tests import preview_cases as pc
 from tests import preview_model as pm
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
+from tests.gpu_harness import PATHS, as_batch, engine_on
 from tests.reduce_model import ReduceBook
-from tests.test_reduce_gpu import PATHS, _engine
-from tests.test_tif_gpu import _b
 
 pytestmark = pytest.mark.gpu
 
@@ -41,8 +40,8 @@ def _preview(eng, queries):
 def _submit(me, eng, a, device):
     """One batch, synchronously: a host batch, or a device batch of a launch group of its own."""
     if not device:
-        return eng.submit_batch(_b(me, a))
-    db = eng.upload(_b(me, a))
+        return eng.submit_batch(as_batch(me, a))
+    db = eng.upload(as_batch(me, a))
     try:
         eng.submit_device(db)
         eng.sync()
@@ -56,14 +55,14 @@ def _run(me, path, case, device=False, **kw):
     model = ReduceBook(case.S)
     total = sum(len(a) for a in case.batches) + len(case.batches)
     kw = dict({"max_resting": 2 * total + 1024}, **case.kw, **kw)
-    with _engine(me, path, case.S, case.base, case.batches, **kw) as eng:
+    with engine_on(me, path, case.S, case.base, case.batches, **kw) as eng:
         for k, a in enumerate(case.batches):
             ctx = f"{case.name} {path} batch {k}"
             if device:  # the batch waits in a partial launch group: the preview's me_sync launches it
-                db = eng.upload(_b(me, a))
+                db = eng.upload(as_batch(me, a))
                 eng.submit_device(db)
             else:
-                r, f = eng.submit_batch(_b(me, a))
+                r, f = eng.submit_batch(as_batch(me, a))
             ro, fo = model.submit(a)
             queries = case.queries(model, k)
             want = pm.expected(model, case.S, queries)
@@ -119,7 +118,7 @@ def test_arguments_and_empty_books(me, path):
     case = pc.mixed(PATHS[path][0])
     S, mid = case.S, int(case.base[0]) + case.L // 2
     model = ReduceBook(S)
-    with _engine(me, path, S, case.base, case.batches) as eng:
+    with engine_on(me, path, S, case.base, case.batches) as eng:
         lib, h = eng.lib, eng.h
         empty = [(s, pc.kd(side, market, tif), mid, 5) for s in range(S) for side in (BUY, SELL) for market in (False, True)
                  for tif in range(4)]
@@ -128,7 +127,7 @@ def test_arguments_and_empty_books(me, path):
         assert not (got["flags"] & pm.PV_HAS_OPP).any() and not got["fill_count"].any()
         assert len(eng.order_preview([], [], [], [])) == 0
         assert lib.me_order_preview(h, None, 0, None) == me.ME_OK
-        eng.submit_batch(_b(me, case.batches[0]))
+        eng.submit_batch(as_batch(me, case.batches[0]))
         model.submit(case.batches[0])
         sy, kd_, px, qt = (np.array([0], dtype=np.uint32), np.array([pc.kd(BUY)], dtype=np.uint8),
                            np.array([mid + 1], dtype=np.int64), np.array([3], dtype=np.int32))
@@ -177,12 +176,12 @@ def test_read_only(me, path):
     S = case.S
     model = ReduceBook(S)
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, S, case.base, case.batches, **kw) as eng:
+    with engine_on(me, path, S, case.base, case.batches, **kw) as eng:
         eng.quotes_enable(1 << 14)
         eng.depth_enable(5, 1 << 15)
         eng.trades_enable(1 << 14)
         for a in case.batches[:-1]:
-            eng.submit_batch(_b(me, a))
+            eng.submit_batch(as_batch(me, a))
             model.submit(a)
         assert model.resting() > 100
         feeds = ((eng.quotes_drain, eng.quotes_stats), (eng.depth_drain, eng.depth_stats), (eng.trades_drain, eng.trades_stats))
@@ -206,7 +205,7 @@ def test_read_only(me, path):
             assert len(drain()) == 0 and st() == s0, f"{path}: a feed moved"
         # the next batch is stamped as if the preview had never been: it was no batch
         a = case.batches[-1]
-        r, f = eng.submit_batch(_b(me, a))
+        r, f = eng.submit_batch(as_batch(me, a))
         ro, fo = model.submit(a)
         assert_results_equal(r, ro, f"read-only {path} next batch")
         assert_fills_equal(f, fo, f"read-only {path} next batch")

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from tests import preview_model as pm
-from tests.test_quotes_service import FeedMatcher
+from tests.service_common import FeedMatcher
 
 pytestmark = pytest.mark.gpu
 

@@ -17,17 +17,16 @@ from tests import order_query_model as oq
 from tests import price_edges as pe
 from tests import quote_model as qm
 from tests._parity import assert_fills_equal, assert_results_equal, side_levels
+from tests.audit_run import Run
+from tests.gpu_harness import PATHS, SMALL, as_batch, engine_on, pipelined
+from tests.model_common import load_model_fixture
 from tests.price_edges import I64_MAX, I64_MIN
 from tests.reduce_model import ReduceBook
-from tests.test_book_audit_gpu import Run
-from tests.test_reduce_gpu import PATHS
-from tests.test_tif_gpu import _b, _env, _pipelined
 
 pytestmark = pytest.mark.gpu
 
 U64_MAX = (1 << 64) - 1
 S = pe.S_EDGE
-SMALL = [p for p in PATHS if PATHS[p][3]]  # the L = 128 paths: launch groups
 DEEP = [p for p in PATHS if not PATHS[p][3]]
 
 
@@ -38,20 +37,6 @@ def me(built):
     return matching_engine_amd
 
 
-def _engine(me, path, nsym, base, arrays, levels=None, **kw):
-    """An engine on `path` (its environment and expected paths() of tests.test_reduce_gpu.PATHS), its window size
-    `levels` when given."""
-    L, env, expect, _ = PATHS[path]
-    total = sum(len(a) for a in arrays)
-    kw.setdefault("max_resting", total + 1024)
-    with _env(env):
-        eng = me.Engine(nsym, levels or L, base, max_batch=max(len(a) for a in arrays), seq_ring=1 << 22, **kw)
-    p = eng.paths()
-    for k, v in expect.items():
-        assert p[k] == v, f"{path}: paths() {p}"
-    return eng
-
-
 def _bases(eng):
     return [int(b) for b in eng.debug_export(["sym"])["sym"]["base"]]
 
@@ -59,7 +44,7 @@ def _bases(eng):
 def _group(run, arrays, tag):
     """One launch group through engine and model (Run.group), then the device-wide resting counter; returns the
     ENGINE's (results, fills) per batch."""
-    bs = [_b(run.me, a) for a in arrays]
+    bs = [as_batch(run.me, a) for a in arrays]
     if run.grouped:
         tickets = [run.eng.submit_host(b) for b in bs]
         outs = [run.eng.collect(t) for t in tickets]
@@ -138,14 +123,14 @@ def test_streams(me, path, group, mode, d):
     if mode == "device":  # (every record of a device batch counts as one that may rest)
         kw["max_resting"] = 2 * sum(len(a) for a in arrays) + 1024
     used = set(int(x) for a in arrays for x in a.seq)
-    with _engine(me, path, S, base, arrays, far_levels=8, **kw) as eng:
+    with engine_on(me, path, S, base, arrays, far_levels=8, **kw) as eng:
         run = Run(me, eng, S, grouped, ctx)
         seen = [_bases(eng)]
         if mode in ("device", "pipelined"):
             if mode == "pipelined":
-                outs = _pipelined(eng, [_b(me, a) for a in arrays], 2 * group + 1)
+                outs = pipelined(eng, [as_batch(me, a) for a in arrays], 2 * group + 1)
             else:
-                dbs = [eng.upload(_b(me, a)) for a in arrays]
+                dbs = [eng.upload(as_batch(me, a)) for a in arrays]
                 try:
                     for db in dbs:
                         eng.submit_device(db)
@@ -204,7 +189,7 @@ def test_scripts(me, config, name):
     grouped = PATHS[path][3]
     kw = {"batches_per_launch": 1} if grouped else {}
     used = set(int(x) for a in case.batches for x in a.seq)
-    with _engine(me, path, case.S, case.base, case.batches, levels=L, **kw) as eng:
+    with engine_on(me, path, case.S, case.base, case.batches, levels=L, **kw) as eng:
         assert eng.config()["levels"] == L
         run = Run(me, eng, case.S, grouped, ctx)
         assert _bases(eng)[0] == min(int(case.base[0]), pe.top_base(L))
@@ -249,13 +234,13 @@ def test_feeds(me, path):
     model = ReduceBook(S)
     view = bq.Snap(model)
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, S, base, arrays, **kw) as eng:
+    with engine_on(me, path, S, base, arrays, **kw) as eng:
         eng.quotes_enable(4 * S * (len(arrays) + 2))
         eng.depth_enable(D, 8 * D * S * (len(arrays) + 2))
         table, maps = qm.tops(qm._Empty(), S), dm.empty_maps(S)
         ends = 0
         for k, a in enumerate(arrays):
-            r, f = eng.submit_batch(_b(me, a))
+            r, f = eng.submit_batch(as_batch(me, a))
             ro, fo = model.submit(a)
             assert_results_equal(r, ro, f"feeds {path} batch {k}")
             assert_fills_equal(f, fo, f"feeds {path} batch {k}")
@@ -274,13 +259,11 @@ def test_feeds(me, path):
 # ---- 4. the fixture ----------------------------------------------------------------------------------------------------
 
 def test_fixture_through_the_engine(me):
-    from tests.test_price_edges_model import load_price_edges_fixture
-
-    meta, batches, res, fills, book = load_price_edges_fixture()
+    meta, batches, res, fills, book = load_model_fixture("price_edges.npz")
     n = meta["num_symbols"]
-    with _engine(me, "reg", n, meta["base"], batches) as eng:
+    with engine_on(me, "reg", n, meta["base"], batches) as eng:
         for k, a in enumerate(batches):
-            r, f = eng.submit_batch(_b(me, a))
+            r, f = eng.submit_batch(as_batch(me, a))
             assert_results_equal(r, res[k], f"fixture batch {k}")
             assert_fills_equal(f, fills[k], f"fixture batch {k}")
         dumps = np.concatenate([eng.dump(s) for s in range(n)])

@@ -35,9 +35,9 @@ from tests import order_query_model as oq
 from tests import price_edges as pe
 from tests import quote_model as qm
 from tests.book_audit import audit
+from tests.model_common import FIELDS_BOOK, FIELDS_FILL, FIELDS_RES, load_model_fixture, same
 from tests.price_edges import I64_MAX, I64_MIN
 from tests.reduce_model import ReduceBook, check_seq_rule, is_reduce
-from tests.test_pybook_cross import FIELDS_BOOK, FIELDS_FILL, FIELDS_RES, same
 from tests.tif_model import Arrays
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -177,9 +177,9 @@ def test_helper_models_carry_these_prices(name):
 
 @pytest.mark.parametrize("L", [128, 1024])
 def test_audit_with_the_base_at_both_clamps(L):
-    """book_audit.audit over synthetic raw arrays (test_book_audit_model.build_image) of the clamps script's book
+    """book_audit.audit over synthetic raw arrays (audit_images.build_image) of the clamps script's book
     — a bid at INT64_MIN, an ask at INT64_MAX — with the window at the bottom and at the top of int64."""
-    from tests.test_book_audit_model import build_image
+    from tests.audit_images import build_image
 
     for b0 in (I64_MIN, pe.top_base(L)):
         case = pe.clamps(L, b0)
@@ -261,23 +261,8 @@ def test_wrong_models_differ_on_the_alias_scripts(L):
 
 # ---- the fixture ---------------------------------------------------------------------------------------------------
 
-def load_price_edges_fixture():
-    from oracle.pybook import BOOK_DTYPE, FILL_DTYPE, RESULT_DTYPE
-
-    z = np.load(os.path.join(ROOT, "tests", "golden", "price_edges.npz"))
-    batches, res, fills = [], [], []
-    for k in range(int(z["nbatches"][0])):
-        batches.append(Arrays(*[z[f"b{k}_{f}"] for f in ("seq", "price_q4", "qty", "symbol", "kind")]))
-        res.append(np.ascontiguousarray(z[f"b{k}_res"]).view(RESULT_DTYPE).reshape(-1))
-        fills.append(np.ascontiguousarray(z[f"b{k}_fills"]).view(FILL_DTYPE).reshape(-1))
-    book = np.ascontiguousarray(z["book"]).view(BOOK_DTYPE).reshape(-1)
-    meta = dict(num_symbols=int(z["num_symbols"][0]), levels=int(z["levels"][0]), base=z["base"],
-                book_counts=z["book_counts"])
-    return meta, batches, res, fills, book
-
-
 def test_fixture_replays_through_the_model():
-    meta, batches, res, fills, book = load_price_edges_fixture()
+    meta, batches, res, fills, book = load_model_fixture("price_edges.npz")
     S, L = meta["num_symbols"], meta["levels"]
     assert [int(b) for b in meta["base"]] == [int(b) for b in pe.bases(S, L)]
     m = ReduceBook(S)

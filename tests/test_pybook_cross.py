@@ -10,25 +10,13 @@ import numpy as np
 import pytest
 
 from tests._parity import load_fixture
+from tests.model_common import FIELDS_BOOK, FIELDS_FILL, FIELDS_RES, same
 
 @pytest.fixture(scope="module")
 def orc(built):
     from oracle import oracle
 
     return oracle
-
-
-FIELDS_RES = ("filled_qty", "remaining_qty", "fill_count", "tape_offset", "status", "reason")
-FIELDS_FILL = ("taker_seq", "maker_seq", "price_q4", "qty", "symbol")
-FIELDS_BOOK = ("seq", "price_q4", "qty", "side")
-
-
-def same(a, b, fields, ctx):
-    assert len(a) == len(b), f"{ctx}: {len(a)} vs {len(b)} entries"
-    for f in fields:
-        if not np.array_equal(np.asarray(a[f]), np.asarray(b[f])):
-            i = int(np.nonzero(np.asarray(a[f]) != np.asarray(b[f]))[0][0])
-            raise AssertionError(f"{ctx}: field {f} differs first at {i}: {a[i]} vs {b[i]}")
 
 
 @pytest.mark.parametrize("cid", [1, 2, 3, 4, 5, 6])

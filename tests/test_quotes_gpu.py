@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from tests import quote_model as qm
-from tests.feed_common import BIG, BUY, PATHS, SELL, SMALL, Rows, _c5_stream, _engine, _same
+from tests.feed_common import BIG, BUY, SELL, Rows, _c5_stream, _same
+from tests.gpu_harness import FEED_PATHS as PATHS, SMALL, feed_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +50,7 @@ def test_events_of_every_group_on_every_path(me, orc, path, group):
     ob = orc.OracleBook(S)
     model = qm.QuoteModel(ob, S)
     kw = {"batches_per_launch": group} if grouped else {}
-    with _engine(me, path, S, base, batch, 2 * total + 1024, **kw) as eng:
+    with feed_engine(me, path, S, base, batch, 2 * total + 1024, **kw) as eng:
         eng.quotes_enable(64 * S * (nb + 1))
         exp = [model.expect(0)]
         if grouped:
@@ -240,7 +241,7 @@ def test_host_pipeline_events_are_there_after_collect(me, orc, group):
     for b in batches:
         ob.submit(b)
         after.append(qm.tops(ob, S))
-    with _engine(me, "reg", S, base, batch, nb * batch + 1024, batches_per_launch=group) as eng:
+    with feed_engine(me, "reg", S, base, batch, nb * batch + 1024, batches_per_launch=group) as eng:
         eng.quotes_enable(64 * S * nb)
         got = np.zeros(0, dtype=qm.QUOTE_DTYPE)
         tickets = []
@@ -323,7 +324,7 @@ def test_enable_mid_stream(me, orc, path):
     S, L = 65, PATHS[path][0]
     base, batches = _c5_stream(me, S, L, 3, 300)
     ob = orc.OracleBook(S)
-    with _engine(me, path, S, base, 300, 2048) as eng:
+    with feed_engine(me, path, S, base, 300, 2048) as eng:
         for b in batches[:2]:
             eng.submit_batch(b)
             ob.submit(b)

@@ -3,7 +3,7 @@ stream after restart recovery, and the cluster's QUOTES collective over RCCL (wo
 import numpy as np
 import pytest
 
-from tests.test_quotes_service import BIG, BUY, SELL, _limit, _run_cluster
+from tests.service_common import BIG, BUY, SELL, _limit, _run_cluster
 
 pytestmark = pytest.mark.gpu
 

@@ -14,10 +14,11 @@ import pytest
 from tests import cancel_targets as ct
 from tests import reduce_model as rm
 from tests import tif_model as tm
-from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
+from tests._parity import assert_fills_equal, assert_results_equal
 from tests.big_qty import Script
+from tests.gpu_harness import PATHS, as_batch, check_books, engine_on, pipelined
+from tests.model_common import load_model_fixture
 from tests.reduce_model import INT32_MAX, KIND_REDUCE, ReduceBook
-from tests.test_tif_gpu import _b, _env, _pipelined
 from tests.tif_model import kind
 
 pytestmark = pytest.mark.gpu
@@ -26,16 +27,6 @@ BUY, SELL = 1, 2
 ST_NEW, ST_PARTIAL, ST_FILLED, ST_CANCELED, ST_REJECTED = 0, 1, 2, 3, 4
 RJ_NONE, RJ_BAD_QTY, RJ_UNKNOWN = 0, 1, 5
 
-# name -> (levels, environment, expected eng.paths(), grouped)
-PATHS = {
-    "reg": (128, {"ME_REG_AGG": "0"}, {"grouped_agg": False}, True),
-    "gwalk": (128, {"ME_REG_AGG": "1", "ME_GW_CANCEL": "0"}, {"grouped_agg": True, "grouped_cancels": False}, True),
-    "gwalk_cx": (128, {"ME_REG_AGG": "1", "ME_GW_CANCEL": "1"}, {"grouped_agg": True, "grouped_cancels": True}, True),
-    "deep256": (256, {"ME_HOT_MIN": "0"}, {"hot_agg": False}, False),
-    "deep": (1024, {"ME_HOT_MIN": "0"}, {"hot_agg": False}, False),
-    "hot_agg": (1024, {"ME_HOT_MIN": "64", "ME_HOT_AGG": "1"}, {"hot_agg": True}, False),
-    "hot": (2048, {"ME_HOT_MIN": "64", "ME_HOT_AGG": "0"}, {"hot_agg": False}, False),
-}
 DRAWS = range(10)
 
 
@@ -46,30 +37,13 @@ def me(built):
     return matching_engine_amd
 
 
-def _engine(me, path, S, base, arrays, ring=1 << 22, **kw):
-    L, env, expect, _ = PATHS[path]
-    total = sum(len(a) for a in arrays)
-    kw.setdefault("max_resting", total + 1024)
-    with _env(env):
-        eng = me.Engine(S, L, base, max_batch=max(len(a) for a in arrays), seq_ring=ring, **kw)
-    p = eng.paths()
-    for k, v in expect.items():
-        assert p[k] == v, f"{path}: paths() {p}"
-    return eng
-
-
-def _check_books(eng, model, ctx):
-    assert_books_equal(eng, model, range(eng.num_symbols), ctx)
-    assert eng.resting_count() == eng.admission()["resting"] == model.resting(), f"{ctx}: resting counters"
-
-
 def _step(eng, model, a, ctx, me):
     """One synchronous batch through engine and model: results, tape and every book."""
-    r, f = eng.submit_batch(_b(me, a))
+    r, f = eng.submit_batch(as_batch(me, a))
     ro, fo = model.submit(a)
     assert_results_equal(r, ro, ctx)
     assert_fills_equal(f, fo, ctx)
-    _check_books(eng, model, ctx)
+    check_books(eng, model, ctx)
     return ro, fo
 
 
@@ -94,17 +68,17 @@ def test_reduced_order_keeps_its_priority(me, path):
     second = sc.take()
     model = ReduceBook(1)
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, 1, base, [first, second], **kw) as eng:
-        eng.submit_batch(_b(me, first))
+    with engine_on(me, path, 1, base, [first, second], **kw) as eng:
+        eng.submit_batch(as_batch(me, first))
         model.submit(first)
-        r, f = eng.submit_batch(_b(me, second))
+        r, f = eng.submit_batch(as_batch(me, second))
         assert _st(r[0]) == (ST_NEW, RJ_NONE, 0, 6, 0)
         assert [(int(x["maker_seq"]), int(x["qty"])) for x in f] == [(A, 6), (B, 2)]
         assert [(int(e["seq"]), int(e["qty"])) for e in eng.dump(0)] == [(B, 8), (C, 10)]
         ro, fo = model.submit(second)
         assert_results_equal(r, ro, path)
         assert_fills_equal(f, fo, path)
-        _check_books(eng, model, path)
+        check_books(eng, model, path)
 
 
 # ---- slots: chunks, blocks, quantities ------------------------------------------------------------------------
@@ -157,7 +131,7 @@ def test_slots_chunks_and_blocks(me, path):
     sc.new(0, SELL, p - 2, 3)
     script.append(sc.take())
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, S, base, script, **kw) as eng:
+    with engine_on(me, path, S, base, script, **kw) as eng:
         outs = [_step(eng, model, a, f"slots {path} batch {k}", me) for k, a in enumerate(script)]
         # the script does what it says
         r = outs[1][0]
@@ -211,7 +185,7 @@ def test_far_levels_on_each_side(me, path):
     sc.reduce(0, fa[2], 1)
     script.append(sc.take())
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, S, base, script, **kw) as eng:
+    with engine_on(me, path, S, base, script, **kw) as eng:
         outs = [_step(eng, model, a, f"far {path} batch {k}", me) for k, a in enumerate(script)]
         assert [_st(r)[:4] for r in outs[1][0]] == [(ST_NEW, 0, 0, 5), (ST_NEW, 0, 0, 1), (ST_NEW, 0, 0, 7), (ST_NEW, 0, 0, 7)]
         assert [int(x["qty"]) for x in outs[2][1]] == [5, 5, 2, 5, 1, 2]
@@ -241,7 +215,7 @@ def test_target_older_than_the_ring_horizon(me, path):
          sc.reduce(0, A2, 1), sc.reduce(0, A, 1)]
     script.append(sc.take())
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, S, base, script, ring=R, **kw) as eng:
+    with engine_on(me, path, S, base, script, ring=R, **kw) as eng:
         outs = [_step(eng, model, a, f"old {path} batch {k}", me) for k, a in enumerate(script)]
         r = outs[-1][0]
         want = [(ST_NEW, 0, 0, 5), (ST_NEW, 0, 0, 1), None, (ST_NEW, 0, 0, 1), (ST_CANCELED, 0, 0, 1),
@@ -278,14 +252,14 @@ def test_hostile_targets_as_reduces(me, name, path, group):
     c = ct.CASES[name]
     assert PATHS[path][0] == c.levels
     base, arrays, exp, model = _hostile(name)
-    batches = [_b(me, a) for a in arrays]
+    batches = [as_batch(me, a) for a in arrays]
     kw = {"batches_per_launch": group} if PATHS[path][3] else {}
-    with _engine(me, path, ct.S_CX, base, arrays, ring=c.ring, **kw) as eng:
-        outs = _pipelined(eng, batches, 2 * group + 1) if PATHS[path][3] else [eng.submit_batch(b) for b in batches]
+    with engine_on(me, path, ct.S_CX, base, arrays, ring=c.ring, **kw) as eng:
+        outs = pipelined(eng, batches, 2 * group + 1) if PATHS[path][3] else [eng.submit_batch(b) for b in batches]
         for k, (ro, fo) in enumerate(exp):
             assert_results_equal(outs[k][0], ro, f"hostile {name} {path} batch {k}")
             assert_fills_equal(outs[k][1], fo, f"hostile {name} {path} batch {k}")
-        _check_books(eng, model, f"hostile {name} {path}")
+        check_books(eng, model, f"hostile {name} {path}")
 
 
 # ---- every path: seeded model streams ----------------------------------------------------------------------------
@@ -320,13 +294,13 @@ def _run_draw(me, shape, draw, path, group=1, mode="pipelined", **kw):
     S = SHAPES[shape][0]
     assert SHAPES[shape][1] == PATHS[path][0]
     base, arrays, exp, model, _ = _draw(shape, draw)
-    batches = [_b(me, a) for a in arrays]
+    batches = [as_batch(me, a) for a in arrays]
     ctx = f"{shape}#{draw} {path} G={group} {mode}"
     if PATHS[path][3]:
         kw["batches_per_launch"] = group
     if mode == "device":  # (every record of a device batch counts as one that may rest)
         kw["max_resting"] = 2 * sum(len(a) for a in arrays) + 1024
-    with _engine(me, path, S, base, arrays, **kw) as eng:
+    with engine_on(me, path, S, base, arrays, **kw) as eng:
         if mode == "device":
             dbs = [eng.upload(b) for b in batches]
             try:
@@ -339,13 +313,13 @@ def _run_draw(me, shape, draw, path, group=1, mode="pipelined", **kw):
                 for db in dbs:
                     db.free()
         elif mode == "pipelined":
-            outs = _pipelined(eng, batches, 2 * group + 1)
+            outs = pipelined(eng, batches, 2 * group + 1)
         else:
             outs = [eng.submit_batch(b) for b in batches]
         for k, (ro, fo) in enumerate(exp):
             assert_results_equal(outs[k][0], ro, f"{ctx} batch {k}")
             assert_fills_equal(outs[k][1], fo, f"{ctx} batch {k}")
-        _check_books(eng, model, ctx)
+        check_books(eng, model, ctx)
         return eng.stats()
 
 
@@ -389,13 +363,11 @@ def test_streams_on_the_other_submit_paths(me, mode, draw):
 
 
 def test_fixture_through_the_engine(me):
-    from tests.test_reduce_model import load_reduce_fixture
-
-    meta, batches, res, fills, book = load_reduce_fixture()
+    meta, batches, res, fills, book = load_model_fixture("match_reduce.npz")
     S = meta["num_symbols"]
-    with _engine(me, "reg", S, meta["base"], batches) as eng:
+    with engine_on(me, "reg", S, meta["base"], batches) as eng:
         for k, a in enumerate(batches):
-            r, f = eng.submit_batch(_b(me, a))
+            r, f = eng.submit_batch(as_batch(me, a))
             assert_results_equal(r, res[k], f"fixture batch {k}")
             assert_fills_equal(f, fills[k], f"fixture batch {k}")
         dumps = np.concatenate([eng.dump(s) for s in range(S)])
@@ -431,7 +403,7 @@ def test_quote_and_depth_feeds_follow_a_reduce(me, path):
     sc.reduce(0, deep[-2], 9)  # (m-5 is the fifth level: outside the view too)
     below = sc.take()
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, S, base, [build, at_top, below], **kw) as eng:
+    with engine_on(me, path, S, base, [build, at_top, below], **kw) as eng:
         _step(eng, model, build, "feeds build", me)
         eng.quotes_enable(64)
         eng.depth_enable(D, 256)
@@ -490,14 +462,14 @@ def test_full_book_accepts_a_batch_of_reduces(me):
         g = Script(sc.next)
         for i in range(64):
             g.new(i % S, BUY, int(base[i % S]) + 10, 1)
-        gtc = _b(me, g.take())
+        gtc = as_batch(me, g.take())
         with pytest.raises(me.EngineError) as ei:
             eng.submit_batch(gtc)
         assert ei.value.code == me.ME_E_CAPACITY
         for j, (s, t) in enumerate(ids):
             sc.reduce(s, t, (3, 10, 9, 11)[j % 4])
         red = sc.take()
-        assert eng.admits(_b(me, red))
+        assert eng.admits(as_batch(me, red))
         ro, _ = _step(eng, model, red, "reduces on a full book", me)
         assert (ro["status"] == ST_NEW).sum() == R // 2 and (ro["status"] == ST_CANCELED).sum() == R // 2
         assert model.resting() == R // 2

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from tests import reduce_model as rm
+from tests.model_common import FIELDS_BOOK, FIELDS_FILL, FIELDS_RES, load_model_fixture, same
 from tests.reduce_model import INT32_MAX, KIND_REDUCE, ReduceBook
 from tests.tif_model import TIF_FOK, TIF_IOC, Arrays, TifBook, kind
 
@@ -25,9 +26,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUY, SELL = 1, 2
 ST_NEW, ST_PARTIAL, ST_FILLED, ST_CANCELED, ST_REJECTED = 0, 1, 2, 3, 4
 RJ_NONE, RJ_BAD_QTY, RJ_BAD_SYMBOL, RJ_UNKNOWN = 0, 1, 4, 5
-FIELDS_RES = ("filled_qty", "remaining_qty", "fill_count", "tape_offset", "status", "reason")
-FIELDS_FILL = ("taker_seq", "maker_seq", "price_q4", "qty", "symbol")
-FIELDS_BOOK = ("seq", "price_q4", "qty", "side")
 CX = kind(BUY, 0, 1)
 RD = KIND_REDUCE
 
@@ -37,14 +35,6 @@ def orc(built):
     from oracle import oracle
 
     return oracle
-
-
-def same(a, b, fields, ctx):
-    assert len(a) == len(b), f"{ctx}: {len(a)} vs {len(b)} entries"
-    for f in fields:
-        if not np.array_equal(np.asarray(a[f]), np.asarray(b[f])):
-            i = int(np.nonzero(np.asarray(a[f]) != np.asarray(b[f]))[0][0])
-            raise AssertionError(f"{ctx}: field {f} differs first at {i}: {a[i]} vs {b[i]}")
 
 
 # ---- hand cases ----------------------------------------------------------------------------------
@@ -250,23 +240,8 @@ def test_rewrite_pins_the_model_to_the_native_oracle(pinned):
 
 # ---- the committed fixture ---------------------------------------------------------------------------
 
-def load_reduce_fixture():
-    z = np.load(os.path.join(ROOT, "tests", "golden", "match_reduce.npz"))
-    from oracle.pybook import BOOK_DTYPE, FILL_DTYPE, RESULT_DTYPE
-
-    batches, res, fills = [], [], []
-    for k in range(int(z["nbatches"][0])):
-        batches.append(Arrays(*[z[f"b{k}_{f}"] for f in ("seq", "price_q4", "qty", "symbol", "kind")]))
-        res.append(np.ascontiguousarray(z[f"b{k}_res"]).view(RESULT_DTYPE).reshape(-1))
-        fills.append(np.ascontiguousarray(z[f"b{k}_fills"]).view(FILL_DTYPE).reshape(-1))
-    book = np.ascontiguousarray(z["book"]).view(BOOK_DTYPE).reshape(-1)
-    meta = dict(num_symbols=int(z["num_symbols"][0]), levels=int(z["levels"][0]), base=z["base"],
-                book_counts=z["book_counts"])
-    return meta, batches, res, fills, book
-
-
 def test_fixture_replays_through_the_model():
-    meta, batches, res, fills, book = load_reduce_fixture()
+    meta, batches, res, fills, book = load_model_fixture("match_reduce.npz")
     rb = ReduceBook(meta["num_symbols"])
     outcomes = set()
     for k, b in enumerate(batches):
@@ -284,7 +259,7 @@ def test_fixture_generator_reproduces_the_committed_file():
     from tests.golden import make_reduce_golden as g
 
     base, batches = rm.reduce_stream(20261020, g.S, g.L, g.NB, g.N, far_pct=2, drift=3, skew=True)
-    meta, fb, _, _, _ = load_reduce_fixture()
+    meta, fb, _, _, _ = load_model_fixture("match_reduce.npz")
     assert np.array_equal(base, meta["base"])
     for a, b in zip(batches, fb):
         for f in ("seq", "price_q4", "qty", "symbol", "kind"):

@@ -14,9 +14,8 @@ from tests import order_query_model as oq
 from tests import seq_edges as se
 from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
 from tests.book_audit import audit, names
+from tests.gpu_harness import PATHS, as_batch, engine_on, env
 from tests.reduce_model import ReduceBook
-from tests.test_reduce_gpu import PATHS
-from tests.test_tif_gpu import _b, _env
 
 pytestmark = pytest.mark.gpu
 
@@ -32,18 +31,6 @@ def me(built):
     return matching_engine_amd
 
 
-def _engine(me, path, S, base, arrays, group, ring):
-    L, env, expect, grouped = PATHS[path]
-    kw = {"batches_per_launch": group} if grouped else {}
-    with _env(env):
-        eng = me.Engine(S, L, base, max_batch=max(len(a) for a in arrays), seq_ring=ring,
-                        max_resting=sum(len(a) for a in arrays) + 1024, **kw)
-    p = eng.paths()
-    for k, v in expect.items():
-        assert p[k] == v, f"{path}: paths() {p}"
-    return eng
-
-
 class Run:
     """One engine against ReduceBook; `group` runs one launch group through both (pipelined host batches, one
     device group, or synchronous batches on the ungrouped paths) and checks everything the engine says and
@@ -56,7 +43,7 @@ class Run:
         self.last_seq = 0
 
     def group(self, arrays, tag):
-        eng, bs, ctx = self.eng, [_b(self.me, a) for a in arrays], f"{self.ctx} {tag}"
+        eng, bs, ctx = self.eng, [as_batch(self.me, a) for a in arrays], f"{self.ctx} {tag}"
         if not self.grouped:
             outs = [eng.submit_batch(b) for b in bs]
         elif self.mode == "host":
@@ -92,7 +79,7 @@ class Run:
 def _run_case(me, path, case, mode):
     grouped = PATHS[path][3]
     ctx = f"{case.name} [{path} {mode}]"
-    with _engine(me, path, case.S, case.base, case.batches, max(case.groups), case.ring) as eng:
+    with engine_on(me, path, case.S, case.base, case.batches, group=max(case.groups), ring=case.ring) as eng:
         run = Run(me, eng, case.S, path, mode, ctx)
         k = 0
         for gi, g in enumerate(case.groups):
@@ -153,7 +140,7 @@ def _run_overlay(me, path, seed, group, ring, plain=False, high=False):
     for k in range(0, len(arrays), group):  # a launch group has to span fewer seqs than the ring
         assert int(arrays[min(k + group, len(arrays)) - 1].seq[-1]) - int(arrays[k].seq[0]) < ring
     cancelled = 0
-    with _engine(me, path, OS, base, arrays, group, ring) as eng:
+    with engine_on(me, path, OS, base, arrays, group=group, ring=ring) as eng:
         run = Run(me, eng, OS, path, "host", f"overlay {path} #{seed} G={group} ring={ring} plain={plain}")
         for k in range(0, len(arrays), group):
             res, raw = run.group(arrays[k:k + group], f"batches {k}..")
@@ -202,8 +189,8 @@ def test_service_cancel_of_the_last_order(me):
     accepted order is its slice's first record and repeats its target's seq. The engine behind the service is
     created under the gwalk_cx environment, so the cancel walk answers (asserted through paths())."""
     LIMIT, BUY, SELL, MID = 0, 1, 2, 1_000_000
-    L, env, expect, _ = PATHS["gwalk_cx"]
-    with _env(env):
+    L, row_env, expect, _ = PATHS["gwalk_cx"]
+    with env(row_env):
         eng = me.Engine(2, L, [MID - L // 2, MID - L // 2], max_batch=1024, max_resting=1024, batches_per_launch=1)
     with eng:
         p = eng.paths()

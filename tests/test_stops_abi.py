@@ -59,7 +59,7 @@ def test_me_stop_event_is_64_bytes_and_matches_the_header(built):
 
 def test_library_exports_exactly_the_six_calls(built):
     from matching_engine_amd import _abi
-    from tests.test_abi import declared_functions
+    from tests.abi_layout import declared_functions
 
     lib = C.CDLL(_abi.LIB_PATH)
     for name in EXPORTS:

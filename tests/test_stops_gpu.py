@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from tests import stops_model as sm
-from tests.feed_common import BUY, PATHS, SELL, SMALL, Rows, _c5_stream, _engine, _same
+from tests.feed_common import BUY, SELL, Rows, _c5_stream, _same
+from tests.gpu_harness import FEED_PATHS as PATHS, SMALL, feed_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -123,7 +124,7 @@ def test_events_of_every_group_on_every_path(me, orc, path, group):
     assert two or group == 1
     total = nb * batch
     kw = {"batches_per_launch": group} if grouped else {}
-    with _engine(me, path, S_PATHS, base, batch, 2 * total + 1024, **kw) as eng:
+    with feed_engine(me, path, S_PATHS, base, batch, 2 * total + 1024, **kw) as eng:
         eng.stops_enable(len(stops))
         eng.stops_add(stops)
         _no_deferral(eng, jobs=0, events=0, live=len(stops))
@@ -233,7 +234,7 @@ def test_a_stop_sees_only_batches_submitted_after_it(me, orc, group):
     base = np.array([10_000, 20_000], dtype=np.int64)
     model = sm.StopModel(S)
     ob = orc.OracleBook(S)
-    with _engine(me, "reg", S, base, 64, 1024, batches_per_launch=group) as eng:
+    with feed_engine(me, "reg", S, base, 64, 1024, batches_per_launch=group) as eng:
         eng.stops_enable(8)
         before = sm.stops([(1, P, 0, 1, 0, me.kind(BUY, 1)), (2, P + 50, 0, 1, 0, me.kind(BUY, 1))])
         eng.stops_add(before)
@@ -444,7 +445,7 @@ def test_the_feeds_and_the_outputs_do_not_depend_on_it(me, path):
 
     def run(stops):
         kw = {"batches_per_launch": 4} if grouped else {}
-        with _engine(me, path, S, base, batch, 2 * nb * batch + 1024, **kw) as eng:
+        with feed_engine(me, path, S, base, batch, 2 * nb * batch + 1024, **kw) as eng:
             eng.quotes_enable(64 * S)
             eng.depth_enable(4, 64 * 16 * S)
             eng.trades_enable(64 * S)

@@ -102,7 +102,7 @@ def test_every_matcher_the_package_builds_is_the_whole_struct(built):
 
 def test_exports_and_null_refusals(built):
     from matching_engine_amd import _abi
-    from tests.test_abi import declared_functions
+    from tests.abi_layout import declared_functions
 
     lib = C.CDLL(_abi.LIB_PATH)
     for name in EXPORTS:

@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 
 from tests import tif_model as tm
-from tests._parity import assert_books_equal, assert_fills_equal, assert_results_equal
-from tests.feed_common import PATHS, SMALL, _env  # (other test files import them from here)
+from tests._parity import assert_fills_equal, assert_results_equal
+from tests.gpu_harness import FEED_PATHS as PATHS, SMALL, as_batch, check_books, engine_on, pipelined
+from tests.model_common import load_model_fixture
 from tests.tif_model import TIF_FOK, TIF_GTC, TIF_IOC, TIF_POST_ONLY, TifBook, kind
 
 pytestmark = pytest.mark.gpu
@@ -26,33 +27,8 @@ def me(built):
     return matching_engine_amd
 
 
-def _engine(me, path, S, base, batches, env_over=None, **kw):
-    L, env, expect, _ = PATHS[path]
-    env = dict(env, **(env_over or {}))
-    total = sum(len(b) for b in batches)
-    kw.setdefault("max_resting", total + 1024)
-    with _env(env):
-        eng = me.Engine(S, L, base, max_batch=max(len(b) for b in batches), seq_ring=1 << 22, **kw)
-    p = eng.paths()
-    for k, v in expect.items():
-        assert p[k] == v, f"{path}: paths() {p}"
-    return eng
-
-
-def _b(me, a):
-    return me.Batch(a.seq, a.price_q4, a.qty, a.symbol, a.kind)
-
-
-def _pipelined(eng, batches, lag):
-    out, tickets = [None] * len(batches), []
-    for k, b in enumerate(batches):
-        tickets.append((k, eng.submit_host(b)))
-        while len(tickets) > lag:
-            j, t = tickets.pop(0)
-            out[j] = eng.collect(t)
-    for j, t in tickets:
-        out[j] = eng.collect(t)
-    return out
+def _engine(me, path, S, base, batches, **kw):
+    return engine_on(me, path, S, base, batches, table=PATHS, **kw)
 
 
 def _check_outputs(tb, batches, outs, ctx):
@@ -65,25 +41,19 @@ def _check_outputs(tb, batches, outs, ctx):
     return exp
 
 
-def _check_books(eng, tb, ctx):
-    assert_books_equal(eng, tb, range(eng.num_symbols), ctx)
-    assert eng.resting_count() == tb.resting(), f"{ctx}: resting count"
-    assert eng.admission()["resting"] == tb.resting(), f"{ctx}: ST_RESTING counter"
-
-
 def _run(me, path, S, base, arrays, group=1, ctx="", env_over=None):
     """The batches through one engine of `path` (pipelined host batches in groups for L <= 128) against a
     fresh model; returns (engine stats, model)."""
-    batches = [_b(me, a) for a in arrays]
+    batches = [as_batch(me, a) for a in arrays]
     tb = TifBook(S)
     kw = {"batches_per_launch": group} if PATHS[path][3] else {}
     with _engine(me, path, S, base, batches, env_over=env_over, **kw) as eng:
         if PATHS[path][3]:
-            outs = _pipelined(eng, batches, 2 * group + 1)
+            outs = pipelined(eng, batches, 2 * group + 1)
         else:
             outs = [eng.submit_batch(b) for b in batches]
         _check_outputs(tb, arrays, outs, ctx)
-        _check_books(eng, tb, ctx)
+        check_books(eng, tb, ctx)
         return eng.stats(), tb
 
 
@@ -241,13 +211,11 @@ def test_random_stream_on_every_path(me, path, group):
 
 
 def test_fixture_through_the_engine(me):
-    from tests.test_tif_model import load_tif_fixture
-
-    meta, batches, res, fills, book = load_tif_fixture()
+    meta, batches, res, fills, book = load_model_fixture("match_tif.npz")
     S = meta["num_symbols"]
-    with _engine(me, "reg", S, meta["base"], [_b(me, a) for a in batches]) as eng:
+    with _engine(me, "reg", S, meta["base"], [as_batch(me, a) for a in batches]) as eng:
         for k, a in enumerate(batches):
-            r, f = eng.submit_batch(_b(me, a))
+            r, f = eng.submit_batch(as_batch(me, a))
             assert_results_equal(r, res[k], f"fixture batch {k}")
             assert_fills_equal(f, fills[k], f"fixture batch {k}")
         dumps = np.concatenate([eng.dump(s) for s in range(S)])
@@ -261,9 +229,9 @@ def test_killed_and_rejected_change_nothing(me, path):
     base, arrays = tm.tif_stream(31, S, L, 2, 1000, far_pct=2, mix=(70, 10, 0, 0, 10, 10))
     tb = TifBook(S)
     seq = int(max(a.seq.max() for a in arrays)) + 1
-    with _engine(me, path, S, base, [_b(me, a) for a in arrays]) as eng:
+    with _engine(me, path, S, base, [as_batch(me, a) for a in arrays]) as eng:
         for a in arrays:
-            eng.submit_batch(_b(me, a))
+            eng.submit_batch(as_batch(me, a))
             tb.submit(a)
         sc = Script(seq)
         for s in range(S):
@@ -279,7 +247,7 @@ def test_killed_and_rejected_change_nothing(me, path):
         before = [eng.dump(s) for s in range(S)]
         rest0, hw0 = eng.resting_count(), eng.chunk_stats()["high_water"]
         a = sc.arrays()
-        r, f = eng.submit_batch(_b(me, a))
+        r, f = eng.submit_batch(as_batch(me, a))
         ro, fo = tb.submit(a)
         assert_results_equal(r, ro, path)
         assert len(f) == 0 and len(fo) == 0
@@ -333,7 +301,7 @@ def test_full_book_accepts_ioc_and_fok(me):
     fill = sc.arrays()
     tb = TifBook(S)
     with me.Engine(S, L, base, max_batch=1024, max_resting=R, seq_ring=1 << 20) as eng:
-        r, f = eng.submit_batch(_b(me, fill))
+        r, f = eng.submit_batch(as_batch(me, fill))
         tb.submit(fill)
         assert eng.admission()["resting"] == R
 
@@ -344,7 +312,7 @@ def test_full_book_accepts_ioc_and_fok(me):
             return g.arrays()
 
         with pytest.raises(me.EngineError) as ei:
-            eng.submit_batch(_b(me, gtc(sc.seq)))
+            eng.submit_batch(as_batch(me, gtc(sc.seq)))
         assert ei.value.code == me.ME_E_CAPACITY
         t = Script(sc.seq)
         for i in range(400):
@@ -354,34 +322,34 @@ def test_full_book_accepts_ioc_and_fok(me):
             px = mid + (3 if side == BUY else -3)
             t.new(s, side, px, 1 + i % 25, tif=(TIF_IOC, TIF_FOK)[i % 3 == 0])
         a = t.arrays()
-        r, f = eng.submit_batch(_b(me, a))
+        r, f = eng.submit_batch(as_batch(me, a))
         ro, fo = tb.submit(a)
         assert_results_equal(r, ro, "IOC/FOK on a full book")
         assert_fills_equal(f, fo, "IOC/FOK on a full book")
         assert len(fo) > 100
-        _check_books(eng, tb, "full book")
+        check_books(eng, tb, "full book")
         room = R - tb.resting()
         assert 0 < room < 512
         g = Script(t.seq)
         for i in range(room + 1):
             g.new(i % S, BUY, int(base[i % S]) + 10, 1)
         with pytest.raises(me.EngineError) as ei:
-            eng.submit_batch(_b(me, g.arrays()))
+            eng.submit_batch(as_batch(me, g.arrays()))
         assert ei.value.code == me.ME_E_CAPACITY
         p = Script(t.seq)  # POST_ONLY may rest: it counts
         for i in range(room + 1):
             p.new(i % S, BUY, int(base[i % S]) + 10, 1, tif=TIF_POST_ONLY)
         with pytest.raises(me.EngineError) as ei:
-            eng.submit_batch(_b(me, p.arrays()))
+            eng.submit_batch(as_batch(me, p.arrays()))
         assert ei.value.code == me.ME_E_CAPACITY
-        _check_books(eng, tb, "after the refusals")
+        check_books(eng, tb, "after the refusals")
 
 
 @pytest.mark.parametrize("path", SMALL)
 def test_device_batches_one_group(me, path):
     S, L = 12, 128
     base, arrays = tm.tif_stream(41, S, L, 8, 1200, far_pct=2, skew=True)
-    batches = [_b(me, a) for a in arrays]
+    batches = [as_batch(me, a) for a in arrays]
     tb = TifBook(S)
     total = sum(len(b) for b in batches)
     # every record of a device batch counts as one that may rest
@@ -397,4 +365,4 @@ def test_device_batches_one_group(me, path):
             for db in dbs:
                 db.free()
         _check_outputs(tb, arrays, outs, f"device {path}")
-        _check_books(eng, tb, f"device {path}")
+        check_books(eng, tb, f"device {path}")

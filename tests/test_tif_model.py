@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from tests import tif_model as tm
+from tests.model_common import FIELDS_BOOK, FIELDS_FILL, FIELDS_RES, load_model_fixture, same
 from tests.tif_model import (RJ_BAD_TIF, RJ_WOULD_CROSS, TIF_FOK, TIF_GTC, TIF_IOC, TIF_POST_ONLY, Arrays, TifBook,
                              kind)
 
@@ -26,9 +27,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUY, SELL = 1, 2
 ST_NEW, ST_PARTIAL, ST_FILLED, ST_CANCELED, ST_REJECTED = 0, 1, 2, 3, 4
 RJ_NONE, RJ_BAD_QTY, RJ_BAD_SIDE, RJ_UNKNOWN, RJ_BAD_SEQ = 0, 1, 2, 5, 6
-FIELDS_RES = ("filled_qty", "remaining_qty", "fill_count", "tape_offset", "status", "reason")
-FIELDS_FILL = ("taker_seq", "maker_seq", "price_q4", "qty", "symbol")
-FIELDS_BOOK = ("seq", "price_q4", "qty", "side")
 
 
 @pytest.fixture(scope="module")
@@ -36,14 +34,6 @@ def orc(built):
     from oracle import oracle
 
     return oracle
-
-
-def same(a, b, fields, ctx):
-    assert len(a) == len(b), f"{ctx}: {len(a)} vs {len(b)} entries"
-    for f in fields:
-        if not np.array_equal(np.asarray(a[f]), np.asarray(b[f])):
-            i = int(np.nonzero(np.asarray(a[f]) != np.asarray(b[f]))[0][0])
-            raise AssertionError(f"{ctx}: field {f} differs first at {i}: {a[i]} vs {b[i]}")
 
 
 @pytest.mark.parametrize("seed", [1, 2])
@@ -231,23 +221,8 @@ def test_abi_declares_and_exports_the_tif_entry(built):
 
 # ---- the committed fixture ----------------------------------------------------------------------
 
-def load_tif_fixture():
-    z = np.load(os.path.join(ROOT, "tests", "golden", "match_tif.npz"))
-    from oracle.pybook import BOOK_DTYPE, FILL_DTYPE, RESULT_DTYPE
-
-    batches, res, fills = [], [], []
-    for k in range(int(z["nbatches"][0])):
-        batches.append(Arrays(*[z[f"b{k}_{f}"] for f in ("seq", "price_q4", "qty", "symbol", "kind")]))
-        res.append(np.ascontiguousarray(z[f"b{k}_res"]).view(RESULT_DTYPE).reshape(-1))
-        fills.append(np.ascontiguousarray(z[f"b{k}_fills"]).view(FILL_DTYPE).reshape(-1))
-    book = np.ascontiguousarray(z["book"]).view(BOOK_DTYPE).reshape(-1)
-    meta = dict(num_symbols=int(z["num_symbols"][0]), levels=int(z["levels"][0]), base=z["base"],
-                book_counts=z["book_counts"])
-    return meta, batches, res, fills, book
-
-
 def test_fixture_replays_through_the_model():
-    meta, batches, res, fills, book = load_tif_fixture()
+    meta, batches, res, fills, book = load_model_fixture("match_tif.npz")
     tb = TifBook(meta["num_symbols"])
     tifs = set()
     for k, b in enumerate(batches):

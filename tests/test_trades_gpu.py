@@ -11,7 +11,8 @@ import pytest
 
 from tests import price_edges as pe
 from tests import trade_model as tm
-from tests.feed_common import BIG, BUY, PATHS, SELL, SMALL, Rows, _c5_stream, _engine, _same
+from tests.feed_common import BIG, BUY, SELL, Rows, _c5_stream, _same
+from tests.gpu_harness import FEED_PATHS as PATHS, SMALL, env, feed_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -88,7 +89,7 @@ def test_events_of_every_group_on_every_path(me, orc, path, group):
     assert two or group == 1
     total = nb * batch
     kw = {"batches_per_launch": group} if grouped else {}
-    with _engine(me, path, S_PATHS, base, batch, 2 * total + 1024, **kw) as eng:
+    with feed_engine(me, path, S_PATHS, base, batch, 2 * total + 1024, **kw) as eng:
         eng.trades_enable(S_PATHS * (len(bounds) + 1))
         assert eng.trades_stats() == {"groups": 1, "events": 0, "deferred": 0}
         got = []
@@ -193,14 +194,13 @@ def test_the_folds_other_forms_give_the_same_events(me, orc, form):
     lane its own atomics to HBM, 1 a one-symbol wave reduces first, 2 the LDS table without that reduction; the
     shipped form is 3. 1,030 symbols (slots shared by two symbols of one workgroup), one symbol with whole
     waves of its own, a 70-fill run."""
-    from tests.feed_common import _env
 
     S, L = 1030, 128
     base = np.array([10_000 + 1_000 * s for s in range(S)], dtype=np.int64)
     ob = orc.OracleBook(S)
     model = tm.TradeModel(S)
     with me.Engine(S, L, base, max_batch=2 * S + 512, max_resting=8 * S + 1024, seq_ring=1 << 20) as eng:
-        with _env({"ME_TRADE_FOLD": form}):
+        with env({"ME_TRADE_FOLD": form}):
             eng.trades_enable(4 * S)
         rows = Rows(me)
         for k in range(2):
@@ -228,7 +228,7 @@ def test_long_runs_are_read_by_the_wave(me, orc, path):
     ob = orc.OracleBook(S)
     model = tm.TradeModel(S)
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
-    with _engine(me, path, S, base, 256, 4096, **kw) as eng:
+    with feed_engine(me, path, S, base, 256, 4096, **kw) as eng:
         eng.trades_enable(64)
         rows = Rows(me)
         nbat = 0
@@ -306,7 +306,7 @@ def test_prices_at_the_ends_of_int64(me, path):
     model = tm.TradeModel(case.S)
     kw = {"batches_per_launch": 1} if PATHS[path][3] else {}
     seen = {"open": set(), "last": set(), "high": set(), "low": set()}
-    with _engine(me, path, case.S, case.base, max(len(a) for a in case.batches), 4096, far_levels=8, **kw) as eng:
+    with feed_engine(me, path, case.S, case.base, max(len(a) for a in case.batches), 4096, far_levels=8, **kw) as eng:
         eng.trades_enable(64)
         for k, a in enumerate(case.batches):
             b = me.Batch(a.seq, a.price_q4, a.qty, a.symbol, a.kind)
@@ -367,7 +367,7 @@ def test_host_pipeline_events_are_there_after_collect(me, orc, group):
             return False
         return True
 
-    with _engine(me, "reg", S, base, batch, nb * batch + 1024, batches_per_launch=group) as eng:
+    with feed_engine(me, "reg", S, base, batch, nb * batch + 1024, batches_per_launch=group) as eng:
         eng.trades_enable(64 * S * nb)
         got = np.zeros(0, dtype=tm.TRADE_DTYPE)
         tickets = []
@@ -453,7 +453,7 @@ def test_enable_mid_stream(me, orc, path):
     S, L = 65, PATHS[path][0]
     base, batches = _c5_stream(me, S, L, 4, 300)
     ob = orc.OracleBook(S)
-    with _engine(me, path, S, base, 300, 4096) as eng:
+    with feed_engine(me, path, S, base, 300, 4096) as eng:
         for b in batches[:2]:
             eng.submit_batch(b)
             assert len(ob.submit(b)[1]) > 0  # fills before the feed is on: not counted
@@ -502,7 +502,7 @@ def test_the_other_feeds_and_the_outputs_do_not_depend_on_it(me, path):
 
     def run(trades):
         kw = {"batches_per_launch": 4} if grouped else {}
-        with _engine(me, path, S, base, batch, 2 * nb * batch + 1024, **kw) as eng:
+        with feed_engine(me, path, S, base, batch, 2 * nb * batch + 1024, **kw) as eng:
             eng.quotes_enable(64 * S)
             eng.depth_enable(4, 64 * 16 * S)
             if trades:

@@ -4,7 +4,7 @@ import ctypes as C
 
 import pytest
 
-from tests.test_quotes_service import FeedMatcher
+from tests.service_common import FeedMatcher
 
 
 @pytest.fixture(scope="module")
